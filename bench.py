@@ -10,11 +10,10 @@ BASELINE configs.  N>1: one process per GPU, reads sharded by rank (every rank h
 16-byte RCCL all-gather per step for the merged-output offsets.
 
     python bench.py --gpus 1 --steps 5 --warmup 2
+    python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    (also: the last timed step's records for a seeded sample, DIR/*.npy)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
-import os as _os
-_os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")   # (read when the HIP runtime starts, as airlift-align sets it: a context has nine streams and a kernel that runs for 100 ms on one must not share a hardware queue with the main stream; the default is 4)
 import ctypes as C
 import json
 import os
@@ -250,6 +249,57 @@ def load_traffic(kernel):
     return (e["bytes_per_launch"], t.get("source")) if e else (None, t.get("source"))
 
 
+# --dump-outputs: what al_batch_fetch hands the caller of the timed path for a fixed sample of the batch's fragments, so that two
+# builds can be compared output for output on the same inputs
+DUMP_SEED, DUMP_FRAGS, DUMP_BYTES = 20261002, 65536, 64_000_000
+REG_INT = ["id", "cnt", "rid", "score", "qs", "qe", "rs", "re", "parent", "subsc", "mlen", "blen", "n_sub", "score0"]
+REG_BITS = [("mapq", 0, 8), ("split", 8, 2), ("rev", 10, 1), ("inv", 11, 1), ("sam_pri", 12, 1), ("proper_frag", 13, 1), ("pe_thru", 14, 1),
+            ("seg_split", 15, 1), ("seg_id", 16, 8), ("split_inv", 24, 1)]           # (name, shift, width) in al_reg1_t's bit-field word
+REG_TAIL = ["hash", "dp_score", "dp_max", "dp_max2", "n_ambi", "n_cigar"]
+REG_COLUMNS = ["read"] + REG_INT + [b[0] for b in REG_BITS] + REG_TAIL
+REG_DT = np.dtype([(n, "<i4") for n in REG_INT] + [("bits", "<u4"), ("hash", "<u4"), ("dp_score", "<i4"), ("dp_max", "<i4"), ("dp_max2", "<i4"),
+                   ("n_ambi", "<u4"), ("n_cigar", "<u4"), ("pad", "<u4"), ("cigar", "<u8")])     # al_reg1_t (include/airlift.h), 96 bytes
+
+
+def dump_outputs(ctx, out_dir):
+    """Writes what al_batch_fetch returns for the context's last al_batch_run -- per read its records (al_reg1_t) with their
+    CIGARs, per fragment rep_len -- for a seeded sample of the fragments (two reads each), as float64 arrays, at most DUMP_BYTES in all:
+    frags.npy (sampled fragment indices, ascending), rep_len.npy (per sampled fragment), n_regs.npy (per read of those fragments,
+    mate 1 then mate 2), regs.npy (one row per record, columns REG_COLUMNS; `read` is the read's index in the batch) and cigar.npy
+    (the records' BAM-encoded CIGAR words, concatenated in row order; a row's count is its n_cigar)."""
+    n_regs, regs, rep = ctx.fetch()
+    nf, nr = ctx.n_frag, ctx.n_reads
+    assert nr == 2 * nf
+    cnt = np.ctypeslib.as_array(n_regs).astype(np.int64)
+    ptr = np.frombuffer(regs, dtype=np.uint64)
+    have = np.flatnonzero(cnt)
+    recs = np.frombuffer(b"".join(C.string_at(int(ptr[i]), int(cnt[i]) * REG_DT.itemsize) for i in have), dtype=REG_DT)
+    rec_read = np.repeat(np.arange(nr), cnt)
+    frags = np.sort(np.random.default_rng(DUMP_SEED).choice(nf, size=min(nf, DUMP_FRAGS), replace=False))
+    # bytes per sampled fragment: its index, rep_len, two n_regs, its records' rows and CIGAR words; the sample is cut where the budget ends
+    rec_frag = rec_read // 2
+    row_bytes = 8 * (len(REG_COLUMNS) + recs["n_cigar"].astype(np.int64))
+    frag_bytes = 32 + np.bincount(rec_frag, weights=row_bytes, minlength=nf)[frags]
+    frags = frags[:int(np.searchsorted(np.cumsum(frag_bytes), DUMP_BYTES - 5 * 128, side="right"))]
+    sel = np.flatnonzero(np.isin(rec_frag, frags))
+    r = recs[sel]
+    cols = [rec_read[sel]] + [r[n] for n in REG_INT] + [(r["bits"] >> s) & ((1 << w) - 1) for _, s, w in REG_BITS] + [r[n] for n in REG_TAIL]
+    cig = [np.frombuffer(C.string_at(int(p), 4 * int(n)), dtype="<u4") for p, n in zip(r["cigar"], r["n_cigar"]) if n]
+    out = {"frags": frags, "rep_len": np.ctypeslib.as_array(rep)[frags], "n_regs": cnt[(2 * frags[:, None] + np.arange(2)).ravel()],
+           "regs": np.stack(cols, axis=1) if len(sel) else np.zeros((0, len(REG_COLUMNS))), "cigar": np.concatenate(cig) if cig else np.zeros(0)}
+    # al_batch_fetch malloc()s every read's record array and every record's CIGAR: the caller frees them
+    libc = C.CDLL(None); libc.free.argtypes = [C.c_void_p]; libc.free.restype = None
+    for p in recs["cigar"][recs["cigar"] != 0]:
+        libc.free(int(p))
+    for i in have:
+        libc.free(int(ptr[i]))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(arr, dtype=np.float64))
+    return {"dir": out_dir, "fragments": int(len(frags)), "of_fragments": nf, "records": int(len(sel)), "seed": DUMP_SEED,
+            "bytes": sum(os.path.getsize(os.path.join(out_dir, n + ".npy")) for n in out), "regs_columns": REG_COLUMNS}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -264,7 +314,10 @@ def main():
     ap.add_argument("--ins-mean", type=int, default=0, help="mean insert size override (short inserts make the mates overlap: equal-key anchors)")
     ap.add_argument("--config", default="c4", help="workload of tools/gen_synth.py: c4 (default: the configuration BASELINE.json's metric is quoted on -- 150 bp PE against a human-sized reference; fits one GPU), c5 (250 bp), c3 (100 Mbp), c2 (yeast-sized), c2r, c4s, c3u, c4u")
     ap.add_argument("--test-one-gpu", action="store_true", help="N > 1 on a one-GPU box (validation of the sharded path only): every rank uses device 0, collectives over gloo")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the last one computed (the records al_batch_fetch returns, a seeded sample of the fragments) as DIR/<name>.npy (rank 0)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.pairs <= 0:
         a.pairs = 500_000 if a.config == "c5" else 1_000_000        # (c5: 250 bp pairs hold 2100 seed hits each -- 1 M pairs fill the HBM to within what the runtime's queues need for scratch)
 
@@ -383,6 +436,7 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = dump_outputs(ctx, a.dump_outputs) if a.dump_outputs and rank == 0 else None     # before the leg below runs the batch again
     # PCIe-inclusive rate of the same batch (never `value`): pack + H2D upload, run, D2H of the flat result block
     L.al_batch_fetch_flat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.al_batch_fetch_flat.restype = C.c_int
     t0 = time.perf_counter(); n_io = 2
@@ -498,6 +552,7 @@ def main():
             "roofline": roof,
             "stages_ms": per,
             "merged_output": merged,
+            "dumped_outputs": dumped,
             "counters": {"minimizers_per_read": st.n_mini / (2.0 * a.pairs), "anchors_per_pair": st.n_anchor / float(a.pairs), "chains_per_pair": st.n_chain / float(a.pairs),
                          "regions_aligned_per_read": st.n_regs_aln / (2.0 * a.pairs), "ref_bases_per_region": st.n_refbases / max(1.0, float(st.n_regs_aln)),
                          "rechain": int(st.n_rechain), "heap_fallback": int(st.n_heap_fallback), "chain_fallback": int(st.n_chain_fallback), "side_stream_ms": float(st.ms_side_stream), "sort_tie_flags": int(st.n_sort_tie_flag), **(dist_info or {})},

@@ -1,5 +1,5 @@
 /* The reference's own radix sort, compiled from its header where it lies (REF_KSORT_H is passed by the test; nothing of
- * the reference is copied into this repository).  Only built when /root/reference is present. */
+ * the reference is copied into this repository).  Built by tests/golden/make_ksort_digests.py only. */
 #include <stdint.h>
 #include <stdlib.h>
 #include <string.h>

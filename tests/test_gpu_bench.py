@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -30,6 +31,29 @@ def test_bench_single_gpu_line():
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["kind"] in ("reference", "port") and cb["cores"] >= 1
     assert d["parity_sample"]["identical"] is True
+
+
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """--dump-outputs: the last timed step's records for a seeded sample, float64 .npy; the same arguments give the same inputs, so two
+    runs (different step counts) dump the same arrays; --steps is the number of timed steps ms_per_step is taken over."""
+    dumps = []
+    for steps in (1, 3):
+        out = tmp_path / ("s%d" % steps)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--pairs", "100000", "--steps", str(steps), "--warmup", "1",
+                            "--no-cpu-baseline", "--f2f-pairs", "0", "--dump-outputs", str(out)], capture_output=True, cwd=ROOT)
+        assert r.returncode == 0, r.stderr.decode()[-3000:]
+        d = _line(r.stdout)
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and abs(d["value"] - 2 * 100000 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        files = sorted(os.listdir(out))
+        assert files == ["cigar.npy", "frags.npy", "n_regs.npy", "regs.npy", "rep_len.npy"]
+        assert sum(os.path.getsize(out / f) for f in files) <= 64_000_000
+        a = {f[:-len(".npy")]: np.load(out / f) for f in files}
+        assert all(v.dtype == np.float64 for v in a.values())
+        assert len(a["frags"]) == d["dumped_outputs"]["fragments"] == 65536 and a["regs"].shape == (a["n_regs"].sum(), len(d["dumped_outputs"]["regs_columns"]))
+        assert a["regs"].shape[0] > len(a["frags"]) and a["cigar"].size == a["regs"][:, -1].sum()
+        dumps.append(a)
+    for f in dumps[0]:
+        assert np.array_equal(dumps[0][f], dumps[1][f]), f
 
 
 def test_bench_two_ranks_shard_one_input():

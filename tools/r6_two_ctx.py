@@ -4,7 +4,6 @@ usage: r6_two_ctx.py [pairs] [steps]"""
 import ctypes as C, os, sys, tempfile, threading, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import numpy as np
 import bench as B
 import gen_synth as g
