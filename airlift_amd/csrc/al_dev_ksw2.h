@@ -37,6 +37,7 @@ __device__ __forceinline__ uint32_t pk_mask_in(uint32_t t, uint32_t lo, uint32_t
 __device__ __forceinline__ uint32_t d_bfi(uint32_t mask, uint32_t if_set, uint32_t if_clear) { return (if_set & mask) | (if_clear & ~mask); }   // v_bfi_b32
 __device__ __forceinline__ uint32_t pk_splat(int v) { return (uint32_t)(v & 0xffff) * 0x00010001u; }
 __device__ __forceinline__ uint32_t pk_splat8(int v) { return (uint32_t)((v & 0xff) << 8) * 0x00010001u; }   // int8 value in the high byte of both halves
+__device__ __forceinline__ unsigned long long d_grp_any(unsigned long long b) { b |= b >> 8; b |= b >> 4; b |= b >> 2; b |= b >> 1; return b & 0x0001000100010001ull; }   // bit 16 g: any bit of 16-lane group g
 
 // NP superblocks of 32 cells; LT as for d_ksw_reg; selE / selO: the reversed query as selector bytes of the score permute for a cell in the low
 // half (E(base) = base) and in the high half (O(base) = 4 + base), E(N) = O(N) = 0x0d (the permute's constant 0xff = sc_N); 32 * NP bytes of front
@@ -231,29 +232,6 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 				bkey = nk;
 			}
 		}
-		// ---- this lane's best as (H << 16 | 0xffff - ord), ord = rank in the reference's evaluation order; then the group's
-		const int en1 = st0 + (en0 - st0) / 4 * 4;
-		int key32 = (int)0x80000000;
-#pragma unroll
-		for (int hh = 0; hh < 2; ++hh) {
-			const int k16 = (int)(int16_t)(hh ? bkey >> 16 : bkey & 0xffffu), cc = (int)(hh ? bcc >> 16 : bcc & 0xffffu);
-			const int tt = 32 * cc + 2 * gl + hh, dt = tt - st0;
-			const int ord_a = 1 + (dt & 3) * 4096 + (dt >> 2), ord_b = 1 + 4 * 4096 + (tt - en1);
-			int ord = tt < en1 ? ord_a : ord_b;
-			ord = (k16 & 1) ? 0 : ord;
-			const int k = k16 == -32768 ? (int)0x80000000 : (k16 >> 1) * 65536 + (0xffff - ord);
-			key32 = k > key32 ? k : key32;
-		}
-		int max_H, max_t;
-		{
-			int ord, k = key32;
-			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR1, 0xf, 0xf, false); k = o > k ? o : k; }
-			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR2, 0xf, 0xf, false); k = o > k ? o : k; }
-			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_HALF_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
-			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_ROW_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
-			max_H = k >> 16; ord = 0xffff - (k & 0xffff);
-			max_t = r == 0 ? 0 : ord == 0 ? en0 : ord < 1 + 4 * 4096 ? st0 + ((ord - 1) & 4095) * 4 + ((ord - 1) >> 12) : en1 + (ord - 1 - 4 * 4096);
-		}
 		auto h_of = [&](int t) -> int {                                          // H of cell t (group-uniform t)
 			uint32_t hs = 0;
 #pragma unroll
@@ -262,13 +240,45 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 			return (int)(int16_t)((t & 1) ? v >> 16 : v & 0xffffu);
 		};
 		if (r - st0 == qlen - 1) { const int hs = h_of(st0); if (hs > ez.mqe) { ez.mqe = hs; ez.mqe_t = st0; } }   // :353-354
-		bool brk = false;                                                    // ksw_apply_zdrop, ksw2.h:160-176
-		if (max_H > ez.max) { ez.max = max_H; ez.max_t = max_t; ez.max_q = r - max_t; }
-		else if (max_t >= ez.max_t && r - max_t >= ez.max_q) {
-			const int tl = max_t - ez.max_t, ql = (r - max_t) - ez.max_q, l = tl > ql ? tl - ql : ql - tl;
-			if (zdrop >= 0 && ez.max - max_H > zdrop + l * e2) { ez.zdropped = 1; brk = true; }
+		// ---- does the row's maximum change anything?  ez.max / max_t / max_q move only where some cell's H exceeds ez.max, and z-drop fires only
+		// where the row's best H is below ez.max - zdrop (ez.max - max_H > zdrop + l e2 with l e2 >= 0).  In every other row -- the band beyond the
+		// alignment's end, every other anti-diagonal of a gap-free stretch -- nothing below can have an effect: the wavefront skips the key of the
+		// row's best cell, its reduction and the decode of max_t unless one of its groups needs them.
+		const int lk = max((int)(int16_t)(bkey & 0xffffu), (int)(int16_t)(bkey >> 16));                           // this lane's best 2 H + endbit (-32768: none)
+		const unsigned long long w_on = __ballot(1), w_gt = __ballot(lk > 2 * ez.max + 1),
+		                         w_ge = __ballot(zdrop < 0 || (e2 >= 0 && lk != -32768 && lk >= 2 * (ez.max - zdrop)));
+		if (w_gt != 0 || (d_grp_any(w_on) & ~d_grp_any(w_ge)) != 0) {
+			// ---- this lane's best as (H << 16 | 0xffff - ord), ord = rank in the reference's evaluation order; then the group's
+			const int en1 = st0 + (en0 - st0) / 4 * 4;
+			int key32 = (int)0x80000000;
+#pragma unroll
+			for (int hh = 0; hh < 2; ++hh) {
+				const int k16 = (int)(int16_t)(hh ? bkey >> 16 : bkey & 0xffffu), cc = (int)(hh ? bcc >> 16 : bcc & 0xffffu);
+				const int tt = 32 * cc + 2 * gl + hh, dt = tt - st0;
+				const int ord_a = 1 + (dt & 3) * 4096 + (dt >> 2), ord_b = 1 + 4 * 4096 + (tt - en1);
+				int ord = tt < en1 ? ord_a : ord_b;
+				ord = (k16 & 1) ? 0 : ord;
+				const int k = k16 == -32768 ? (int)0x80000000 : (k16 >> 1) * 65536 + (0xffff - ord);
+				key32 = k > key32 ? k : key32;
+			}
+			int max_H, max_t;
+			{
+				int ord, k = key32;
+				{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR1, 0xf, 0xf, false); k = o > k ? o : k; }
+				{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR2, 0xf, 0xf, false); k = o > k ? o : k; }
+				{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_HALF_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
+				{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_ROW_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
+				max_H = k >> 16; ord = 0xffff - (k & 0xffff);
+				max_t = r == 0 ? 0 : ord == 0 ? en0 : ord < 1 + 4 * 4096 ? st0 + ((ord - 1) & 4095) * 4 + ((ord - 1) >> 12) : en1 + (ord - 1 - 4 * 4096);
+			}
+			bool brk = false;                                                    // ksw_apply_zdrop, ksw2.h:160-176
+			if (max_H > ez.max) { ez.max = max_H; ez.max_t = max_t; ez.max_q = r - max_t; }
+			else if (max_t >= ez.max_t && r - max_t >= ez.max_q) {
+				const int tl = max_t - ez.max_t, ql = (r - max_t) - ez.max_q, l = tl > ql ? tl - ql : ql - tl;
+				if (zdrop >= 0 && ez.max - max_H > zdrop + l * e2) { ez.zdropped = 1; brk = true; }
+			}
+			if (brk) break;
 		}
-		if (brk) break;
 		if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = h_of(tlen - 1);
 		last_st = st; last_en = en;
 	}
