@@ -15,6 +15,21 @@ class AirliftError(RuntimeError):
     pass
 
 
+# mapping option flags (include/airlift.h; the values of the fork's MM_F_*)
+AL_F_CIGAR = 0x004
+AL_F_OUT_SAM = 0x008
+AL_F_OUT_CS = 0x40
+AL_F_OUT_CS_LONG = 0x800
+AL_F_SR = 0x1000
+AL_F_FRAG_MODE = 0x2000
+AL_F_NO_PRINT_2ND = 0x4000
+AL_F_SOFTCLIP = 0x80000
+AL_F_HEAP_SORT = 0x400000
+AL_F_OUT_MD = 0x1000000
+AL_F_EQX = 0x4000000
+AL_F_SAM_HIT_ONLY = 0x40000000
+
+
 def lib_path():
     # AIRLIFT_LIB: another build of the same library (A/B timing of kernel variants on one GPU box)
     return os.environ.get("AIRLIFT_LIB") or os.path.join(HERE, "lib", "libairlift.so")
@@ -113,8 +128,28 @@ def load():
     L.al_write_sam.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, cs, cs, ci, ci, ci, C.POINTER(ci), C.POINTER(C.POINTER(Reg)), cs, ci]; L.al_write_sam.restype = ci
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     L.al_version.restype = cs
+    L.al_gen_cs.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs, ci]; L.al_gen_cs.restype = ci
+    L.al_gen_MD.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs]; L.al_gen_MD.restype = ci
     _lib = L
     return L
+
+
+def gen_tag(idx, reg, seq, kind="MD", no_iden=True):
+    """al_gen_MD / al_gen_cs (mm_gen_MD / mm_gen_cs): the MD:Z or cs:Z value of one record `reg` (a Reg) of the read `seq` (bytes,
+    sequencing orientation) against index handle `idx`.  The slow per-record path for API callers."""
+    L = load()
+    buf = C.c_char_p(None); ml = C.c_int(0)
+    libc = C.CDLL(None); libc.free.argtypes = [C.c_void_p]
+    if kind == "MD":
+        n = L.al_gen_MD(None, C.byref(buf), C.byref(ml), idx, C.byref(reg), seq)
+    else:
+        n = L.al_gen_cs(None, C.byref(buf), C.byref(ml), idx, C.byref(reg), seq, 1 if no_iden else 0)
+    out = C.string_at(buf, n) if n >= 0 else None
+    if buf:
+        libc.free(C.cast(buf, C.c_void_p))
+    if n < 0:
+        raise AirliftError("al_gen_%s failed" % kind)
+    return out
 
 
 def read_fastx(path):

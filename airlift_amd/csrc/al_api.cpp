@@ -115,9 +115,13 @@ static void put_sq(Out &o, const char *seq, int l, int rev, int comp)
 	else o.mem(seq, l);
 }
 
-extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
-                            int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len)
+// al_write_sam with the output options of the file drivers: flag's AL_F_SOFTCLIP (-Y) and, for a record with a CIGAR, the tag value
+// `tag` (tag_len bytes, computed on the device) printed as MD:Z or cs:Z after SA:Z (format.c:533-534)
+int al_write_sam_ex(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
+                    int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len,
+                    int64_t opt_flag, const char *tag, int tag_len)
 {
+	const bool softclip = (opt_flag & AL_F_SOFTCLIP) != 0; const int tag_kind = al_tag_kind(opt_flag);
 	Out o{buf, buf + cap - 1, false};
 	const int n_regs = n_regss[seg_idx];
 	const al_reg1_t *regs = regss[seg_idx], *r_prev = nullptr, *r_next = nullptr;
@@ -142,7 +146,7 @@ extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const cha
 		o.ch('\t'); o.str(mi->seq[r->rid].name.c_str()); o.ch('\t'); o.num(r->rs + 1); o.ch('\t'); o.num(r->mapq); o.ch('\t');
 		if (r->n_cigar == 0) o.ch('*');
 		else {
-			const char clip_char = (flag & 0x800) ? 'H' : 'S';
+			const char clip_char = (flag & 0x800) && !softclip ? 'H' : 'S';
 			const int c0 = r->rev ? l_seq - r->qe : r->qs, c1 = r->rev ? r->qs : l_seq - r->qe;
 			if (c0) { o.num(c0); o.ch(clip_char); }
 			for (uint32_t k = 0; k < r->n_cigar; ++k) { o.num(r->cigar[k] >> 4); o.ch("MIDNSHP=XB"[r->cigar[k] & 0xf]); }
@@ -164,7 +168,7 @@ extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const cha
 		o.num(tlen); o.ch('\t');
 	} else o.str("\t*\t0\t0\t");
 	if (!r) { put_sq(o, seq, l_seq, 0, 0); o.ch('\t'); if (qual) put_sq(o, qual, l_seq, 0, 0); else o.ch('*'); }
-	else if ((flag & 0x900) == 0) { put_sq(o, seq, l_seq, r->rev, r->rev); o.ch('\t'); if (qual) put_sq(o, qual, l_seq, r->rev, 0); else o.ch('*'); }
+	else if ((flag & 0x900) == 0 || softclip) { put_sq(o, seq, l_seq, r->rev, r->rev); o.ch('\t'); if (qual) put_sq(o, qual, l_seq, r->rev, 0); else o.ch('*'); }
 	else if (flag & 0x100) o.str("*\t*");
 	else { put_sq(o, seq + r->qs, r->qe - r->qs, r->rev, r->rev); o.ch('\t'); if (qual) put_sq(o, qual + r->qs, r->qe - r->qs, r->rev, 0); else o.ch('*'); }
 	if (rg_id && rg_id[0]) { o.str("\tRG:Z:"); o.str(rg_id); }
@@ -201,10 +205,93 @@ extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const cha
 				}
 			}
 		}
+		if (tag_kind && r->n_cigar) { o.str(tag_kind == 1 ? "\tMD:Z:" : "\tcs:Z:"); o.mem(tag, tag_len); }
 	}
 	if (rep_len >= 0) { o.str("\trl:i:"); o.num(rep_len); }
 	o.ch('\n'); *o.p = 0;
 	return o.ovf ? -1 : (int)(o.p - buf);
+}
+
+extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
+                            int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len)
+{
+	return al_write_sam_ex(buf, cap, mi, qname, l_seq, seq, qual, seg_idx, reg_idx, n_seg, n_regss, regss, rg_id, rep_len, 0, nullptr, 0);
+}
+
+// mm_gen_cs / mm_gen_MD (format.c:137-234, 546-560) for API callers: one record at a time on the host.  The file drivers compute the
+// same strings for whole batches on the device (al_kernels_tags.hip); this is the path of al_map_frag users.
+static int gen_cs_or_MD(char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq, int no_iden, int is_MD)
+{
+	if (!buf || !max_len || !mi || !r || !seq || r->rid < 0 || (size_t)r->rid >= mi->seq.size() || r->re < r->rs || r->qe < r->qs) return -1;
+	std::string s;
+	if (r->n_cigar && r->cigar) {
+		const unsigned char *nt4 = al_nt4();
+		const int tl = r->re - r->rs, ql = r->qe - r->qs;
+		std::vector<uint8_t> t(tl), q(ql);
+		const uint64_t t0 = mi->seq[r->rid].offset + (uint64_t)r->rs;
+		std::vector<uint32_t> words;                             // the S4 words under [rs, re): the host copy, or the device index's
+		const uint64_t w0 = t0 >> 3, w1 = (t0 + tl + 7) >> 3;
+		if (!mi->S4.empty()) words.assign(mi->S4.begin() + w0, mi->S4.begin() + w1);
+		else {
+			std::lock_guard<std::mutex> lk(mi->dev_mtx);
+			auto it = mi->dev.find(mi->built_on);
+			if (it == mi->dev.end() && !mi->dev.empty()) it = mi->dev.begin();
+			if (it == mi->dev.end() || !it->second.S4) { fprintf(stderr, "[airlift] al_gen_MD / al_gen_cs: the index has no reference bases\n"); return -1; }
+			words.resize(w1 - w0);
+			int dev0 = -1;                                       // the caller's current device is given back afterwards
+			const bool ok = hipGetDevice(&dev0) == hipSuccess && hipSetDevice(it->first) == hipSuccess &&
+			                hipMemcpy(words.data(), it->second.S4 + w0, (w1 - w0) * 4, hipMemcpyDeviceToHost) == hipSuccess;
+			if (dev0 >= 0) (void)hipSetDevice(dev0);
+			if (!ok) { fprintf(stderr, "[airlift] al_gen_MD / al_gen_cs: device copy failed\n"); return -1; }
+		}
+		for (int i = 0; i < tl; ++i) { const uint64_t j = t0 + i - (w0 << 3); t[i] = (uint8_t)((words[j >> 3] >> ((j & 7) << 2)) & 0xf); }
+		for (int i = r->qs; i < r->qe; ++i) {                   // format.c:226-234: the query in the record's strand
+			const uint8_t c = nt4[(uint8_t)seq[i]];
+			if (!r->rev) q[i - r->qs] = c; else q[r->qe - i - 1] = c >= 4 ? 4 : 3 - c;
+		}
+		int q_off = 0, t_off = 0, l_MD = 0;
+		char nb[16];
+		for (uint32_t k = 0; k < r->n_cigar; ++k) {
+			const int op = r->cigar[k] & 0xf, len = (int)(r->cigar[k] >> 4);
+			if (q_off + (op == 0 || op == 1 || op == 7 || op == 8 ? len : 0) > ql || t_off + (op == 0 || op == 2 || op == 3 || op == 7 || op == 8 ? len : 0) > tl) return -1;
+			if (op == 0 || op == 7 || op == 8) {
+				int l_tmp = 0;
+				for (int j = 0; j < len; ++j) {
+					const uint8_t qc = q[q_off + j], tc = t[t_off + j];
+					if (is_MD) { if (qc != tc) { snprintf(nb, sizeof(nb), "%d", l_MD); s += nb; s += "ACGTN"[tc]; l_MD = 0; } else ++l_MD; continue; }
+					if (qc != tc) {
+						if (l_tmp > 0) { if (no_iden) { snprintf(nb, sizeof(nb), ":%d", l_tmp); s += nb; } l_tmp = 0; }
+						s += '*'; s += "acgtn"[tc]; s += "acgtn"[qc];
+					} else { if (!no_iden) { if (l_tmp == 0) s += '='; s += "ACGTN"[qc]; } ++l_tmp; }
+				}
+				if (!is_MD && l_tmp > 0 && no_iden) { snprintf(nb, sizeof(nb), ":%d", l_tmp); s += nb; }
+				q_off += len, t_off += len;
+			} else if (op == 1) {
+				if (!is_MD) { s += '+'; for (int j = 0; j < len; ++j) s += "acgtn"[q[q_off + j]]; }
+				q_off += len;
+			} else if (op == 2) {
+				if (is_MD) { snprintf(nb, sizeof(nb), "%d^", l_MD); s += nb; for (int j = 0; j < len; ++j) s += "ACGTN"[t[t_off + j]]; l_MD = 0; }
+				else { s += '-'; for (int j = 0; j < len; ++j) s += "acgtn"[t[t_off + j]]; }
+				t_off += len;
+			} else if (op == 3) {
+				if (!is_MD && len >= 2) { s += '~'; s += "acgtn"[t[t_off]]; s += "acgtn"[t[t_off + 1]]; s += std::to_string(len); s += "acgtn"[t[t_off + len - 2]]; s += "acgtn"[t[t_off + len - 1]]; }
+				t_off += len;
+			}
+		}
+		if (is_MD && l_MD > 0) s += std::to_string(l_MD);
+	}
+	const int need = (int)s.size() + 1;
+	if (!*buf || *max_len < need) { char *nb2 = (char *)realloc(*buf, (size_t)need); if (!nb2) return -1; *buf = nb2; *max_len = need; }
+	memcpy(*buf, s.data(), s.size()); (*buf)[s.size()] = 0;
+	return (int)s.size();
+}
+extern "C" int al_gen_cs(void *km, char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq, int no_iden)
+{
+	(void)km; return gen_cs_or_MD(buf, max_len, mi, r, seq, no_iden, 0);
+}
+extern "C" int al_gen_MD(void *km, char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq)
+{
+	(void)km; return gen_cs_or_MD(buf, max_len, mi, r, seq, 0, 1);
 }
 
 // The file-level driver (al_map_file_frag) lives in al_pipeline.cpp.
@@ -231,6 +318,8 @@ struct HostSamSink {
 		const unsigned char *ct = al_comp();
 		for (int j = 0; j < len; ++j) { unsigned char c = (unsigned char)text[off + (rev ? len - 1 - j : j)]; if (is_seq && (c == 'u' || c == 'U')) --c; if (comp && c < 128) c = ct[c]; out.push_back((char)c); }
 	}
+	const uint64_t *tag_off = nullptr; const char *tag_txt = nullptr;
+	void tag(uint64_t k) { out.append(tag_txt + tag_off[k], tag_off[k + 1] - tag_off[k]); }
 };
 struct Rng { uint64_t s; uint64_t next() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return s; } uint32_t below(uint32_t n) { return (uint32_t)(next() % n); } };
 }
@@ -239,6 +328,7 @@ extern "C" int al_dbg_sam_selftest(uint64_t seed, int n_frag)
 {
 	int bad = 0;
 	Rng R{seed * 2654435761ULL + 88172645463325252ULL};
+	Rng R2{seed * 40503ULL + 2463534242ULL};                     // output options (-Y, tags): a stream of their own, the records stay those of R
 	// (1) "%.4f": every ratio 1 - m / d the tag can take for short reads, and random doubles
 	for (int d = 1; d <= 700 && bad < 10; ++d) for (int m = 0; m <= d; ++m) {
 		const double v = 1.0 - (double)m / d; char a[64], b[64]; bool neg; uint64_t q;
@@ -296,6 +386,13 @@ extern "C" int al_dbg_sam_selftest(uint64_t seed, int n_frag)
 		// cigar pointers into `arena` were taken before it stopped growing: rebuild the host-side view afterwards (below)
 		al_mapopt_t mo; memset(&mo, 0, sizeof(mo)); if (R.below(2)) mo.flag |= AL_F_NO_PRINT_2ND; if (R.below(3) == 0) mo.flag |= AL_F_SAM_HIT_ONLY;
 		AlSamCfg C; C.names = names.data(); C.name_off = noff.data(); C.rg_id = "grp1"; C.rg_len = with_rg ? 4 : 0; C.no_print_2nd = (mo.flag & AL_F_NO_PRINT_2ND) ? 1 : 0; C.hit_only = (mo.flag & AL_F_SAM_HIT_ONLY) ? 1 : 0; C.pe_ori = 1;
+		if (R2.below(2)) { const uint32_t o = 1 + R2.below(5); if (o & 1) mo.flag |= AL_F_SOFTCLIP; if (o >= 2) mo.flag |= o >= 4 ? AL_F_OUT_MD : AL_F_OUT_CS; }   // half of the fragments keep the plain options
+		C.softclip = (mo.flag & AL_F_SOFTCLIP) ? 1 : 0; C.tag_kind = al_tag_kind(mo.flag);
+		std::string tags[2]; std::vector<uint64_t> tag_off[2];        // tag value of each record: what the device tag stage would have left
+		for (int j = 0; j < n_seg; ++j) {
+			tag_off[j].push_back(0);
+			for (size_t k = 0; k < regs[j].size(); ++k) { const int l = (int)R2.below(40); for (int i = 0; i < l; ++i) tags[j].push_back("0123456789ACGT^*:=+-acgt"[R2.below(24)]); tag_off[j].push_back(tags[j].size()); }
+		}
 		// the host records al_write_sam takes: AlReg -> al_reg1_t with the un-flip of al_reg_from_raw
 		std::vector<al_reg1_t> hr[2]; int n_regss[2] = {0, 0}; const al_reg1_t *regss[2] = {nullptr, nullptr};
 		for (int j = 0; j < n_seg; ++j) {
@@ -314,11 +411,18 @@ extern "C" int al_dbg_sam_selftest(uint64_t seed, int n_frag)
 			std::string exp; std::vector<char> buf(1 << 16);
 			std::string seq(text.data() + rd[j].seq, (size_t)rd[j].qlen); for (char &c : seq) if (c == 'u' || c == 'U') --c;       // what the host parsers hand to al_write_sam (bseq.c:72-74)
 			std::string qual; if (with_qual) qual.assign(text.data() + rd[j].qual, (size_t)rd[j].qlen);
-			auto emit = [&](int k) { const int l = al_write_sam(buf.data(), buf.size(), &mi, nm[j].c_str(), rd[j].qlen, seq.c_str(), with_qual ? qual.c_str() : nullptr, j, k, n_seg, n_regss, regss, with_rg ? "grp1" : "", rep_len); if (l > 0) exp.append(buf.data(), (size_t)l); };
+			auto emit = [&](int k) {
+				const int l = mo.flag & (AL_F_SOFTCLIP | AL_F_OUT_MD | AL_F_OUT_CS)
+				    ? al_write_sam_ex(buf.data(), buf.size(), &mi, nm[j].c_str(), rd[j].qlen, seq.c_str(), with_qual ? qual.c_str() : nullptr, j, k, n_seg, n_regss, regss, with_rg ? "grp1" : "", rep_len,
+				                      mo.flag, k >= 0 ? tags[j].data() + tag_off[j][k] : nullptr, k >= 0 ? (int)(tag_off[j][k + 1] - tag_off[j][k]) : 0)
+				    : al_write_sam(buf.data(), buf.size(), &mi, nm[j].c_str(), rd[j].qlen, seq.c_str(), with_qual ? qual.c_str() : nullptr, j, k, n_seg, n_regss, regss, with_rg ? "grp1" : "", rep_len);
+				if (l > 0) exp.append(buf.data(), (size_t)l);
+			};
 			if (n_regss[j] > 0) { for (int k = 0; k < n_regss[j]; ++k) { if ((mo.flag & AL_F_NO_PRINT_2ND) && hr[j][k].id != hr[j][k].parent) continue; emit(k); } }
 			else if (!(mo.flag & AL_F_SAM_HIT_ONLY)) emit(-1);
-			HostSamSink o; o.C = &C; o.text = text.data();
-			AlSamCountSink cnt; cnt.C = &C; cnt.text = text.data();
+			C.tag_reg0 = rd[j].regs;
+			HostSamSink o; o.C = &C; o.text = text.data(); o.tag_off = tag_off[j].data(); o.tag_txt = tags[j].data();
+			AlSamCountSink cnt; cnt.C = &C; cnt.text = text.data(); cnt.tag_off = tag_off[j].data();
 			al_sam_read_records(o, C, rd[j], n_seg == 2 ? &rd[1 - j] : nullptr, j, n_seg, rep_len);
 			al_sam_read_records(cnt, C, rd[j], n_seg == 2 ? &rd[1 - j] : nullptr, j, n_seg, rep_len);
 			if (o.out != exp || cnt.n != exp.size()) {

@@ -62,8 +62,9 @@ const unsigned char *seq16()
 // clipping, SEQ/QUAL orientation and tags.  *key gets (refID << 32 | pos) for the coordinate sort, *unmapped the 0x4 bit.
 int al_write_bam_rec(std::vector<char> &out, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
                      int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len,
-                     uint64_t *key, int *unmapped)
+                     uint64_t *key, int *unmapped, int64_t opt_flag, const char *tag, int tag_len)
 {
+	const bool softclip = (opt_flag & AL_F_SOFTCLIP) != 0; const int tag_kind = al_tag_kind(opt_flag);
 	const int n_regs = n_regss[seg_idx];
 	const al_reg1_t *regs = regss[seg_idx], *r_prev = nullptr, *r_next = nullptr;
 	const al_reg1_t *r = n_regs > 0 && reg_idx < n_regs && reg_idx >= 0 ? &regs[reg_idx] : nullptr;
@@ -83,7 +84,7 @@ int al_write_bam_rec(std::vector<char> &out, const al_idx_t *mi, const char *qna
 	else {
 		this_rid = r->rid; this_pos = r->rs; mapq = r->mapq;
 		if (r->n_cigar) {
-			const uint32_t clip_op = (flag & 0x800) ? 5 : 4;
+			const uint32_t clip_op = (flag & 0x800) && !softclip ? 5 : 4;
 			const int c0 = r->rev ? l_seq - r->qe : r->qs, c1 = r->rev ? r->qs : l_seq - r->qe;
 			if (c0) cig.push_back((uint32_t)c0 << 4 | clip_op);
 			for (uint32_t k = 0; k < r->n_cigar; ++k) cig.push_back(r->cigar[k]);
@@ -102,7 +103,7 @@ int al_write_bam_rec(std::vector<char> &out, const al_idx_t *mi, const char *qna
 	// SEQ / QUAL as printed (format.c:480-503)
 	const char *sq = seq, *ql = qual; int sl = l_seq; bool rev = false, none = false;
 	if (r) {
-		if ((flag & 0x900) == 0) rev = r->rev;
+		if ((flag & 0x900) == 0 || softclip) rev = r->rev;
 		else if (flag & 0x100) none = true;
 		else { sq = seq + r->qs; ql = qual ? qual + r->qs : nullptr; sl = r->qe - r->qs; rev = r->rev; }
 	}
@@ -167,6 +168,7 @@ int al_write_bam_rec(std::vector<char> &out, const al_idx_t *mi, const char *qna
 				w.tag_Z("SA", sa.c_str());
 			}
 		}
+		if (tag_kind && r->n_cigar) { w.mem(tag_kind == 1 ? "MDZ" : "csZ", 3); w.mem(tag, (size_t)tag_len); w.u8(0); }
 	}
 	if (rep_len >= 0) w.tag_i("rl", rep_len);
 	const uint32_t bs = (uint32_t)(out.size() - start - 4);

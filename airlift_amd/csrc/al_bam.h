@@ -24,6 +24,6 @@ extern const unsigned char AL_BGZF_EOF[28];
 int al_bam_header(AlBgzf &z, const al_idx_t *mi, const char *rg, char *rg_id, bool sorted);
 int al_write_bam_rec(std::vector<char> &out, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
                      int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len,
-                     uint64_t *key, int *unmapped);
+                     uint64_t *key, int *unmapped, int64_t opt_flag = 0, const char *tag = nullptr, int tag_len = 0);   // opt_flag, tag: as al_write_sam_ex
 // stable sort permutation of n 64-bit keys, radix-sorted on the context's GPU (al_runtime.hip)
 int al_sort_keys(al_ctx_t *c, const uint64_t *keys, uint32_t *perm, size_t n);

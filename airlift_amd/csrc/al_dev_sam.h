@@ -50,6 +50,9 @@ struct AlSamCfg {                     // what the formatter needs besides the re
 	const char *rg_id; int rg_len;    // RG:Z: value ("" = none)
 	int no_print_2nd, hit_only;       // AL_F_NO_PRINT_2ND, AL_F_SAM_HIT_ONLY
 	int pe_ori;
+	int softclip = 0;                 // AL_F_SOFTCLIP (-Y): S clips and full SEQ / QUAL on supplementary and secondary records
+	int tag_kind = 0;                 // al_tag_kind(): 0 none, 1 MD:Z, 2 cs:Z -- the value of output record k is the sink's tag(k) ...
+	const AlReg *tag_reg0 = nullptr;  // ... k counted from this record (the batch's first)
 };
 
 struct AlSamRead {                    // one read as the formatter sees it
@@ -109,7 +112,7 @@ AL_SD void al_sam_record(S &o, const AlSamCfg &C, const AlSamRead &me, const AlS
 		o.ch('\t'); o.cname(r->rid); o.ch('\t'); o.num(r->rs + 1); o.ch('\t'); o.num((int)(r->mapq & 0xff)); o.ch('\t');
 		if (n_cig == 0) o.ch('*');
 		else {
-			const char clip_char = (flag & 0x800) ? 'H' : 'S';
+			const char clip_char = (flag & 0x800) && !C.softclip ? 'H' : 'S';
 			const int c0 = v.rev ? l_seq - v.qe : v.qs, c1 = v.rev ? v.qs : l_seq - v.qe;
 			if (c0) { o.num(c0); o.ch(clip_char); }
 			for (uint32_t k = 0; k < n_cig; ++k) { o.num((int)(cig[k] >> 4)); o.ch("MIDNSHP=XB"[cig[k] & 0xf]); }
@@ -132,7 +135,7 @@ AL_SD void al_sam_record(S &o, const AlSamCfg &C, const AlSamRead &me, const AlS
 	} else o.lit("\t*\t0\t0\t");
 	const bool hq = me.qual != ~0u;
 	if (!r) { o.seqfld(me.seq, l_seq, 0, 0, 1); o.ch('\t'); if (hq) o.seqfld(me.qual, l_seq, 0, 0, 0); else o.ch('*'); }
-	else if ((flag & 0x900) == 0) { o.seqfld(me.seq, l_seq, v.rev, v.rev, 1); o.ch('\t'); if (hq) o.seqfld(me.qual, l_seq, v.rev, 0, 0); else o.ch('*'); }
+	else if ((flag & 0x900) == 0 || C.softclip) { o.seqfld(me.seq, l_seq, v.rev, v.rev, 1); o.ch('\t'); if (hq) o.seqfld(me.qual, l_seq, v.rev, 0, 0); else o.ch('*'); }
 	else if (flag & 0x100) o.lit("*\t*");
 	else { o.seqfld(me.seq + v.qs, v.qe - v.qs, v.rev, v.rev, 1); o.ch('\t'); if (hq) o.seqfld(me.qual + v.qs, v.qe - v.qs, v.rev, 0, 0); else o.ch('*'); }
 	if (C.rg_len > 0) { o.lit("\tRG:Z:"); o.mem(C.rg_id, C.rg_len); }
@@ -176,6 +179,7 @@ AL_SD void al_sam_record(S &o, const AlSamCfg &C, const AlSamRead &me, const AlS
 				}
 			}
 		}
+		if (C.tag_kind && n_cig) { o.lit(C.tag_kind == 1 ? "\tMD:Z:" : "\tcs:Z:"); o.tag((uint64_t)(r - C.tag_reg0)); }   // format.c:533-534
 	}
 	if (rep_len >= 0) { o.lit("\trl:i:"); o.num(rep_len); }
 	o.ch('\n');
@@ -216,4 +220,6 @@ struct AlSamCountSink {               // pass 1: bytes only
 	AL_SM void mem(const char *, int len) { n += (uint64_t)len; }
 	AL_SM void cname(int rid) { n += C->name_off[rid + 1] - C->name_off[rid]; }
 	AL_SM void seqfld(uint32_t, int len, int, int, int) { if (len > 0) n += (uint64_t)len; }
+	const uint64_t *tag_off = nullptr;
+	AL_SM void tag(uint64_t k) { n += tag_off[k + 1] - tag_off[k]; }
 };

@@ -2752,6 +2752,8 @@ struct AlignState {            // lives in al_ctx_s::align_state (opaque there)
 	DevBuf<uint32_t> ford_key, ford_idx, ford;   // fragments ordered by their number of hits (k_ext_prep / k_ext_finish)
 	int logtab_a = -1, logtab_n = 0;
 	uint64_t out_total = 0;
+	AlTagBufs tags, eqx;                         // --MD / --cs tags, --eqx CIGARs (al_kernels_tags.hip); untouched without them
+	bool eqx_on = false;                         // the last run's records point into eqx.arena instead of arena
 };
 static std::map<al_ctx_t *, AlignState *> g_states;
 static std::mutex g_states_mtx;
@@ -2771,6 +2773,7 @@ void al_align_state_free(al_ctx_t *c)
 	s->regs0.release(); s->mregs.release(); s->rtmp.release(); s->out.release(); s->aux128.release(); s->seg_a.release(); s->aux64.release(); s->seg_u.release();
 	s->nu_off.release(); s->out_off.release(); s->auxi.release(); s->reg_cnt.release(); s->seg_na.release(); s->arena.release(); s->gws.release(); s->long_state.release(); s->logtab.release(); s->dbgbuf.release(); s->hist.release(); s->jobs.release(); s->outs.release(); s->rext.release(); s->seg_fast.release(); s->regs_n0.release(); s->cap2.release(); s->b2_off.release();
 	s->job_off.release(); s->sc_off.release(); s->sc_ws.release(); s->n_jobs.release(); s->n_sc.release(); s->job_key.release(); s->job_key2.release(); s->job_idx.release(); s->job_idx2.release(); s->frag_slow.release(); s->slow_list.release(); s->early_list.release(); s->gws2.release(); s->sort_tmp.release(); s->ford_key.release(); s->ford_idx.release(); s->ford.release(); s->heavy_list.release();
+	s->tags.len.release(); s->tags.off.release(); s->tags.arena.release(); s->eqx.len.release(); s->eqx.off.release(); s->eqx.arena.release();
 	delete s; g_states.erase(it);
 }
 
@@ -2779,6 +2782,7 @@ int al_run_align_stage(al_ctx_t *c)
 	hipStream_t s = c->stream;
 	AlignState *A = get_state(c);
 	const int nf = c->n_frag, nr = c->n_reads;
+	A->eqx_on = false;
 	if (nf == 0) { for (int i = ST_REGS; i < ST_COMPACT; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); return 0; }
 	// logf table from the HOST libm (the reference's logf is glibc's): logf((float)k / a) and logf((float)k)
 	const int Lmax0 = c->max_rd_len;
@@ -3210,6 +3214,20 @@ int al_run_align_stage(al_ctx_t *c)
 	return 0;
 }
 
+// --MD / --cs: the tag stage on the final records (after the arena-overflow re-runs, so it sees the CIGARs that stay)
+int al_run_tags(al_ctx_t *c)
+{
+	AlignState *A = get_state(c);
+	A->tags.bytes = 0; A->eqx_on = false;
+	if (c->n_frag == 0) return 0;
+	if (c->opt.flag & AL_F_EQX) {                 // before the tags: they read the CIGARs the records end up with (ops 7 / 8 count as matches)
+		if (al_run_eqx_stage(c, A->out.p, A->out_off.p, A->out_total, A->arena.p, A->eqx)) return -1;
+		A->eqx_on = true;
+	}
+	if (!al_tag_kind(c->opt.flag)) return 0;
+	return al_run_tag_stage(c, A->out.p, A->out_off.p, A->out_total, A->eqx_on ? (const uint32_t *)A->eqx.arena.p : A->arena.p, A->tags);
+}
+
 // the CIGAR arena of the last al_run_align_stage() was too small (counters[9] != 0): twice the size for the re-run
 void al_align_grow_arena(al_ctx_t *c) { get_state(c)->arena_scale *= 2; }
 
@@ -3223,13 +3241,19 @@ int al_fetch_raw(al_ctx_t *c, AlRawResult &R)
 	if (h[7] || h[8] || h[9]) { fprintf(stderr, "[airlift] device pipeline error: limit=0x%llx (byte k = site k: 0 prep qlen, 1 prep window, 2 dp window, 3 qlen, 4 split capacity, 5 pair scores, 6 lane cigar, 7 finish pair scores) logf_miss=%llu cigar_arena_overflow=%llu\n", h[7], h[8], h[9]); return -4; }
 	if (R.off.resize(nr + 1) || R.out.resize(A->out_total) || R.rep.resize(nf)) return -1;
 	R.flip = c->h_flip; R.rd_len.assign(c->h_rd_len.begin(), c->h_rd_len.begin() + nr);
+	R.tag_kind = nf ? al_tag_kind(c->opt.flag) : 0;
 	if (nf == 0) return 0;
 	AL_HIP_CHECK(hipMemcpy(R.off.data(), A->out_off.p, (size_t)(nr + 1) * 8, hipMemcpyDeviceToHost));
 	if (A->out_total) AL_HIP_CHECK(hipMemcpy(R.out.data(), A->out.p, A->out_total * sizeof(AlReg), hipMemcpyDeviceToHost));
 	AL_HIP_CHECK(hipMemcpy(R.rep.data(), c->frag_rep.p, (size_t)nf * 4, hipMemcpyDeviceToHost));
-	const uint64_t n_arena = h[11];
+	const uint64_t n_arena = A->eqx_on ? A->eqx.bytes : h[11];
 	if (R.arena.resize(n_arena)) return -1;
-	if (n_arena) AL_HIP_CHECK(hipMemcpy(R.arena.data(), A->arena.p, n_arena * 4, hipMemcpyDeviceToHost));
+	if (n_arena) AL_HIP_CHECK(hipMemcpy(R.arena.data(), A->eqx_on ? (const uint32_t *)A->eqx.arena.p : A->arena.p, n_arena * 4, hipMemcpyDeviceToHost));
+	if (R.tag_kind) {
+		if (R.tag_off.resize(A->out_total + 1) || R.tag.resize(A->tags.bytes)) return -1;
+		AL_HIP_CHECK(hipMemcpy(R.tag_off.data(), A->tags.off.p, (A->out_total + 1) * 8, hipMemcpyDeviceToHost));
+		if (A->tags.bytes) AL_HIP_CHECK(hipMemcpy(R.tag.data(), A->tags.arena.p, A->tags.bytes, hipMemcpyDeviceToHost));
+	}
 	return 0;
 }
 
@@ -3242,7 +3266,8 @@ int al_align_result(al_ctx_t *c, AlDevResult *r)
 	AL_HIP_CHECK(hipSetDevice(c->device));
 	unsigned long long h[16]; AL_HIP_CHECK(hipMemcpyAsync(h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost, c->stream)); AL_HIP_CHECK(hipStreamSynchronize(c->stream));
 	if (h[7] || h[8] || h[9]) { fprintf(stderr, "[airlift] device pipeline error: limit=0x%llx logf_miss=%llu cigar_arena_overflow=%llu\n", h[7], h[8], h[9]); return -4; }
-	r->out = A->out.p; r->out_off = A->out_off.p; r->arena = A->arena.p; r->out_total = A->out_total;
+	r->out = A->out.p; r->out_off = A->out_off.p; r->arena = A->eqx_on ? (const uint32_t *)A->eqx.arena.p : A->arena.p; r->out_total = A->out_total;
+	r->tag_kind = al_tag_kind(c->opt.flag); r->tag_off = A->tags.off.p; r->tag = A->tags.arena.p;
 	return 0;
 }
 

@@ -33,11 +33,30 @@ static long long parse_num(const char *str, const char *opt)
 	return (long long)(x + .499);
 }
 
+// output options of the fork's command line (main.c:164, 207, 210, 223-233): 1 if `a` was one of them
+static int parse_out_opt(const char *a, al_mapopt_t &mo)
+{
+	if (!strcmp(a, "--MD")) mo.flag |= AL_F_OUT_MD;
+	else if (!strcmp(a, "--eqx")) mo.flag |= AL_F_EQX;
+	else if (!strcmp(a, "-Y")) mo.flag |= AL_F_SOFTCLIP;
+	else if (!strcmp(a, "--cs") || !strncmp(a, "--cs=", 5)) {
+		const char *v = a[4] == '=' ? a + 5 : nullptr;
+		mo.flag |= AL_F_OUT_CS | AL_F_CIGAR;
+		if (!v || !strcmp(v, "short")) mo.flag &= ~(int64_t)AL_F_OUT_CS_LONG;
+		else if (!strcmp(v, "long")) mo.flag |= AL_F_OUT_CS_LONG;
+		else if (!strcmp(v, "none")) mo.flag &= ~(int64_t)AL_F_OUT_CS;
+		else fprintf(stderr, "[WARNING]\033[1;31m --cs only takes 'short' or 'long'. Invalid values are assumed to be 'short'.\033[0m\n");
+	} else return 0;
+	return 1;
+}
+
 static int usage()
 {
 	fprintf(stderr, "Usage: airlift-align mem [-R RG] [-t N] ref.fa reads_1.fq [reads_2.fq]\n"
 	                "       airlift-align aln [-n X] [-t N] ref.fa reads.fa > x.sai ; airlift-align samse ref.fa x.sai reads.fa\n"
-	                "       airlift-align -ax sr [-t N] [-R RG] ref.fa reads_1.fq [reads_2.fq]\n");
+	                "       airlift-align -ax sr [-t N] [-R RG] ref.fa reads_1.fq [reads_2.fq]\n"
+	                "output options (every mode that writes alignments): --MD (MD:Z tag), --cs[=short|long|none] (cs:Z tag; --MD wins),\n"
+	                "       --eqx (=/X CIGAR operations instead of M), -Y (soft clips and full SEQ/QUAL on supplementary records)\n");
 	return 1;
 }
 
@@ -80,6 +99,7 @@ int main(int argc, char **argv)
 			else if (!strcmp(argv[j], "-R") && j + 1 < argc) rg = argv[++j];
 			else if (!strcmp(argv[j], "-o") && j + 1 < argc) out_p = argv[++j];
 			else if (!strcmp(argv[j], "--singletons") && j + 1 < argc) out_s = argv[++j];
+			else if (parse_out_opt(argv[j], mo)) {}
 			else p.push_back(argv[j]);
 		}
 		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
@@ -141,6 +161,7 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--score-N") && i + 1 < argc) mo.sc_ambi = atoi(argv[++i]);
 		else if (!strcmp(a, "--seed") && i + 1 < argc) mo.seed = atoi(argv[++i]);
 		else if (!strcmp(a, "--sam-hit-only")) mo.flag |= AL_F_SAM_HIT_ONLY;
+		else if (parse_out_opt(a, mo)) {}
 		else if (!strcmp(a, "--count-candidates")) count_only = true;
 		else if (!strcmp(a, "--prefilter") && i + 1 < argc) {   // N4: --prefilter ADJ_E[,SNAKE_E[,SNAKE_K[,SNAKE_ITER]]] with --count-candidates
 			prefilter = true; char *e; const char *v = argv[++i];

@@ -138,6 +138,13 @@ struct al_ctx_s {
 int al_upload_index(const al_idx_t *mi, int device, AlDevIndex *out);
 void al_ctx_no_taps(al_ctx_t *c);         // see al_ctx_s::no_taps
 int al_run_align_stage(al_ctx_t *c);      // al_kernels_align.hip: KA (regs) + K5 (extension, MAPQ, pairing)
+// MD:Z / cs:Z tags of a batch's compacted records (--MD / --cs, al_kernels_tags.hip): value bytes of output record k at arena[off[k] .. off[k + 1])
+struct AlTagBufs { DevBuf<uint32_t> len; DevBuf<uint64_t> off; DevBuf<char> arena; uint64_t bytes = 0; };
+int al_run_tag_stage(al_ctx_t *c, const AlReg *out, const uint64_t *out_off, uint64_t n_out, const uint32_t *arena, AlTagBufs &T);
+// --eqx (al_kernels_tags.hip): the records' M operations rewritten as =/X runs into a fresh arena E (E.bytes = its words), records updated in place
+int al_run_eqx_stage(al_ctx_t *c, AlReg *out, const uint64_t *out_off, uint64_t n_out, const uint32_t *arena, AlTagBufs &E);
+int al_run_tags(al_ctx_t *c);             // al_kernels_align.hip: the =/X pass and the tag stage on the last run's records, when the options ask for them
+static inline int al_tag_kind(int64_t flag) { return (flag & AL_F_OUT_MD) ? 1 : (flag & AL_F_OUT_CS) ? 2 : 0; }   // 0 none, 1 MD, 2 cs (MD wins, format.c:533)
 int al_fetch_align(al_ctx_t *c, int *n_regs, al_reg1_t **regs, int *rep_len);
 void al_align_grow_arena(al_ctx_t *c);
 
@@ -172,8 +179,15 @@ struct AlRawResult {         // flat host copy of one batch's results (no per-re
 	PinnedVec<int32_t> rep;               // per fragment repeat length
 	std::vector<uint8_t> flip;            // read was mapped reverse-complemented
 	std::vector<uint32_t> rd_len;
+	int tag_kind = 0;                     // al_tag_kind() of the run's options: tag values of record k at tag[tag_off[k] .. tag_off[k + 1])
+	PinnedVec<uint64_t> tag_off;
+	PinnedVec<char> tag;
 };
 int  al_fetch_raw(al_ctx_t *c, AlRawResult &R);
+// al_write_sam with the file drivers' output options (al_api.cpp): AL_F_SOFTCLIP, and the record's MD:Z / cs:Z value (tag, tag_len) by al_tag_kind(opt_flag)
+int  al_write_sam_ex(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
+                     int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len,
+                     int64_t opt_flag, const char *tag, int tag_len);
 void al_reg_from_raw(const AlRawResult &R, int read, int k, al_reg1_t &q);
 
 // host worker pool helper: fn(lo, hi, thread) over [0, n) split into contiguous ranges

@@ -1384,6 +1384,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 4, 0, 8 * sizeof(unsigned long long), c->stream));     // [4..11]: stage statistics, error words, arena cursor
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 14, 0, sizeof(unsigned long long), c->stream));
 	}
+	if ((al_tag_kind(c->opt.flag) || (c->opt.flag & AL_F_EQX)) && al_run_tags(c)) return failed();
 	for (int i = 0; i < ST_N; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) != hipSuccess) ms = 0; c->ms_stage[i] = ms; }
 	float tot = 0; (void)hipEventElapsedTime(&tot, c->ev[0], c->ev[ST_N]); c->ms_total = tot;
 	{ float a = 0, b = 0; if (hipEventElapsedTime(&a, c->ev_side[0], c->ev_side[1]) != hipSuccess) a = 0; if (c->n_rechain == 0 || hipEventElapsedTime(&b, c->ev_side[2], c->ev_side[3]) != hipSuccess) b = 0; c->ms_side = a + b; (void)hipGetLastError(); }

@@ -18,7 +18,7 @@
 
 struct AlFqRec { uint32_t name, name_len, seq, len, qual; };      // one FASTQ record: offsets into its file's text
 struct AlRdText { uint32_t name, name_len, seq, qual; };          // one read (fragment-major order): offsets into the text of its file
-struct AlBulk { uint64_t dst; uint32_t src; uint32_t len_flags; }; // SEQ / QUAL field of a SAM record: copied by k_sam_bulk (len | file << 27 | u2t << 28 | comp << 29 | rev << 30)
+struct AlBulk { uint64_t dst; uint32_t src; uint32_t len_flags; }; // SEQ / QUAL field of a SAM record: copied by k_sam_bulk (len | file << 27 | u2t << 28 | comp << 29 | rev << 30); bit 31: a tag value, src = offset into the tag arena
 
 // rd_info bits (per read)
 #define AL_RI_FLIP   1u      // mapped reverse-complemented (map.c:468): un-flip at output (map.c:486-497)
@@ -77,5 +77,6 @@ int  al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id);
 int  al_stream_sam_fetch(AlStreamSlot &S, uint64_t off, uint64_t n, char *dst, hipEvent_t done);
 
 // device result arrays of the last al_batch_run (al_kernels_align.hip)
-struct AlDevResult { const AlReg *out; const uint64_t *out_off; const uint32_t *arena; uint64_t out_total; };
+struct AlDevResult { const AlReg *out; const uint64_t *out_off; const uint32_t *arena; uint64_t out_total;
+                     int tag_kind; const uint64_t *tag_off; const char *tag; };   // tags (--MD / --cs): values of record k at tag[tag_off[k] .. tag_off[k + 1])
 int  al_align_result(al_ctx_t *c, AlDevResult *r);

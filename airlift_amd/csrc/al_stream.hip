@@ -218,6 +218,7 @@ struct SamIn {
 	const AlRdText *rtxt; const uint8_t *rd_info; const uint32_t *rd_frag, *rd_len; const int32_t *frag_rep;
 	const char *t0, *t1; int two_files; uint32_t n_reads;
 	AlSamCfg C;
+	const uint64_t *tag_off; const char *tag_txt;   // C.tag_kind != 0: tag values of output record k at tag_txt[tag_off[k] .. tag_off[k + 1])
 };
 __device__ __forceinline__ AlSamRead d_sam_read(const SamIn &I, uint32_t i)
 {
@@ -236,14 +237,14 @@ k_sam_len(SamIn I, uint32_t *__restrict__ sam_len, uint32_t *__restrict__ sam_nr
 	const AlSamRead me = d_sam_read(I, i);
 	AlSamRead mt; const bool paired = (info & AL_RI_PAIRED) != 0;
 	if (paired) mt = d_sam_read(I, (info & AL_RI_SEG1) ? i - 1 : i + 1);
-	AlSamCountSink o; o.C = &I.C; o.text = (I.two_files && (info & AL_RI_SEG1)) ? I.t1 : I.t0;
+	AlSamCountSink o; o.C = &I.C; o.text = (I.two_files && (info & AL_RI_SEG1)) ? I.t1 : I.t0; o.tag_off = I.tag_off;
 	const int n = al_sam_read_records(o, I.C, me, paired ? &mt : nullptr, (info & AL_RI_SEG1) ? 1 : 0, paired ? 2 : 1, I.frag_rep[I.rd_frag[i]]);
 	sam_len[i] = (uint32_t)o.n; sam_nrec[i] = (uint32_t)n;
 }
 struct SamWriteSink {
-	const AlSamCfg *C; const char *text; char *p; char *base; AlBulk *bulk, *next; uint32_t file; int slot;
+	const AlSamCfg *C; const char *text; char *p; char *base; AlBulk *bulk, *next; uint32_t file; int slot, n_slot; const uint64_t *tag_off; const char *tag_txt;
 	__device__ __forceinline__ char peek(uint32_t off) const { return text[off]; }
-	__device__ __forceinline__ void begin_record() { bulk = next; next += 2; slot = 0; }   // two descriptor slots per record
+	__device__ __forceinline__ void begin_record() { bulk = next; next += n_slot; slot = 0; }   // two descriptor slots per record (SEQ, QUAL), three with a tag
 	__device__ __forceinline__ void ch(char c) { *p++ = c; }
 	__device__ __forceinline__ void lit(const char *s) { while (*s) *p++ = *s++; }
 	__device__ __forceinline__ void num(long long v)
@@ -263,6 +264,14 @@ struct SamWriteSink {
 		bulk[slot] = AlBulk{(uint64_t)(p - base), off, (uint32_t)len | file << 27 | (is_seq ? 1u << 28 : 0u) | (comp ? 1u << 29 : 0u) | (rev ? 1u << 30 : 0u)};
 		++slot; p += len;
 	}
+	__device__ __forceinline__ void tag(uint64_t k)
+	{   // the record's MD:Z / cs:Z value: a short one (a typical MD) copied here, a long one (cs, long form) by k_sam_bulk (bit 31)
+		const uint64_t a = tag_off[k], len = tag_off[k + 1] - a;
+		if (len == 0) return;
+		if (len <= 32) { for (uint32_t j = 0; j < (uint32_t)len; ++j) p[j] = tag_txt[a + j]; p += len; return; }
+		bulk[slot] = AlBulk{(uint64_t)(p - base), (uint32_t)a, (uint32_t)len | 1u << 31};
+		++slot; p += len;
+	}
 };
 __global__ void __launch_bounds__(256)
 k_sam_write(SamIn I, const uint64_t *__restrict__ sam_off, const uint64_t *__restrict__ rec_off, char *__restrict__ sam, AlBulk *__restrict__ bulk)
@@ -275,17 +284,19 @@ k_sam_write(SamIn I, const uint64_t *__restrict__ sam_off, const uint64_t *__res
 	if (paired) mt = d_sam_read(I, (info & AL_RI_SEG1) ? i - 1 : i + 1);
 	const uint32_t file = (I.two_files && (info & AL_RI_SEG1)) ? 1u : 0u;
 	SamWriteSink o; o.C = &I.C; o.text = file ? I.t1 : I.t0; o.base = sam; o.p = sam + sam_off[i]; o.file = file;
-	o.next = bulk + 2 * rec_off[i]; o.bulk = o.next; o.slot = 0;
+	o.n_slot = I.C.tag_kind ? 3 : 2; o.tag_off = I.tag_off; o.tag_txt = I.tag_txt;
+	o.next = bulk + (uint64_t)o.n_slot * rec_off[i]; o.bulk = o.next; o.slot = 0;
 	al_sam_read_records(o, I.C, me, paired ? &mt : nullptr, (info & AL_RI_SEG1) ? 1 : 0, paired ? 2 : 1, I.frag_rep[I.rd_frag[i]]);
 }
-// a SEQ / QUAL field: a wavefront per descriptor, one byte per lane and step (the destination is contiguous)
+// a SEQ / QUAL field, or a tag value: a wavefront per descriptor, one byte per lane and step (the destination is contiguous)
 __global__ void __launch_bounds__(256)
-k_sam_bulk(const AlBulk *__restrict__ bulk, uint64_t n_desc, const char *__restrict__ t0, const char *__restrict__ t1, const uint8_t *__restrict__ tabs, char *__restrict__ sam)
+k_sam_bulk(const AlBulk *__restrict__ bulk, uint64_t n_desc, const char *__restrict__ t0, const char *__restrict__ t1, const uint8_t *__restrict__ tabs, char *__restrict__ sam, const char *__restrict__ tag)
 {
 	const uint64_t d = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); const uint32_t l = threadIdx.x & 63;
 	if (d >= n_desc) return;
 	const AlBulk b = bulk[d];
 	const uint32_t len = b.len_flags & 0x7ffffffu; if (len == 0) return;
+	if (b.len_flags >> 31) { const char *s = tag + b.src; char *o = sam + b.dst; for (uint32_t j = l; j < len; j += 64) o[j] = s[j]; return; }
 	const char *s = ((b.len_flags >> 27 & 1u) ? t1 : t0) + b.src;
 	const bool u2t = b.len_flags >> 28 & 1u, comp = b.len_flags >> 29 & 1u, rev = b.len_flags >> 30 & 1u;
 	const uint8_t *ct = tabs + 256;
@@ -498,6 +509,8 @@ int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id)
 	I.t0 = (const char *)S.txt[0].p; I.t1 = (const char *)(S.n_files == 2 ? S.txt[1].p : S.txt[0].p); I.two_files = S.n_files == 2 ? 1 : 0; I.n_reads = nr;
 	I.C.names = S.names.p; I.C.name_off = S.name_off.p; I.C.rg_id = S.rg.p; I.C.rg_len = S.rg_len;
 	I.C.no_print_2nd = (c->opt.flag & AL_F_NO_PRINT_2ND) ? 1 : 0; I.C.hit_only = (c->opt.flag & AL_F_SAM_HIT_ONLY) ? 1 : 0; I.C.pe_ori = c->opt.pe_ori;
+	I.C.softclip = (c->opt.flag & AL_F_SOFTCLIP) ? 1 : 0; I.C.tag_kind = R.tag_kind; I.C.tag_reg0 = R.out; I.tag_off = R.tag_kind ? R.tag_off : nullptr; I.tag_txt = R.tag_kind ? R.tag : nullptr;
+	const uint64_t n_slot = R.tag_kind ? 3 : 2;                      // bulk descriptors per record
 	if (S.sam_len.ensure((size_t)nr + 2) || S.sam_nrec.ensure((size_t)nr + 2) || S.sam_off.ensure((size_t)nr + 2) || S.rec_off.ensure((size_t)nr + 2)) return -1;
 	hipLaunchKernelGGL(k_sam_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
 	if (scan_excl_u64(S, S.sam_len.p, S.sam_off.p, (size_t)nr + 1, s) || scan_excl_u64(S, S.sam_nrec.p, S.rec_off.p, (size_t)nr + 1, s)) return -1;
@@ -505,11 +518,11 @@ int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id)
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[0], S.sam_off.p + nr, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[1], S.rec_off.p + nr, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
-	if (S.sam.ensure(tot[0] + 64) || S.bulk.ensure(2 * tot[1] + 2)) return -1;
+	if (S.sam.ensure(tot[0] + 64) || S.bulk.ensure(n_slot * tot[1] + 2)) return -1;
 	if (tot[1]) {
-		AL_HIP_CHECK(hipMemsetAsync(S.bulk.p, 0, 2 * tot[1] * sizeof(AlBulk), s));
+		AL_HIP_CHECK(hipMemsetAsync(S.bulk.p, 0, n_slot * tot[1] * sizeof(AlBulk), s));
 		hipLaunchKernelGGL(k_sam_write, dim3((nr + 255) / 256), dim3(256), 0, s, I, S.sam_off.p, S.rec_off.p, S.sam.p, S.bulk.p);
-		hipLaunchKernelGGL(k_sam_bulk, dim3((unsigned)((2 * tot[1] + 3) / 4)), dim3(256), 0, s, S.bulk.p, 2 * tot[1], I.t0, I.t1, S.tabs.p, S.sam.p);
+		hipLaunchKernelGGL(k_sam_bulk, dim3((unsigned)((n_slot * tot[1] + 3) / 4)), dim3(256), 0, s, S.bulk.p, n_slot * tot[1], I.t0, I.t1, S.tabs.p, S.sam.p, R.tag_kind ? R.tag : (const char *)nullptr);
 		// the text leaves on the slot's own stream (al_stream_sam_fetch): the context goes on with its next batch
 		AL_HIP_CHECK(hipEventRecord(S.ev, s));
 		AL_HIP_CHECK(hipStreamWaitEvent(S.io, S.ev, 0));

@@ -32,6 +32,12 @@ extern "C" {
 #define AL_F_NO_PRINT_2ND  0x4000
 #define AL_F_HEAP_SORT     0x400000
 #define AL_F_SAM_HIT_ONLY  0x40000000
+/* output options (main.c:164, 207, 210, 223-233): cs:Z / MD:Z tags, soft clips and full SEQ on supplementaries (-Y), =/X CIGARs (--eqx; also what al_map_frag returns) */
+#define AL_F_OUT_CS        0x40
+#define AL_F_OUT_CS_LONG   0x800
+#define AL_F_SOFTCLIP      0x80000
+#define AL_F_OUT_MD        0x1000000
+#define AL_F_EQX           0x4000000
 
 /* replaces mm_idxopt_t (minimap.h:101-105) */
 typedef struct {
@@ -319,6 +325,14 @@ int  al_write_sam_hdr(FILE *out, const al_idx_t *mi, const char *rg, char *rg_id
 int  al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
                   int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss,
                   const char *rg_id, int rep_len);
+
+/* mm_gen_cs / mm_gen_MD (minimap.h:363-364, format.c:137-214): the cs:Z / MD:Z value (no tag prefix) of one record r as al_map_frag
+ * returned it, for the read `seq` in sequencing orientation.  no_iden != 0: short cs (":len"), else long ("=BASES").  *buf is malloc()ed /
+ * realloc()ed to fit (*max_len its size); returns the string length, -1 on error.  km is ignored.  The reference window comes from the
+ * index's host copy when it has one (al_idx_build, al_idx_str, al_idx_load), otherwise [rs, re) is copied from the device index.
+ * This is the slow path for API callers: the file drivers (--MD / --cs) compute the tags on the device for a whole batch. */
+int  al_gen_cs(void *km, char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq, int no_iden);
+int  al_gen_MD(void *km, char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq);
 
 const char *al_version(void);
 
