@@ -45,9 +45,13 @@ __device__ __forceinline__ unsigned long long d_grp_any(unsigned long long b) { 
 // DIR: 0 = left-aligned gaps, 1 = right-aligned (EZ_RIGHT), 2 = by the flag (a wavefront whose groups differ).  The tags of the five-way choice RIDE IN THE STATE: x, y, x2, y2
 // carry theirs in the low byte of either half from the moment they are made (the constant subtracted there is q + e less the tag), u and v have zero low bytes,
 // so the sums a = x + v ... come out tagged and the four ors per cell pair are gone; with DIR known the gap-stays-open test needs no or either.
-template <int NP, class LT, int DIR = 2>
+// EXIT: the group leaves the row loop as soon as no later anti-diagonal can change what an extension job's caller reads (max, max_t, max_q,
+// reach_end, mqe_t when reach_end, the CIGAR from the chosen end cell); only k_ext_dp asks for it, every other caller keeps the full DP and its
+// zdropped / score.  The rule and its proof are in DESIGN.md §4.  xcnt (shadow mode, AL_DBG2 bit 5): the rule is evaluated, the state at the
+// first row where it holds is compared with the full run's, and the counts go to xcnt[0..7].
+template <int NP, class LT, int DIR = 2, bool EXIT = false>
 __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE, const uint8_t *__restrict__ selO, const int gl, GroupWs &ws, int qlen, int tlen, const AlParams &P,
-                                         int w, int zdrop, int end_bonus, int flag, EzD &ez, bool do_bt = true)
+                                         int w, int zdrop, int end_bonus, int flag, EzD &ez, bool do_bt = true, unsigned long long *xcnt = nullptr)
 {
 	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
 	if (q2 + e2 < q + e) { int t = q; q = q2; q2 = t; t = e; e = e2; e2 = t; }
@@ -94,6 +98,17 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 	uint8_t *const ptb = ws.p;
 	int last_st = -1, last_en = -1, r;
 	const int n_rows = qlen + tlen - 1;
+	// ---- early exit (EXIT).  After row r >= qlen, U = max(F(r-1), F(r), B(r)) bounds H in every later row: F(r) is the largest H + a (qlen - 1 - i)
+	// of row r's cells (a = sc_mch; every step of a path gains at most a, and a later cell is reached from a cell of row r - 1 or r or from the
+	// target boundary i = -1, whose H(t, -1) = -gap(t + 1) gives B(r)).  This needs (a) the band's start to be the query end's diagonal from row
+	// r - 1 on (then no stale cell left of the band feeds a cell of the band) and (b) a + |worst score| <= q + e.
+	const bool shadow = EXIT && xcnt != nullptr;
+	const int bmax = P.b > 1 ? P.b : 1;                                       // |worst score| (sc_N = -1)
+	const bool ex_on = EXIT && (P.dp_exit != 0 || shadow) && (flag & EZ_EXTZ_ONLY) && sc_mch + bmax <= qe;
+	const bool no_empty = tlen - 1 <= ((qlen + tlen - 2 + w) >> 1);            // E3(a): no later row has an empty band (st - en grows from row qlen - 1 on)
+	const uint32_t ATT = (uint32_t)(sc_mch * 2 * gl) | (uint32_t)(sc_mch * (2 * gl + 1)) << 16;   // a t of this lane's two cells in superblock 0
+	int f_prev = KSW_NEG_INF;
+	if constexpr (EXIT) if (shadow && gl == 0) L.ezc[5] = 0xffffffffu;          // (shadow mode: the exit row, in LDS -- no register for it in the row loop)
 	for (r = 0; r < n_rows; ++r) {
 		int st, en;
 		d_row_bounds(r, qlen, tlen, w, st, en);
@@ -138,6 +153,8 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 			hprev = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)hs, DPP_ROW_BCAST15, 0xf, 0xf, false);
 		}
 		uint32_t bkey = 0x80008000u, bcc = 0;                                   // per half: best 2 H + (end cell) of this lane's cells, and its superblock
+		uint32_t gacc = 0x80008000u;                                            // (EXIT) per half: largest H + a t of this lane's cells in the row
+		const bool acc_row = EXIT && __ballot(ex_on && r >= qlen - 1) != 0;   // (wavefront-uniform: a scalar branch per superblock)
 		// the cell recurrence (:177-265) on two cells: left neighbours (xt1, vt1, x2t1), the cells' own u, y, y2 and score -> new state and traceback byte
 		auto cell = [&](const uint32_t xt1, const uint32_t vt1, const uint32_t x2t1, const uint32_t uo, const uint32_t yo, const uint32_t y2o, const uint32_t so,
 		                uint32_t &xn, uint32_t &vn, uint32_t &x2n, uint32_t &un, uint32_t &yn, uint32_t &y2n, uint32_t &d) {
@@ -176,6 +193,7 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 				prl[16 * c] = (uint16_t)__builtin_amdgcn_perm(0u, d, 0x0c0c0200u);
 				const uint32_t hn = pk_add(H[c], pk_sar8(vn));
 				H[c] = hn;
+				if (acc_row) gacc = pk_max(gacc, pk_add(pk_add(hn, ATT), pk_splat(32 * sc_mch * c)));
 				const uint32_t nk = pk_max(bkey, pk_add(hn, hn));
 				const uint32_t ch = pk_minu1(nk ^ bkey);
 				bcc = pk_u(pk_s(bcc) + pk_s(ch) * (pk_s(pk_splat(c)) - pk_s(bcc)));
@@ -222,6 +240,7 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 				if (c == 0 && r == 0) { const uint32_t m0 = (gl == 0 && act) ? 0x0000ffffu : 0u; h = d_bfi(m0, pk_sub(pk_sar8(vn), pk_splat(qe)), h); upd |= m0; }   // H[0][0] = v - qe
 				const uint32_t hn = d_bfi(upd, h, hold);
 				H[c] = hn;
+				if (acc_row) gacc = pk_max(gacc, d_bfi(upd, pk_add(pk_add(hn, ATT), pk_splat(32 * sc_mch * c)), 0x80008000u));
 				// candidate key 2 H + (end cell or cell (0, 0)): a strictly greater key takes over -- among equal H the end cell (evaluated first by the
 				// reference) wins, then the earlier superblock (its cell comes earlier in the reference's order, see d_ksw_reg)
 				const uint32_t endbit = (men | (r == 0 ? 0x0000ffffu : 0u)) & 0x00010001u;
@@ -281,6 +300,53 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 		}
 		if (r == qlen + tlen - 2 && en0 == tlen - 1) ez.score = h_of(tlen - 1);
 		last_st = st; last_en = en;
+		if constexpr (EXIT) if (acc_row) {
+			int k = max((int)(int16_t)(gacc & 0xffffu), (int)(int16_t)(gacc >> 16));
+			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR1, 0xf, 0xf, false); k = o > k ? o : k; }
+			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_QUAD_XOR2, 0xf, 0xf, false); k = o > k ? o : k; }
+			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_HALF_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
+			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_ROW_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
+			const int f_row = k == -32768 ? KSW_NEG_INF : k + sc_mch * (qlen - 1 - r);   // F(r)
+			if (ex_on && r >= qlen) {
+				const int t1 = r + 1, gb = min(q + e * t1, q2 + e2 * t1);
+				const int bnd = t1 <= tlen - 1 && t1 <= w ? sc_mch * (1 + min(qlen - 1, tlen - 2 - r)) - gb : KSW_NEG_INF;   // B(r): cells (t, 0), t > r
+				const int U = max(max(f_row, f_prev), bnd);
+				const bool wok = ((r - w) >> 1) <= r - qlen;                      // row r - 1 (and so every later row): st = r - qlen + 1
+				const bool c1 = U <= ez.max;
+				const bool c2 = U <= ez.mqe || (U + end_bonus <= ez.max && ez.mqe + end_bonus <= ez.max);
+				// E3(b): z-drop cannot fire later.  With k = qlen - 1 - max_q, a later row's cell C at the query end, t_C = r' - qlen + 1, is reached
+				// from the max cell by k diagonal steps (>= -|worst score| each) and d = t_C - max_t - k >= 0 deletions, so its row's best B has
+				// max - H_B <= k |worst| + q2 + e2 d, and B (i_B <= qlen - 1, t_B >= t_C) lies l >= d off the max cell's diagonal.
+				const int kq = qlen - 1 - ez.max_q;
+				const bool c3 = ez.mqe + end_bonus <= ez.max || (no_empty && (zdrop < 0 || (ez.max_t >= 0 && kq * bmax + q2 <= zdrop && ez.max_t + kq <= tlen - 1 && r + 2 - qlen - ez.max_t - kq >= 0)));
+				if (wok && c1 && c2 && c3) {                                     // E1, E2, E3
+					if (!shadow) break;
+					if ((int)L.ezc[5] < 0 && gl == 0) { L.ezc[0] = (uint32_t)ez.max; L.ezc[1] = (uint32_t)ez.max_t; L.ezc[2] = (uint32_t)ez.max_q; L.ezc[3] = (uint32_t)ez.mqe; L.ezc[4] = (uint32_t)ez.mqe_t; L.ezc[5] = (uint32_t)r; }   // (L.ezc is free until the backtrack)
+				}
+			}
+			f_prev = f_row;
+		}
+	}
+	GSYNC();
+	if constexpr (EXIT) if (shadow && ex_on) {   // shadow mode: the state at the exit row against the full run's
+		const int exit_row = (int)L.ezc[5];
+		const int rows_run = r < n_rows ? r + 1 : n_rows, need = exit_row >= 0 ? exit_row + 1 : rows_run;
+		bool differs = false;
+		if (exit_row >= 0) {
+			const int smax = (int)L.ezc[0], smax_t = (int)L.ezc[1], smax_q = (int)L.ezc[2], smqe = (int)L.ezc[3], smqe_t = (int)L.ezc[4];
+			const bool reach_f = !ez.zdropped && ez.mqe + end_bonus > ez.max, reach_s = smqe + end_bonus > smax;
+			differs = smax != ez.max || smax_t != ez.max_t || smax_q != ez.max_q || reach_s != reach_f || (reach_f && smqe_t != ez.mqe_t);
+		}
+		int wn = need, wr = rows_run;                                           // per wavefront: the largest over its groups (full wavefronts only)
+		const bool full = __ballot(1) == ~0ull;
+		if (full) { wn = max(wn, __shfl_xor(wn, 16)); wn = max(wn, __shfl_xor(wn, 32)); wr = max(wr, __shfl_xor(wr, 16)); wr = max(wr, __shfl_xor(wr, 32)); }
+		if (gl == 0) {
+			const int sv = (int)((long long)(n_rows - need) * 100 / n_rows);
+			atomicAdd(xcnt + 0, 1ull); if (differs) atomicAdd(xcnt + 1, 1ull);
+			atomicAdd(xcnt + 2, (unsigned long long)n_rows); atomicAdd(xcnt + 3, (unsigned long long)need);
+			atomicAdd(xcnt + (sv < 25 ? 6 : 7), (sv < 10 || (sv >= 25 && sv < 40)) ? 1ull : 1ull << 32);   // saved share of the rows: < 10 % | 10-25 % ; 25-40 % | >= 40 %
+		}
+		if (full && threadIdx.x == 0) { atomicAdd(xcnt + 4, (unsigned long long)wr); atomicAdd(xcnt + 5, (unsigned long long)wn); }
 	}
 	GSYNC();
 	if (do_bt) {

@@ -87,6 +87,8 @@ struct AlParams {             // kernel parameter block (copy of the options the
 	int pe_ori, pe_bonus, mid_occ, max_occ;
 	int dbg;                  // timing experiments only (AL_DBG env): skips phases, results become wrong
 	int dbg2;                 // more of the same (AL_DBG2 env): bit 3 cycle counters of the lane chaining kernels' phases (printed per batch), bit 20 the seed / sort / chain stages only
+	                          // (bit 5, shadow mode of the extension DP's early exit, leaves the results valid: counts printed per batch)
+	int dp_exit;              // the extension DP's early exit (al_dev_ksw2.h): on unless AL_DP_EXIT=0
 };
 
 struct AlMatch {              // one query minimizer that passed the occurrence filter (mm_match_t, map.c:82-88)

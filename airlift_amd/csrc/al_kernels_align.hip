@@ -2249,9 +2249,11 @@ k_ext_dp(const uint32_t *__restrict__ rd_seq, const uint64_t *__restrict__ rd_of
 			GSYNC();
 			// the job list is ordered by direction inside a block count (k_ext_prep's key): nearly every wavefront holds jobs of one direction and takes the form compiled for it
 			const unsigned long long w_act = __ballot(1), w_right = __ballot((flag & EZ_RIGHT) != 0);
-			if (w_right == 0) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 0>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez);
-			else if (w_right == w_act) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 1>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez);
-			else d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 2>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez);
+			unsigned long long *const xcnt = ((P.dbg2 >> 5) & 1) ? G.counters + 24 : nullptr;   // AL_DBG2 bit 5: the early exit in shadow mode
+			// (the early exit from 12 target blocks up: on the 8-block class its bookkeeping cost more than the rows it saved)
+			if (w_right == 0) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 0, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
+			else if (w_right == w_act) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 1, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
+			else d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 2, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
 		} else
 		d_ksw_reg<NB>(L, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez);
 		ExtOut o;

@@ -456,7 +456,8 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 	P.a = opt->a; P.b = opt->b; P.q = opt->q; P.e = opt->e; P.q2 = opt->q2; P.e2 = opt->e2; P.sc_ambi = opt->sc_ambi; P.zdrop = opt->zdrop; P.zdrop_inv = opt->zdrop_inv;
 	P.end_bonus = opt->end_bonus; P.min_dp_max = opt->min_dp_max; P.pe_ori = opt->pe_ori; P.pe_bonus = opt->pe_bonus; P.mid_occ = opt->mid_occ; P.max_occ = opt->max_occ;
 	{ const char *d = getenv("AL_DBG"); P.dbg = d ? atoi(d) : 0; if (P.dbg) fprintf(stderr, "[airlift] AL_DBG=%d: timing experiment, results are NOT valid\n", P.dbg); }
-	{ const char *d = getenv("AL_DBG2"); P.dbg2 = d ? atoi(d) : 0; if (P.dbg2) fprintf(stderr, "[airlift] AL_DBG2=%d: timing experiment, results are NOT valid\n", P.dbg2); }
+	{ const char *d = getenv("AL_DBG2"); P.dbg2 = d ? atoi(d) : 0; if (P.dbg2 & ~32) fprintf(stderr, "[airlift] AL_DBG2=%d: timing experiment, results are NOT valid\n", P.dbg2); }
+	{ const char *d = getenv("AL_DP_EXIT"); P.dp_exit = d ? atoi(d) != 0 : 1; }
 	memset(&c->stat, 0, sizeof(c->stat));
 	return c;
 }
@@ -1398,6 +1399,9 @@ extern "C" int al_batch_run(al_ctx_t *c)
 		fprintf(stderr, "[airlift] lane chaining kernels (cycles per wavefront, all launches of the batch): setup %llu load %llu recurrence %llu ends/backtrack/order %llu copy %llu; wavefronts %llu\n", t[5] ? t[0] / t[5] : 0, t[5] ? t[1] / t[5] : 0, t[5] ? t[2] / t[5] : 0, t[5] ? t[3] / t[5] : 0, t[5] ? t[4] / t[5] : 0, t[5]); }
 	if ((c->P.dbg2 >> 4) & 1) { unsigned long long t[8]; AL_HIP_CHECK(hipMemcpy(t, c->counters.p + 24, sizeof(t), hipMemcpyDeviceToHost));
 		fprintf(stderr, "[airlift] k_regs_heavy (lane 0 = mate 0, cycles summed over fragments): gen_regs %llu set_parent %llu squeeze %llu; hits %llu; whole blocks %llu over %llu fragments\n", t[0], t[1], t[2], t[3], t[4], t[5]); }
+	if ((c->P.dbg2 >> 5) & 1) { unsigned long long t[8]; AL_HIP_CHECK(hipMemcpy(t, c->counters.p + 24, sizeof(t), hipMemcpyDeviceToHost));
+		fprintf(stderr, "[airlift] DP exit shadow (two-cells-per-lane jobs): jobs %llu, differing %llu; rows needed %llu of %llu (%.1f %%); per wavefront %llu of %llu (%.1f %%); jobs saving < 10 %% %llu, 10-25 %% %llu, 25-40 %% %llu, >= 40 %% %llu\n",
+		        t[0], t[1], t[3], t[2], t[2] ? 100.0 * (double)t[3] / (double)t[2] : 0.0, t[5], t[4], t[4] ? 100.0 * (double)t[5] / (double)t[4] : 0.0, t[6] & 0xffffffffull, t[6] >> 32, t[7] & 0xffffffffull, t[7] >> 32); }
 	if (getenv("AL_TRACE")) { fprintf(stderr, "[airlift] trace: counters"); for (int i = 0; i < 16; ++i) fprintf(stderr, " [%d]=%llu", i, h[i]); fprintf(stderr, " rechain=%u\n", c->n_rechain); }
 	al_batch_stat_t &st = c->stat; memset(&st, 0, sizeof(st));
 	st.n_frag = c->n_frag; st.n_reads = c->n_reads; st.n_bases = c->n_bases;
