@@ -9,8 +9,13 @@ mason-like reads; generated here with fixed seeds; it fits one GPU: 23 GB index)
 BASELINE configs.  N>1: one process per GPU, reads sharded by rank (every rank holds the full index; weak scaling), one
 16-byte RCCL all-gather per step for the merged-output offsets.
 
+A plain run does only what `value` needs: set-up, warm-up, the timed steps, --dump-outputs, and the JSON line with the stage
+intervals, roofline and counters those steps yield.  --full adds the legs that run the batch or other programs again: the
+PCIe-inclusive rate and, at N=1, the CPU comparator with its SAM parity sample and the file-to-file leg.
+
     python bench.py --gpus 1 --steps 5 --warmup 2
     python bench.py --gpus 1 --steps 5 --warmup 2 --dump-outputs DIR    (also: the last timed step's records for a seeded sample, DIR/*.npy)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 """
 import argparse
@@ -307,10 +312,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--pairs", type=int, default=0, help="(default: 1 M; 500 k for c5, the size its earlier lines were quoted at) fragments per GPU per step (C4: about 1250 seed hits and 155 chains per pair, ~100 bytes of workspace per seed hit: 1 M pairs take ~140 GB next to the 23 GB index; a batch that does not fit is halved)")
     ap.add_argument("--read-len", type=int, default=0, help="default: the config's (150; C5: 250)")
+    ap.add_argument("--full", action="store_true", help="also run the legs the headline value does not need: the PCIe-inclusive rate (two more runs of the batch) and, at N=1, the CPU comparator and the file-to-file leg")
     ap.add_argument("--cpu-sample-pairs", type=int, default=2_000_000)   # >= 12 mini-batches of the preset's 50 Mbases: the reference's three-step pipeline has something to overlap
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU comparator")
     ap.add_argument("--f2f-sleep", type=float, default=5.0, help="seconds to wait before each process of the file-to-file leg (recorded in the output)")
-    ap.add_argument("--f2f-pairs", type=int, default=6_250_000, help="pairs of the file-to-file leg (FASTQ files -> airlift-align -> SAM file; rank 0, N=1 only; 0 = skip)")
+    ap.add_argument("--f2f-pairs", type=int, default=6_250_000, help="pairs of the file-to-file leg (--full: FASTQ files -> airlift-align -> SAM file; rank 0, N=1 only; 0 = skip)")
     ap.add_argument("--ins-mean", type=int, default=0, help="mean insert size override (short inserts make the mates overlap: equal-key anchors)")
     ap.add_argument("--config", default="c4", help="workload of tools/gen_synth.py: c4 (default: the configuration BASELINE.json's metric is quoted on -- 150 bp PE against a human-sized reference; fits one GPU), c5 (250 bp), c3 (100 Mbp), c2 (yeast-sized), c2r, c4s, c3u, c4u")
     ap.add_argument("--test-one-gpu", action="store_true", help="N > 1 on a one-GPU box (validation of the sharded path only): every rank uses device 0, collectives over gloo")
@@ -437,16 +443,19 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     dumped = dump_outputs(ctx, a.dump_outputs) if a.dump_outputs and rank == 0 else None     # before the leg below runs the batch again
-    # PCIe-inclusive rate of the same batch (never `value`): pack + H2D upload, run, D2H of the flat result block
-    L.al_batch_fetch_flat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.al_batch_fetch_flat.restype = C.c_int
-    t0 = time.perf_counter(); n_io = 2
-    for _ in range(n_io):
-        upload(a.pairs); ctx.run()
-        nrec, nby = C.c_uint64(), C.c_uint64()
-        if L.al_batch_fetch_flat(ctx.h, C.byref(nrec), C.byref(nby)) != 0:
-            raise SystemExit("fetch failed")
-    torch.cuda.synchronize()
-    dt_io = (time.perf_counter() - t0) / n_io
+    pcie = {}
+    if a.full:
+        # PCIe-inclusive rate of the same batch (never `value`): pack + H2D upload, run, D2H of the flat result block
+        L.al_batch_fetch_flat.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]; L.al_batch_fetch_flat.restype = C.c_int
+        t0 = time.perf_counter(); n_io = 2
+        for _ in range(n_io):
+            upload(a.pairs); ctx.run()
+            nrec, nby = C.c_uint64(), C.c_uint64()
+            if L.al_batch_fetch_flat(ctx.h, C.byref(nrec), C.byref(nby)) != 0:
+                raise SystemExit("fetch failed")
+        torch.cuda.synchronize()
+        dt_io = (time.perf_counter() - t0) / n_io
+        pcie = {"value_incl_pcie": 2.0 * a.pairs / dt_io, "incl_pcie_note": "this rank: 4-bit packing on %d host threads + H2D, one step, D2H of %d records (%.1f MB); serial, no overlap between batches" % (min(32, os.cpu_count() or 1), int(nrec.value), nby.value / 1e6)}
     st = ctx.stat()
     dist_info = None; na = nu = na_p1 = None
     if rank == 0:   # distribution of the per-fragment sizes that decide which kernels run
@@ -548,7 +557,7 @@ def main():
             "scaling": "weak", "vs_baseline": None, "dtype": "u8/int32 (int8 SW lanes, u64 hashes)", "data": "synthetic",
             "config": {"workload": "%s, %d x 2 x %d bp PE reads per GPU per step, preset sr" % (WORKLOADS.get(a.config, a.config), a.pairs, a.read_len), "key": a.config,
                        "reads_per_step_per_gpu": 2 * a.pairs, "pairs_asked_per_gpu": pairs_asked, "read_len": a.read_len, "sharding": "one input of %d fragments, rank r maps the contiguous range [r N / R, (r + 1) N / R); index replicated" % (a.pairs * world)},
-            "value_incl_pcie": 2.0 * a.pairs / dt_io, "incl_pcie_note": "this rank: 4-bit packing on %d host threads + H2D, one step, D2H of %d records (%.1f MB); serial, no overlap between batches" % (min(32, os.cpu_count() or 1), int(nrec.value), nby.value / 1e6),
+            **pcie,
             "roofline": roof,
             "stages_ms": per,
             "merged_output": merged,
@@ -558,13 +567,13 @@ def main():
                          "rechain": int(st.n_rechain), "heap_fallback": int(st.n_heap_fallback), "chain_fallback": int(st.n_chain_fallback), "side_stream_ms": float(st.ms_side_stream), "sort_tie_flags": int(st.n_sort_tie_flag), **(dist_info or {})},
             "host": {"gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES"), "index_build_on_gpu_s": t_index, "pack_upload_s": t_upload, "reference_generation_s": t_gen, "read_simulation_s": t_reads, "reference_model": getattr(ref, "stats", None)},
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             n_cpu = max(1, a.cpu_sample_pairs)
             arr_cpu = arr if n_cpu <= a.pairs else np.concatenate([arr[:a.pairs], make_workload(a.config, a.pairs, n_cpu, a.read_len, 20261002, ref, a.ins_mean)])   # (the same input's next fragments: the sample stays the head of the file-to-file leg's files)
             out["cpu_baseline"], out["e2e_cli"] = cpu_baseline(tmp, "ref.fa", arr_cpu, n_cpu, a.read_len)
             out["parity_sample"] = {"pairs": n_cpu, "identical": out["e2e_cli"]["identical_sam"]}
             del arr_cpu
-        if world == 1 and a.f2f_pairs > 0:
+        if a.full and world == 1 and a.f2f_pairs > 0:
             out["file_to_file"] = file_to_file(tmp, "ref.fa", a, arr, ref, out["value"])
         print(json.dumps(out))
     shutil.rmtree(tmp, ignore_errors=True)

@@ -21,7 +21,7 @@ def _line(out):
 
 
 def test_bench_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--pairs", "200000", "--steps", "2", "--warmup", "1", "--cpu-sample-pairs", "50000"], capture_output=True, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--pairs", "200000", "--steps", "2", "--warmup", "1", "--cpu-sample-pairs", "50000", "--full"], capture_output=True, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     d = _line(r.stdout)
     assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0 and d["higher_is_better"] and d["scaling"] == "weak" and d["vs_baseline"] is None
@@ -31,6 +31,7 @@ def test_bench_single_gpu_line():
     cb = d["cpu_baseline"]
     assert cb["value"] > 0 and cb["kind"] in ("reference", "port") and cb["cores"] >= 1
     assert d["parity_sample"]["identical"] is True
+    assert d["value_incl_pcie"] > 0 and "file_to_file" in d           # --full also runs the legs beside the timed steps
 
 
 def test_bench_dump_outputs_repeatable(tmp_path):
@@ -69,3 +70,4 @@ def test_bench_two_ranks_shard_one_input():
     one = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--pairs", "200000", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"], capture_output=True, cwd=ROOT)
     d1 = _line(one.stdout)
     assert d1["merged_output"]["records"] == m["records"]            # two shards of the one input == the whole input
+    assert "value_incl_pcie" not in d1 and "file_to_file" not in d1   # a plain run (no --full) runs no leg besides the timed steps
