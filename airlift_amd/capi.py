@@ -18,6 +18,7 @@ class AirliftError(RuntimeError):
 # mapping option flags (include/airlift.h; the values of the fork's MM_F_*)
 AL_F_CIGAR = 0x004
 AL_F_OUT_SAM = 0x008
+AL_F_OUT_CG = 0x020
 AL_F_OUT_CS = 0x40
 AL_F_OUT_CS_LONG = 0x800
 AL_F_SR = 0x1000
@@ -27,7 +28,9 @@ AL_F_SOFTCLIP = 0x80000
 AL_F_HEAP_SORT = 0x400000
 AL_F_OUT_MD = 0x1000000
 AL_F_EQX = 0x4000000
+AL_F_PAF_NO_HIT = 0x8000000
 AL_F_SAM_HIT_ONLY = 0x40000000
+AL_F_OUT_PAF = 0x100000000   # ours (above the fork's 32 bits): PAF output; only with it is AL_F_CIGAR looked at (clear = map-only)
 
 
 def lib_path():
@@ -126,6 +129,8 @@ def load():
     L.al_dbg_copy.argtypes = [vp, cs, vp, C.c_int64]; L.al_dbg_copy.restype = C.c_int64
     L.al_dbg_alser_count.argtypes = [vp, C.POINTER(C.c_int64)]; L.al_dbg_alser_count.restype = ci
     L.al_write_sam.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, cs, cs, ci, ci, ci, C.POINTER(ci), C.POINTER(C.POINTER(Reg)), cs, ci]; L.al_write_sam.restype = ci
+    L.al_write_paf.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, C.POINTER(Reg), C.c_int64, ci, cs]; L.al_write_paf.restype = ci
+    L.al_dbg_paf_selftest.argtypes = [C.c_uint64, ci]; L.al_dbg_paf_selftest.restype = ci
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     L.al_version.restype = cs
     L.al_gen_cs.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs, ci]; L.al_gen_cs.restype = ci
@@ -150,6 +155,18 @@ def gen_tag(idx, reg, seq, kind="MD", no_iden=True):
     if n < 0:
         raise AirliftError("al_gen_%s failed" % kind)
     return out
+
+
+def write_paf(idx, qname, l_seq, reg, opt_flag=0, rep_len=-1, tag=None):
+    """al_write_paf (mm_write_paf3): the PAF line (with its newline) of hit `reg` (a Reg as al_map_frag returned it; None: the line of a
+    read without hits) of read `qname` (bytes) with `l_seq` bases.  opt_flag: AL_F_OUT_CG prints cg:Z:, AL_F_OUT_MD / AL_F_OUT_CS name
+    the value `tag` (bytes from gen_tag) holds."""
+    L = load()
+    buf = C.create_string_buffer(65536 + (len(tag) if tag else 0) + (16 * reg.n_cigar if reg is not None else 0))
+    n = L.al_write_paf(buf, len(buf), idx, qname, l_seq, C.byref(reg) if reg is not None else None, opt_flag, rep_len, tag)
+    if n < 0:
+        raise AirliftError("al_write_paf failed")
+    return buf.raw[:n]
 
 
 def read_fastx(path):

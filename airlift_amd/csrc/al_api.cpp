@@ -218,6 +218,49 @@ extern "C" int al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const cha
 	return al_write_sam_ex(buf, cap, mi, qname, l_seq, seq, qual, seg_idx, reg_idx, n_seg, n_regss, regss, rg_id, rep_len, 0, nullptr, 0);
 }
 
+// mm_write_paf3 (format.c:304-330) + write_tags (:276-302): restated on the host next to al_write_sam; the pin of the device formatter (al_dev_paf.h)
+int al_write_paf_ex(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const al_reg1_t *r, int64_t opt_flag, int rep_len, const char *tag, int tag_len)
+{
+	if (!buf || cap < 2 || !mi || !qname) return -1;
+	Out o{buf, buf + cap - 1, false};
+	o.str(qname); o.ch('\t'); o.num(l_seq);
+	if (!r) {
+		o.str("\t0\t0\t*\t*\t0\t0\t0\t0\t0\t0");
+		if (rep_len >= 0) { o.str("\trl:i:"); o.num(rep_len); }
+		o.ch('\n'); *o.p = 0;
+		return o.ovf ? -1 : (int)(o.p - buf);
+	}
+	if (r->rid < 0 || (size_t)r->rid >= mi->seq.size()) return -1;
+	o.ch('\t'); o.num(r->qs); o.ch('\t'); o.num(r->qe); o.ch('\t'); o.ch("+-"[r->rev]); o.ch('\t'); o.str(mi->seq[r->rid].name.c_str());
+	o.ch('\t'); o.num(mi->seq[r->rid].len); o.ch('\t'); o.num(r->rs); o.ch('\t'); o.num(r->re);
+	o.ch('\t'); o.num(r->mlen); o.ch('\t'); o.num(r->blen); o.ch('\t'); o.num(r->mapq);
+	const bool has_p = r->n_cigar && r->cigar;
+	const char type = r->id == r->parent ? (r->inv ? 'I' : 'P') : (r->inv ? 'i' : 'S');
+	if (has_p) { o.str("\tNM:i:"); o.num(r->blen - r->mlen + (int)r->n_ambi); o.str("\tms:i:"); o.num(r->dp_max); o.str("\tAS:i:"); o.num(r->dp_score); o.str("\tnn:i:"); o.num(r->n_ambi); }
+	o.str("\ttp:A:"); o.ch(type); o.str("\tcm:i:"); o.num(r->cnt); o.str("\ts1:i:"); o.num(r->score);
+	if (r->parent == r->id) { o.str("\ts2:i:"); o.num(r->subsc); }
+	if (has_p) {
+		int n_gapo = 0, n_gap = 0;
+		for (uint32_t i = 0; i < r->n_cigar; ++i) { int op = r->cigar[i] & 0xf, len = r->cigar[i] >> 4; if (op == 1 || op == 2) ++n_gapo, n_gap += len; }
+		const double div = 1.0 - (double)r->mlen / (r->blen - n_gap + n_gapo);
+		if (div == 0.0) o.str("\tde:f:0"); else { char b[32]; snprintf(b, 32, "%.4f", div); o.str("\tde:f:"); o.str(b); }
+	}
+	if (r->split) { o.str("\tzd:i:"); o.num(r->split); }
+	if (rep_len >= 0) { o.str("\trl:i:"); o.num(rep_len); }
+	if (has_p && (opt_flag & AL_F_OUT_CG)) {
+		o.str("\tcg:Z:");
+		for (uint32_t k = 0; k < r->n_cigar; ++k) { o.num(r->cigar[k] >> 4); o.ch("MIDNSHP=XB"[r->cigar[k] & 0xf]); }
+	}
+	const int tk = (opt_flag & AL_F_OUT_MD) ? 1 : (opt_flag & AL_F_OUT_CS) ? 2 : 0;      // (format.c:327: whatever the record carries, MD wins)
+	if (has_p && tag && tk) { o.str(tk == 1 ? "\tMD:Z:" : "\tcs:Z:"); o.mem(tag, tag_len); }
+	o.ch('\n'); *o.p = 0;
+	return o.ovf ? -1 : (int)(o.p - buf);
+}
+extern "C" int al_write_paf(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const al_reg1_t *r, int64_t opt_flag, int rep_len, const char *tag)
+{
+	return al_write_paf_ex(buf, cap, mi, qname, l_seq, r, opt_flag, rep_len, tag, tag ? (int)strlen(tag) : 0);
+}
+
 // mm_gen_cs / mm_gen_MD (format.c:137-234, 546-560) for API callers: one record at a time on the host.  The file drivers compute the
 // same strings for whole batches on the device (al_kernels_tags.hip); this is the path of al_map_frag users.
 static int gen_cs_or_MD(char **buf, int *max_len, const al_idx_t *mi, const al_reg1_t *r, const char *seq, int no_iden, int is_MD)
@@ -429,6 +472,75 @@ extern "C" int al_dbg_sam_selftest(uint64_t seed, int n_frag)
 				if (bad < 2) fprintf(stderr, "[airlift] sam selftest: fragment %d read %d differs (counted %llu bytes)\n  al_write_sam: %s  formatter:    %s", f, j, (unsigned long long)cnt.n, exp.c_str(), o.out.c_str());
 				++bad;
 			}
+		}
+	}
+	return bad;
+}
+
+// The PAF twin: the device formatter of al_dev_paf.h compiled for the CPU against al_write_paf on random reads -- hits with and without a
+// CIGAR (inline and in the arena), both orientations, secondaries, reads without hits, every option.  Returns the number of differences.
+#include "al_dev_paf.h"
+extern "C" int al_dbg_paf_selftest(uint64_t seed, int n_frag)
+{
+	int bad = 0;
+	Rng R{seed * 2654435761ULL + 88172645463325252ULL};
+	al_idx_t mi; const char *cn[3] = {"chr1", "contig_two", "c"}; const uint32_t cl[3] = {1000000u, 77u, 4000000000u};
+	for (int i = 0; i < 3; ++i) { AlSeq s; s.name = cn[i]; s.offset = 0; s.len = cl[i]; mi.seq.push_back(s); }
+	std::string names; std::vector<uint32_t> noff; for (int i = 0; i < 3; ++i) { noff.push_back((uint32_t)names.size()); names += cn[i]; } noff.push_back((uint32_t)names.size());
+	for (int f = 0; f < n_frag && bad < 20; ++f) {
+		const int L = 30 + (int)R.below(220), rep_len = (int)R.below(3) == 0 ? -1 : (int)R.below(200);
+		const std::string nm = "read" + std::to_string(f) + (R.below(2) ? "/" + std::to_string(1 + R.below(2)) : std::string());
+		std::string text = nm; text.push_back('\n');
+		AlSamRead rd; rd.name = 0; rd.name_len = (uint32_t)nm.size(); rd.seq = rd.qual = ~0u; rd.qlen = L; rd.flip = (int)R.below(2);
+		std::vector<AlReg> regs; std::vector<uint32_t> arena;
+		const int n = (int)R.below(4) == 0 ? 0 : 1 + (int)R.below(5);
+		const bool aligned = R.below(2) != 0;                        // map-only runs leave no record with a CIGAR
+		for (int k = 0; k < n; ++k) {
+			AlReg r; memset(&r, 0, sizeof(r));
+			r.id = k; r.parent = R.below(3) == 0 && k > 0 ? (int)R.below((uint32_t)k) : k; r.rid = (int)R.below(3); r.cnt = 1 + (int)R.below(30); r.score = (int)R.below(300);
+			r.qs = (int)R.below((uint32_t)L / 2); r.qe = r.qs + 1 + (int)R.below((uint32_t)(L - r.qs)); r.rs = (int)R.below(900000); r.re = r.rs + (r.qe - r.qs) + (int)R.below(7);
+			r.subsc = (int)R.below(200); r.mlen = (int)R.below(200); r.blen = r.mlen + (int)R.below(30); r.mapq = R.below(61);
+			r.dp_score = (int)R.below(300); r.dp_max = (int)R.below(300); r.n_ambi = R.below(3);
+			r.flags = R.below(4) == 0 ? R.below(4) : 0; if (R.below(2)) r.flags |= ALR_REV;
+			if (aligned && R.below(8) != 0) {
+				r.flags |= ALR_HAS_P; r.n_cigar = 1 + R.below(R.below(4) == 0 ? 9u : 3u);
+				uint32_t *cg;
+				if (r.n_cigar <= 4) { r.cigar_off = AL_CIG_INLINE; cg = r.cig_inl; } else { r.cigar_off = (uint32_t)arena.size(); arena.resize(arena.size() + r.n_cigar); cg = arena.data() + r.cigar_off; }
+				int bl = 0, ml = 0;
+				for (uint32_t i = 0; i < r.n_cigar; ++i) { cg[i] = (1 + R.below(120)) << 4 | (i % 2 == 0 ? (R.below(3) == 0 ? 7u + R.below(2) : 0u) : 1u + R.below(2)); bl += (int)(cg[i] >> 4); if ((cg[i] & 0xf) != 1 && (cg[i] & 0xf) != 2) ml += (int)(cg[i] >> 4); }
+				r.blen = bl; r.mlen = (int)R.below((uint32_t)ml + 1);
+			}
+			regs.push_back(r);
+		}
+		rd.regs = regs.data(); rd.n_regs = n; rd.arena = arena.data();
+		int64_t flag = 0;
+		if (R.below(2)) flag |= AL_F_NO_PRINT_2ND; if (R.below(2)) flag |= AL_F_PAF_NO_HIT; if (R.below(2)) flag |= AL_F_OUT_CG;
+		{ const uint32_t o = R.below(4); if (o == 1) flag |= AL_F_OUT_MD; else if (o == 2) flag |= AL_F_OUT_CS; else if (o == 3) flag |= AL_F_OUT_CS | AL_F_OUT_MD; }
+		AlSamCfg C; C.names = names.data(); C.name_off = noff.data(); C.rg_id = ""; C.rg_len = 0; C.hit_only = 0; C.pe_ori = 1;
+		C.no_print_2nd = (flag & AL_F_NO_PRINT_2ND) ? 1 : 0; C.paf_no_hit = (flag & AL_F_PAF_NO_HIT) ? 1 : 0; C.out_cg = (flag & AL_F_OUT_CG) ? 1 : 0;
+		C.tag_kind = al_tag_kind(flag); C.tag_reg0 = regs.data(); C.ctg_len = cl;
+		std::string tags; std::vector<uint64_t> tag_off(1, 0);
+		for (int k = 0; k < n; ++k) { const int l = (int)R.below(40); for (int i = 0; i < l; ++i) tags.push_back("0123456789ACGT^*:=+-acgt"[R.below(24)]); tag_off.push_back(tags.size()); }
+		std::string exp; std::vector<char> buf(1 << 14);
+		for (int k = 0; k < n; ++k) {
+			const AlReg &r = regs[k];
+			if ((flag & AL_F_NO_PRINT_2ND) && r.id != r.parent) continue;
+			al_reg1_t q; memset(&q, 0, sizeof(q));                   // AlReg -> al_reg1_t with the un-flip of al_reg_from_raw
+			q.id = r.id; q.cnt = r.cnt; q.rid = r.rid; q.score = r.score; q.qs = r.qs; q.qe = r.qe; q.rs = r.rs; q.re = r.re; q.parent = r.parent; q.subsc = r.subsc; q.mlen = r.mlen; q.blen = r.blen;
+			q.mapq = r.mapq & 0xff; q.split = r.flags & 3; q.rev = (r.flags & ALR_REV) ? 1 : 0; q.dp_score = r.dp_score; q.dp_max = r.dp_max; q.n_ambi = r.n_ambi; q.n_cigar = (r.flags & ALR_HAS_P) ? r.n_cigar : 0;
+			q.cigar = q.n_cigar ? const_cast<uint32_t *>(r.cigar_off == AL_CIG_INLINE ? r.cig_inl : arena.data() + r.cigar_off) : nullptr;
+			if (rd.flip) { const int t = q.qs; q.qs = L - q.qe; q.qe = L - t; q.rev = !q.rev; }
+			const std::string tv = tags.substr(tag_off[k], tag_off[k + 1] - tag_off[k]);
+			const int l = al_write_paf(buf.data(), buf.size(), &mi, nm.c_str(), L, &q, flag, rep_len, al_tag_kind(flag) ? tv.c_str() : nullptr);
+			if (l > 0) exp.append(buf.data(), (size_t)l); else ++bad;
+		}
+		if (n == 0 && (flag & AL_F_PAF_NO_HIT)) { const int l = al_write_paf(buf.data(), buf.size(), &mi, nm.c_str(), L, nullptr, flag, rep_len, nullptr); if (l > 0) exp.append(buf.data(), (size_t)l); else ++bad; }
+		HostSamSink o; o.C = &C; o.text = text.data(); o.tag_off = tag_off.data(); o.tag_txt = tags.data();
+		AlSamCountSink cnt; cnt.C = &C; cnt.text = text.data(); cnt.tag_off = tag_off.data();
+		al_paf_read_records(o, C, rd, rep_len); al_paf_read_records(cnt, C, rd, rep_len);
+		if (o.out != exp || cnt.n != exp.size()) {
+			if (bad < 2) fprintf(stderr, "[airlift] paf selftest: read %d differs (counted %llu bytes)\n  al_write_paf: %s  formatter:    %s", f, (unsigned long long)cnt.n, exp.c_str(), o.out.c_str());
+			++bad;
 		}
 	}
 	return bad;

@@ -342,40 +342,50 @@ AL_D int d_squeeze_a(int n_regs, AlReg *regs, AlAnchor *a, uint64_t *aux)
 	return as;
 }
 
-// mm_set_mapq, hit.c:446-491 (is_sr = 1; no inversions on this path).  float32 + logf as the reference.
+// mm_set_mapq, hit.c:446-491 (is_sr = 1; no inversions on this path).  float32 + logf as the reference.  In two parts, so that the
+// map-only kernel (k_map_only) can give the records of one read to the lanes of a wavefront: the sum over the primaries, then every
+// record on its own.
+AL_D long long d_mapq_sum(int n_regs, const AlReg *regs)
+{
+	long long sum_sc = 0;
+	for (int i = 0; i < n_regs; ++i) if (regs[i].parent == regs[i].id) sum_sc += regs[i].score;
+	return sum_sc;
+}
+AL_D float d_mapq_uniq_ratio(long long sum_sc, int rep_len) { return (float)((double)(float)sum_sc / (double)(float)(sum_sc + rep_len)); }
+AL_D void d_mapq_one(AlReg *r, float uniq_ratio, int min_chain_sc, const AlLogTab &lt)
+{
+	const float q_coef = 40.0f;
+	if (r->flags & ALR_INV) r->mapq = 0;
+	else if (r->parent == r->id) {
+		int mapq;
+		const float pen_s1 = __fmul_rn((r->score > 100 ? 1.0f : __fmul_rn(0.01f, (float)r->score)), uniq_ratio);
+		float pen_cm = r->cnt > 10 ? 1.0f : __fmul_rn(0.1f, (float)r->cnt);
+		pen_cm = pen_s1 < pen_cm ? pen_s1 : pen_cm;
+		const int subsc = r->subsc > min_chain_sc ? r->subsc : min_chain_sc;
+		const bool has_p = (r->flags & ALR_HAS_P) != 0;
+		if (has_p && r->dp_max2 > 0 && r->dp_max > 0) {
+			const float identity = al_fdiv((float)r->mlen, (float)r->blen);
+			const float x = al_fdiv(al_fdiv(__fmul_rn((float)r->dp_max2, (float)subsc), (float)r->dp_max), (float)r->score0);
+			const float lg = al_logf_q(lt, r->dp_max);
+			mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(__fmul_rn(identity, pen_cm), q_coef), __fsub_rn(1.0f, __fmul_rn(x, x))), lg);
+		} else {
+			const float x = al_fdiv((float)subsc, (float)r->score0);
+			if (has_p) {
+				const float identity = al_fdiv((float)r->mlen, (float)r->blen);
+				const float lg = al_logf_q(lt, r->dp_max);
+				mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(__fmul_rn(identity, pen_cm), q_coef), __fsub_rn(1.0f, x)), lg);
+			} else mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(pen_cm, q_coef), __fsub_rn(1.0f, x)), al_logf_i(lt, r->score));   // no base-level alignment (r->p == 0, hit.c:479)
+		}
+		mapq -= (int)__fadd_rn(__fmul_rn(4.343f, al_logf_i(lt, r->n_sub + 1)), .499f);
+		mapq = mapq > 0 ? mapq : 0;
+		r->mapq = mapq < 60 ? mapq : 60;
+		if (has_p && r->dp_max > r->dp_max2 && r->mapq == 0) r->mapq = 1;
+	} else r->mapq = 0;
+}
 AL_D void d_set_mapq(int n_regs, AlReg *regs, int min_chain_sc, int match_sc, int rep_len, const AlLogTab &lt)
 {
-	const float q_coef = 40.0f; long long sum_sc = 0;
+	(void)match_sc;                                                   // (logf(dp_max / match_sc) comes from the table, which is built for it)
 	if (n_regs == 0) return;
-	for (int i = 0; i < n_regs; ++i) if (regs[i].parent == regs[i].id) sum_sc += regs[i].score;
-	const float uniq_ratio = (float)((double)(float)sum_sc / (double)(float)(sum_sc + rep_len));
-	for (int i = 0; i < n_regs; ++i) {
-		AlReg *r = &regs[i];
-		if (r->flags & ALR_INV) r->mapq = 0;
-		else if (r->parent == r->id) {
-			int mapq;
-			const float pen_s1 = __fmul_rn((r->score > 100 ? 1.0f : __fmul_rn(0.01f, (float)r->score)), uniq_ratio);
-			float pen_cm = r->cnt > 10 ? 1.0f : __fmul_rn(0.1f, (float)r->cnt);
-			pen_cm = pen_s1 < pen_cm ? pen_s1 : pen_cm;
-			const int subsc = r->subsc > min_chain_sc ? r->subsc : min_chain_sc;
-			const bool has_p = (r->flags & ALR_HAS_P) != 0;
-			if (has_p && r->dp_max2 > 0 && r->dp_max > 0) {
-				const float identity = al_fdiv((float)r->mlen, (float)r->blen);
-				const float x = al_fdiv(al_fdiv(__fmul_rn((float)r->dp_max2, (float)subsc), (float)r->dp_max), (float)r->score0);
-				const float lg = al_logf_q(lt, r->dp_max);
-				mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(__fmul_rn(identity, pen_cm), q_coef), __fsub_rn(1.0f, __fmul_rn(x, x))), lg);
-			} else {
-				const float x = al_fdiv((float)subsc, (float)r->score0);
-				if (has_p) {
-					const float identity = al_fdiv((float)r->mlen, (float)r->blen);
-					const float lg = al_logf_q(lt, r->dp_max);
-					mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(__fmul_rn(identity, pen_cm), q_coef), __fsub_rn(1.0f, x)), lg);
-				} else mapq = (int)__fmul_rn(__fmul_rn(__fmul_rn(pen_cm, q_coef), __fsub_rn(1.0f, x)), al_logf_i(lt, r->score));
-			}
-			mapq -= (int)__fadd_rn(__fmul_rn(4.343f, al_logf_i(lt, r->n_sub + 1)), .499f);
-			mapq = mapq > 0 ? mapq : 0;
-			r->mapq = mapq < 60 ? mapq : 60;
-			if (has_p && r->dp_max > r->dp_max2 && r->mapq == 0) r->mapq = 1;
-		} else r->mapq = 0;
-	}
+	const float uniq_ratio = d_mapq_uniq_ratio(d_mapq_sum(n_regs, regs), rep_len);
+	for (int i = 0; i < n_regs; ++i) d_mapq_one(&regs[i], uniq_ratio, min_chain_sc, lt);
 }

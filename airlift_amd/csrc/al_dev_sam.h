@@ -53,6 +53,8 @@ struct AlSamCfg {                     // what the formatter needs besides the re
 	int softclip = 0;                 // AL_F_SOFTCLIP (-Y): S clips and full SEQ / QUAL on supplementary and secondary records
 	int tag_kind = 0;                 // al_tag_kind(): 0 none, 1 MD:Z, 2 cs:Z -- the value of output record k is the sink's tag(k) ...
 	const AlReg *tag_reg0 = nullptr;  // ... k counted from this record (the batch's first)
+	const uint32_t *ctg_len = nullptr;    // PAF (al_dev_paf.h): contig lengths, ...
+	int out_cg = 0, paf_no_hit = 0;       // ... AL_F_OUT_CG, AL_F_PAF_NO_HIT
 };
 
 struct AlSamRead {                    // one read as the formatter sees it
@@ -73,6 +75,30 @@ AL_SD AlSamView al_sam_view(const AlReg &r, int qlen, int flip)
 AL_SD uint32_t al_sam_ncig(const AlReg &r) { return (r.flags & ALR_HAS_P) ? r.n_cigar : 0u; }
 AL_SD const uint32_t *al_sam_cig(const AlReg &r, const uint32_t *arena) { return r.cigar_off == AL_CIG_INLINE ? r.cig_inl : arena + r.cigar_off; }
 AL_SD int al_sam_pri_idx(const AlReg *r, int n) { for (int i = 0; i < n; ++i) if (r[i].flags & ALR_SAM_PRI) return i; return -1; }
+
+// write_tags (format.c:276-302), shared by the SAM and the PAF record: the NM / ms / AS / nn group and de:f: only on a record with a CIGAR
+// (r->p); dv:f: does not occur (mm_est_err is skipped for short reads, map.c:387)
+template <class S>
+AL_SD void al_sam_write_tags(S &o, const AlReg &r, const uint32_t *cig, const uint32_t n_cig)
+{
+	const char type = r.id == r.parent ? 'P' : 'S';                       // inversions do not occur on this path (inv = 0)
+	if (n_cig) { o.lit("\tNM:i:"); o.num(r.blen - r.mlen + (int)r.n_ambi); o.lit("\tms:i:"); o.num(r.dp_max); o.lit("\tAS:i:"); o.num(r.dp_score); o.lit("\tnn:i:"); o.num((int)r.n_ambi); }
+	o.lit("\ttp:A:"); o.ch(type); o.lit("\tcm:i:"); o.num(r.cnt); o.lit("\ts1:i:"); o.num(r.score);
+	if (r.parent == r.id) { o.lit("\ts2:i:"); o.num(r.subsc); }
+	if (n_cig) {
+		int n_gapo = 0, n_gap = 0;
+		for (uint32_t i = 0; i < n_cig; ++i) { const int op = cig[i] & 0xf, len = (int)(cig[i] >> 4); if (op == 1 || op == 2) ++n_gapo, n_gap += len; }
+		const double div = 1.0 - (double)r.mlen / (double)(r.blen - n_gap + n_gapo);
+		if (div == 0.0) o.lit("\tde:f:0");
+		else {
+			bool neg; uint64_t q; al_fmt_f4(div, &neg, &q);
+			o.lit("\tde:f:"); if (neg) o.ch('-');
+			o.num((long long)(q / 10000)); o.ch('.');
+			const int fr = (int)(q % 10000); o.ch((char)('0' + fr / 1000)); o.ch((char)('0' + fr / 100 % 10)); o.ch((char)('0' + fr / 10 % 10)); o.ch((char)('0' + fr % 10));
+		}
+	}
+	if (r.flags & 3u) { o.lit("\tzd:i:"); o.num((int)(r.flags & 3u)); }
+}
 
 // One record.  reg_idx < 0: the unmapped record of a read without hits.  `me` is the read, `mate` the other read of the pair
 // (nullptr for single-end), seg_idx its position in the fragment.  Sink: ch(c), lit("..."), num(v), txt(off, len) (bytes of the
@@ -140,23 +166,7 @@ AL_SD void al_sam_record(S &o, const AlSamCfg &C, const AlSamRead &me, const AlS
 	else { o.seqfld(me.seq + v.qs, v.qe - v.qs, v.rev, v.rev, 1); o.ch('\t'); if (hq) o.seqfld(me.qual + v.qs, v.qe - v.qs, v.rev, 0, 0); else o.ch('*'); }
 	if (C.rg_len > 0) { o.lit("\tRG:Z:"); o.mem(C.rg_id, C.rg_len); }
 	if (r) {
-		const char type = r->id == r->parent ? 'P' : 'S';                       // inversions do not occur on this path (inv = 0)
-		if (n_cig) { o.lit("\tNM:i:"); o.num(r->blen - r->mlen + (int)r->n_ambi); o.lit("\tms:i:"); o.num(r->dp_max); o.lit("\tAS:i:"); o.num(r->dp_score); o.lit("\tnn:i:"); o.num((int)r->n_ambi); }
-		o.lit("\ttp:A:"); o.ch(type); o.lit("\tcm:i:"); o.num(r->cnt); o.lit("\ts1:i:"); o.num(r->score);
-		if (r->parent == r->id) { o.lit("\ts2:i:"); o.num(r->subsc); }
-		if (n_cig) {
-			int n_gapo = 0, n_gap = 0;
-			for (uint32_t i = 0; i < n_cig; ++i) { const int op = cig[i] & 0xf, len = (int)(cig[i] >> 4); if (op == 1 || op == 2) ++n_gapo, n_gap += len; }
-			const double div = 1.0 - (double)r->mlen / (double)(r->blen - n_gap + n_gapo);
-			if (div == 0.0) o.lit("\tde:f:0");
-			else {
-				bool neg; uint64_t q; al_fmt_f4(div, &neg, &q);
-				o.lit("\tde:f:"); if (neg) o.ch('-');
-				o.num((long long)(q / 10000)); o.ch('.');
-				const int fr = (int)(q % 10000); o.ch((char)('0' + fr / 1000)); o.ch((char)('0' + fr / 100 % 10)); o.ch((char)('0' + fr / 10 % 10)); o.ch((char)('0' + fr % 10));
-			}
-		}
-		if (r->flags & 3u) { o.lit("\tzd:i:"); o.num((int)(r->flags & 3u)); }
+		al_sam_write_tags(o, *r, cig, n_cig);
 		if (r->parent == r->id && n_cig && n_regs > 1) {
 			int n_sa = 0;
 			for (int i = 0; i < n_regs; ++i) if (i != reg_idx && regs[i].parent == regs[i].id && al_sam_ncig(regs[i])) ++n_sa;

@@ -1607,7 +1607,7 @@ k_regs(const AlAnchor *__restrict__ chained, const uint64_t *__restrict__ u_all,
 			else { st_step(S0, first, pv, a1, tl, ql, span); if (first) f0 = a1; l0 = a1; bl0 += db; ml0 += dm; sa0[w0++] = a1; }
 		}
 		auto st_done = [&](Stretch &S, const uint32_t c, const AlAnchor &fa, const AlAnchor &la, const uint32_t sid) {
-			if (c == 0) return;
+			if (c == 0 || !W.rext) return;                                         // (no rext: map-only run, nothing is extended)
 			AlAnchor A = fa, B = la;                                              // cnt < 2: the whole (one-anchor) hit
 			if (c >= 2) { if (S.score > S.max_score) { S.mf = S.cf; S.ml = la; } A = S.mf; B = S.ml; }
 			RegExt x; x.rs0 = x.re0 = x.core_score = 0; x.job = 0;
@@ -2723,6 +2723,51 @@ k_compact(const uint32_t *__restrict__ frag_first, WsBase W, const uint64_t *__r
 	}
 }
 
+// Map-only runs (AL_F_OUT_PAF without AL_F_CIGAR; the fork's `-x sr` without -a / -c): what is left of mm_map_frag after mm_seg_gen and the
+// per-mate mm_set_parent when align_regs returns at once (map.c:262) -- mm_set_mapq per mate on chain-level hits (no r->p), no mm_pair
+// (map.c:404), no mm_filter_regs -- fused with the compaction: every hit is read once from its mate's array, gets its MAPQ and is
+// written once to the dense output.  A lane per fragment takes the mates with up to AL_MO_LIGHT hits (nearly all: one or two); a mate
+// with more (a read in a repeat keeps up to best_n secondaries per primary) goes to a list and k_map_only_wave gives it a wavefront,
+// a hit per lane, so that one such read does not hold 63 other fragments up.
+#define AL_MO_LIGHT 4
+template <bool WAVE>
+__device__ __forceinline__ void d_map_only_mate(const AlReg *__restrict__ m, AlReg *__restrict__ o, const int n, const int lane, const int rep_len, const int min_chain_sc, const AlLogTab &lt)
+{
+	long long sum_sc = 0;
+	for (int i = lane; i < n; i += WAVE ? 64 : 1) if (m[i].parent == m[i].id) sum_sc += m[i].score;
+	if (WAVE) for (int d = 32; d > 0; d >>= 1) sum_sc += __shfl_xor(sum_sc, d, 64);
+	const float uniq_ratio = d_mapq_uniq_ratio(sum_sc, rep_len);
+	for (int i = lane; i < n; i += WAVE ? 64 : 1) { AlReg r = m[i]; d_mapq_one(&r, uniq_ratio, min_chain_sc, lt); o[i] = r; }
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_map_only(const uint32_t *__restrict__ frag_first, const int32_t *__restrict__ frag_rep, WsBase W, const uint64_t *__restrict__ out_off, AlReg *__restrict__ out, int n_frag,
+           int min_chain_sc, AlLogTab lt, uint32_t *__restrict__ heavy_list, uint32_t *__restrict__ heavy_cnt)
+{
+	const int f = blockIdx.x * blockDim.x + threadIdx.x;
+	if (f >= n_frag) return;
+	const uint32_t r0 = frag_first[f], n_segs = frag_first[f + 1] - r0;
+	if (W.frag_nu[f] == 0) return;
+	FragWs fw; d_frag_ws(W, (uint32_t)f, fw);
+	const int rep_len = frag_rep[f];
+	for (uint32_t s = 0; s < n_segs; ++s) {
+		const uint32_t n = W.reg_cnt[r0 + s];
+		if (n == 0) continue;
+		if (n > AL_MO_LIGHT) { heavy_list[atomicAdd(heavy_cnt, 1u)] = (uint32_t)f << 1 | s; continue; }       // (at most one entry per read: the list has n_reads slots)
+		d_map_only_mate<false>(s ? fw.mreg[1] : fw.mreg[0], out + out_off[r0 + s], (int)n, 0, rep_len, min_chain_sc, lt);
+	}
+}
+extern "C" __global__ void __launch_bounds__(64)
+k_map_only_wave(const uint32_t *__restrict__ frag_first, const int32_t *__restrict__ frag_rep, WsBase W, const uint64_t *__restrict__ out_off, AlReg *__restrict__ out,
+                int min_chain_sc, AlLogTab lt, const uint32_t *__restrict__ heavy_list, const uint32_t *__restrict__ heavy_cnt)
+{
+	const uint32_t n_list = *heavy_cnt;
+	for (uint32_t e = blockIdx.x; e < n_list; e += gridDim.x) {
+		const uint32_t f = heavy_list[e] >> 1, s = heavy_list[e] & 1u, r0 = frag_first[f];
+		FragWs fw; d_frag_ws(W, f, fw);
+		d_map_only_mate<true>(s ? fw.mreg[1] : fw.mreg[0], out + out_off[r0 + s], (int)W.reg_cnt[r0 + s], (int)threadIdx.x, frag_rep[f], min_chain_sc, lt);
+	}
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side of the stage
 struct CastU64b { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
@@ -2784,6 +2829,7 @@ int al_run_align_stage(al_ctx_t *c)
 	hipStream_t s = c->stream;
 	AlignState *A = get_state(c);
 	const int nf = c->n_frag, nr = c->n_reads;
+	const bool map_only = al_map_only(c->opt.flag);
 	A->eqx_on = false;
 	if (nf == 0) { for (int i = ST_REGS; i < ST_COMPACT; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); return 0; }
 	// logf table from the HOST libm (the reference's logf is glibc's): logf((float)k / a) and logf((float)k)
@@ -2878,10 +2924,10 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipMemcpyAsync(&b2_total, A->b2_off.p + nf, 8, hipMemcpyDeviceToHost, s));
 		AL_HIP_CHECK(hipStreamSynchronize(s));
 		Btot2 = b2_total + 8;
-		if (A->mregs.ensure(2 * Btot2) || A->rtmp.ensure(Btot2) || A->rext.ensure(2 * Btot2 + 1)) return -1;
+		if (A->mregs.ensure(2 * Btot2) || A->rtmp.ensure(Btot2) || (!map_only && A->rext.ensure(2 * Btot2 + 1))) return -1;
 		{ static const char *scrub = getenv("AL_TEST_SCRUB");
-		  if (scrub) { const int v = atoi(scrub); AL_HIP_CHECK(hipMemsetAsync(A->mregs.p, v, A->mregs.cap * sizeof(AlReg), s)); AL_HIP_CHECK(hipMemsetAsync(A->rtmp.p, v, A->rtmp.cap * sizeof(AlReg), s)); AL_HIP_CHECK(hipMemsetAsync(A->rext.p, v, A->rext.cap * sizeof(RegExt), s)); } }
-		W.mregs = A->mregs.p; W.rtmp = A->rtmp.p; W.rext = A->rext.p; W.cap2 = A->cap2.p; W.b2_off = A->b2_off.p;
+		  if (scrub) { const int v = atoi(scrub); AL_HIP_CHECK(hipMemsetAsync(A->mregs.p, v, A->mregs.cap * sizeof(AlReg), s)); AL_HIP_CHECK(hipMemsetAsync(A->rtmp.p, v, A->rtmp.cap * sizeof(AlReg), s)); if (!map_only) AL_HIP_CHECK(hipMemsetAsync(A->rext.p, v, A->rext.cap * sizeof(RegExt), s)); } }
+		W.mregs = A->mregs.p; W.rtmp = A->rtmp.p; W.rext = map_only ? nullptr : A->rext.p; W.cap2 = A->cap2.p; W.b2_off = A->b2_off.p;
 	}
 	int regs_part = 0;
 	if (regs_n0 && heavy_n > 0) {
@@ -2945,6 +2991,24 @@ int al_run_align_stage(al_ctx_t *c)
 		        (unsigned long long)n_done, (unsigned long long)n_set, mx_set, mx_set_nu, (unsigned long long)n_unset, mx_unset);
 	}
 	AL_HIP_CHECK(hipEventRecord(c->ev[ST_REGS + 1], s));
+	if (map_only) {   // no extension stage: no jobs, no DP, no CIGAR arena, no traceback areas -- MAPQ of the chain-level hits and the dense output in one step
+		for (int i = ST_EXT_PREP; i <= ST_EXT_FINISH; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s));        // (empty intervals)
+		AL_HIP_CHECK(hipMemsetAsync(A->reg_cnt.p + nr, 0, 4, s));
+		if (scan32(c, A->reg_cnt.p, A->out_off.p, nr)) return -1;
+		uint64_t out_total = 0;
+		AL_HIP_CHECK(hipMemcpyAsync(&out_total, A->out_off.p + nr, 8, hipMemcpyDeviceToHost, s));
+		AL_HIP_CHECK(hipStreamSynchronize(s));
+		if (A->out.ensure(out_total + 1) || A->slow_list.ensure((size_t)nr + 1)) return -1;
+		A->out_total = out_total;
+		uint32_t *heavy_cnt = (uint32_t *)(c->counters.p + 14);
+		AL_HIP_CHECK(hipMemsetAsync(heavy_cnt, 0, sizeof(unsigned long long), s));
+		AlLogTab lt; lt.t = A->logtab.p; lt.n = A->logtab_n; lt.miss = c->counters.p + 8;
+		hipLaunchKernelGGL(k_map_only, dim3((nf + 255) / 256), dim3(256), 0, s, c->frag_first.p, c->frag_rep.p, W, A->out_off.p, A->out.p, nf, c->P.min_chain_score, lt, A->slow_list.p, heavy_cnt);
+		hipLaunchKernelGGL(k_map_only_wave, dim3(std::min(nr, 2048)), dim3(64), 0, s, c->frag_first.p, c->frag_rep.p, W, A->out_off.p, A->out.p, c->P.min_chain_score, lt, A->slow_list.p, heavy_cnt);
+		AL_HIP_CHECK(hipGetLastError());
+		AL_HIP_CHECK(hipEventRecord(c->ev[ST_MAPONLY + 1], s));
+		return 0;
+	}
 	// extension stage geometry
 	const int Lmax = c->max_rd_len;
 	const al_mapopt_t &o = c->opt;
@@ -3203,6 +3267,7 @@ int al_run_align_stage(al_ctx_t *c)
 		fprintf(stderr, "[airlift] DP differential check: %llu mismatching calls\n", h[0]);
 		for (unsigned long long k = 0; k < h[0] && k < 32; ++k) { const unsigned long long *o = h.data() + 1 + k * 16; fprintf(stderr, "  qlen=%llu tlen=%llu flag=%llu max %d/%d max_t %d/%d max_q %d/%d mqe %d/%d mqe_t %d/%d score %d/%d zd %llu\n", o[0], o[1], o[2], (int)o[3], (int)o[4], (int)o[5], (int)o[6], (int)o[7], (int)o[8], (int)o[9], (int)o[10], (int)o[11], (int)o[12], (int)o[13], (int)o[14], o[15]); }
 	}
+	AL_HIP_CHECK(hipEventRecord(c->ev[ST_MAPONLY + 1], s));          // (empty: the interval of map-only runs)
 	// dense output
 	AL_HIP_CHECK(hipMemsetAsync(A->reg_cnt.p + nr, 0, 4, s));
 	if (scan32(c, A->reg_cnt.p, A->out_off.p, nr)) return -1;

@@ -11,6 +11,7 @@
 //   N3     airlift-align ... --bam | --sorted-bam [-l LEVEL]       BAM on stdout; sorted = mapped records in coordinate order,
 //                                                                   i.e. the result of `| samtools view -h -F4 | samtools sort -l5`
 //   N2     airlift-align tokens --read-size R --skip S [-t N] REF.fa GAPS.fa      gaps_to_fasta.py GAPS.fa R tokens.fa S ; samse REF x tokens.fa
+//   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
 #include <stdio.h>
@@ -33,21 +34,39 @@ static long long parse_num(const char *str, const char *opt)
 	return (long long)(x + .499);
 }
 
-// output options of the fork's command line (main.c:164, 207, 210, 223-233): 1 if `a` was one of them
-static int parse_out_opt(const char *a, al_mapopt_t &mo)
+// output options of the fork's command line (main.c:158, 164, 207, 210-233) and --paf: 1 if `a` was one of them.  The fork writes PAF unless -a
+// is given; here SAM stays the default (every existing invocation keeps its output) and --paf selects PAF, whatever else (-a, -ax) was said.
+// As in the fork, PAF comes without base-level alignment unless -c or --cs asks for it (--MD alone does not, and then prints nothing).
+struct OutSel { bool paf = false, aln = false; };
+static int parse_out_opt(const char *a, al_mapopt_t &mo, OutSel &sel)
 {
 	if (!strcmp(a, "--MD")) mo.flag |= AL_F_OUT_MD;
 	else if (!strcmp(a, "--eqx")) mo.flag |= AL_F_EQX;
 	else if (!strcmp(a, "-Y")) mo.flag |= AL_F_SOFTCLIP;
+	else if (!strcmp(a, "--paf")) sel.paf = true;
+	else if (!strcmp(a, "-c")) { mo.flag |= AL_F_OUT_CG; sel.aln = true; }
+	else if (!strcmp(a, "--paf-no-hit")) mo.flag |= AL_F_PAF_NO_HIT;
+	else if (!strncmp(a, "--secondary=", 12)) {                        // main.c:213-222 (yes_or_no)
+		if (!strcmp(a + 12, "yes") || !strcmp(a + 12, "y")) mo.flag &= ~(int64_t)AL_F_NO_PRINT_2ND;
+		else if (!strcmp(a + 12, "no") || !strcmp(a + 12, "n")) mo.flag |= AL_F_NO_PRINT_2ND;
+		else fprintf(stderr, "[WARNING]\033[1;31m option '--secondary' only accepts 'yes' or 'no'.\033[0m\n");
+	}
 	else if (!strcmp(a, "--cs") || !strncmp(a, "--cs=", 5)) {
 		const char *v = a[4] == '=' ? a + 5 : nullptr;
-		mo.flag |= AL_F_OUT_CS | AL_F_CIGAR;
+		mo.flag |= AL_F_OUT_CS | AL_F_CIGAR; sel.aln = true;
 		if (!v || !strcmp(v, "short")) mo.flag &= ~(int64_t)AL_F_OUT_CS_LONG;
 		else if (!strcmp(v, "long")) mo.flag |= AL_F_OUT_CS_LONG;
 		else if (!strcmp(v, "none")) mo.flag &= ~(int64_t)AL_F_OUT_CS;
 		else fprintf(stderr, "[WARNING]\033[1;31m --cs only takes 'short' or 'long'. Invalid values are assumed to be 'short'.\033[0m\n");
 	} else return 0;
 	return 1;
+}
+// after the command line is read: --paf replaces SAM, and the alignment stays on only where -c / --cs asked for it
+static void apply_out_sel(al_mapopt_t &mo, const OutSel &sel)
+{
+	if (!sel.paf) return;
+	mo.flag = (mo.flag & ~(int64_t)(AL_F_OUT_SAM | AL_F_CIGAR)) | AL_F_OUT_PAF;
+	if (sel.aln) mo.flag |= AL_F_CIGAR;
 }
 
 static int usage()
@@ -56,7 +75,10 @@ static int usage()
 	                "       airlift-align aln [-n X] [-t N] ref.fa reads.fa > x.sai ; airlift-align samse ref.fa x.sai reads.fa\n"
 	                "       airlift-align -ax sr [-t N] [-R RG] ref.fa reads_1.fq [reads_2.fq]\n"
 	                "output options (every mode that writes alignments): --MD (MD:Z tag), --cs[=short|long|none] (cs:Z tag; --MD wins),\n"
-	                "       --eqx (=/X CIGAR operations instead of M), -Y (soft clips and full SEQ/QUAL on supplementary records)\n");
+	                "       --eqx (=/X CIGAR operations instead of M), -Y (soft clips and full SEQ/QUAL on supplementary records),\n"
+	                "       --secondary=yes|no (secondary alignments; the sr preset leaves them out)\n"
+	                "PAF:   --paf (PAF instead of SAM: chaining and MAPQ only, no base-level alignment, unless -c or --cs is given), -c (cg:Z CIGAR),\n"
+	                "       --paf-no-hit (a line for reads without hits); not with mem / samse / aln / tokens, --bam, --sorted-bam, --count-candidates\n");
 	return 1;
 }
 
@@ -68,6 +90,7 @@ int main(int argc, char **argv)
 	enum { MODE_MEM, MODE_ALN, MODE_SAMSE, MODE_MM2, MODE_TOKENS } mode = MODE_MM2; int tok_size = 0, tok_skip = 1;
 	bool prefilter = false; int pf[4] = {3, 3, 5, 3};          // adjacency e, GreedySnake e, k-mer size, rounds
 	const char *dump_fn = nullptr;
+	OutSel sel;
 	int i = 1; bool k_given = false; int rank = -1, world = 0; const char *rendezvous = nullptr, *out_path = nullptr;
 	if (argc < 2) return usage();
 	al_set_opt(0, &io, &mo);
@@ -99,9 +122,10 @@ int main(int argc, char **argv)
 			else if (!strcmp(argv[j], "-R") && j + 1 < argc) rg = argv[++j];
 			else if (!strcmp(argv[j], "-o") && j + 1 < argc) out_p = argv[++j];
 			else if (!strcmp(argv[j], "--singletons") && j + 1 < argc) out_s = argv[++j];
-			else if (parse_out_opt(argv[j], mo)) {}
+			else if (parse_out_opt(argv[j], mo, sel)) {}
 			else p.push_back(argv[j]);
 		}
+		apply_out_sel(mo, sel);
 		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
 		if (!getenv("AL_PG_PLAIN")) al_set_program_line(AL_MM_VERSION, argc, argv);
 		if (!k_given) setenv("AL_AUTO_BATCH", "1", 0);
@@ -161,7 +185,7 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--score-N") && i + 1 < argc) mo.sc_ambi = atoi(argv[++i]);
 		else if (!strcmp(a, "--seed") && i + 1 < argc) mo.seed = atoi(argv[++i]);
 		else if (!strcmp(a, "--sam-hit-only")) mo.flag |= AL_F_SAM_HIT_ONLY;
-		else if (parse_out_opt(a, mo)) {}
+		else if (parse_out_opt(a, mo, sel)) {}
 		else if (!strcmp(a, "--count-candidates")) count_only = true;
 		else if (!strcmp(a, "--prefilter") && i + 1 < argc) {   // N4: --prefilter ADJ_E[,SNAKE_E[,SNAKE_K[,SNAKE_ITER]]] with --count-candidates
 			prefilter = true; char *e; const char *v = argv[++i];
@@ -196,6 +220,12 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--version")) { puts(al_version()); return 0; }
 		else { fprintf(stderr, "[WARNING] airlift-align: option '%s' ignored\n", a); }
 	}
+	if (sel.paf && (mode != MODE_MM2 || bam_mode || count_only)) {     // (decided before any device is opened)
+		fprintf(stderr, "[ERROR] --paf writes PAF text from the -x sr mapping of reads: it cannot be combined with %s\n",
+		        mode == MODE_MEM ? "mem" : mode == MODE_ALN ? "aln" : mode == MODE_SAMSE ? "samse" : mode == MODE_TOKENS ? "tokens" : bam_mode == 2 ? "--sorted-bam" : bam_mode ? "--bam" : "--count-candidates");
+		return 1;
+	}
+	apply_out_sel(mo, sel);
 	// one process per GPU?  (--world, or --rank / --ranked with the launcher's WORLD_SIZE.)  Anything else -- also WORLD_SIZE = 1, or WORLD_SIZE set
 	// without --rank / --ranked -- is a single process and writes -o FILE itself (main.c:183-190).
 	if (world <= 0 && rank >= 0 && getenv("WORLD_SIZE")) world = atoi(getenv("WORLD_SIZE"));

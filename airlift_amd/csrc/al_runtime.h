@@ -144,7 +144,9 @@ int al_run_tag_stage(al_ctx_t *c, const AlReg *out, const uint64_t *out_off, uin
 // --eqx (al_kernels_tags.hip): the records' M operations rewritten as =/X runs into a fresh arena E (E.bytes = its words), records updated in place
 int al_run_eqx_stage(al_ctx_t *c, AlReg *out, const uint64_t *out_off, uint64_t n_out, const uint32_t *arena, AlTagBufs &E);
 int al_run_tags(al_ctx_t *c);             // al_kernels_align.hip: the =/X pass and the tag stage on the last run's records, when the options ask for them
-static inline int al_tag_kind(int64_t flag) { return (flag & AL_F_OUT_MD) ? 1 : (flag & AL_F_OUT_CS) ? 2 : 0; }   // 0 none, 1 MD, 2 cs (MD wins, format.c:533)
+// a map-only run (no base-level alignment): PAF output without AL_F_CIGAR; only under AL_F_OUT_PAF is AL_F_CIGAR looked at (airlift.h)
+static inline bool al_map_only(int64_t flag) { return (flag & AL_F_OUT_PAF) && !(flag & AL_F_CIGAR); }
+static inline int al_tag_kind(int64_t flag) { return al_map_only(flag) ? 0 : (flag & AL_F_OUT_MD) ? 1 : (flag & AL_F_OUT_CS) ? 2 : 0; }   // 0 none, 1 MD, 2 cs (MD wins, format.c:533)
 int al_fetch_align(al_ctx_t *c, int *n_regs, al_reg1_t **regs, int *rep_len);
 void al_align_grow_arena(al_ctx_t *c);
 
@@ -188,6 +190,8 @@ int  al_fetch_raw(al_ctx_t *c, AlRawResult &R);
 int  al_write_sam_ex(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
                      int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss, const char *rg_id, int rep_len,
                      int64_t opt_flag, const char *tag, int tag_len);
+// al_write_paf with the tag value given by length (the device's tag arena is not NUL-terminated)
+int  al_write_paf_ex(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const al_reg1_t *r, int64_t opt_flag, int rep_len, const char *tag, int tag_len);
 void al_reg_from_raw(const AlRawResult &R, int read, int k, al_reg1_t &q);
 
 // host worker pool helper: fn(lo, hi, thread) over [0, n) split into contiguous ranges

@@ -368,12 +368,12 @@ static void al_dev_free_raw(void *p)
 
 static const char *g_stage_names[ST_N] = { "sketch", "seed_lookup", "scan", "size_order", "anchor_sort_small", "anchor_sort", "anchor_sort_blk", "anchor_sort_big", "anchor_heap",
                                            "chain_lds32", "chain_lds48", "chain_lds64", "chain_lds128", "chain_tile", "chain_deferred", "chain_fallback", "chain_ties", "rechain",
-                                           "regs", "ext_prep", "ext_sort", "ext_dp_lane", "ext_dp_g4", "ext_dp_g8", "ext_dp_g12", "ext_dp_g16", "ext_dp_g22", "ext_finish", "compact" };
+                                           "regs", "ext_prep", "ext_sort", "ext_dp_lane", "ext_dp_g4", "ext_dp_g8", "ext_dp_g12", "ext_dp_g16", "ext_dp_g22", "ext_finish", "map_only", "compact" };
 // kernel behind each interval (what rocprofv3 --kernel-trace lists); "" = several launches
 // the kernel of an interval that is exactly one launch of one kernel ("" otherwise: several kernels or several launches)
 static const char *g_stage_kernels[ST_N] = { "k_sketch", "k_seed", "", "", "k_anchor_sort_small", "", "", "", "",
                                              "", "", "", "", "", "", "", "",  "",
-                                             "", "k_ext_prep", "", "", "", "k_ext_dp<8, 256, 128, true>", "k_ext_dp<12, 256, 192, true>", "k_ext_dp<16, 256, 256, true>", "k_ext_dp<22, 256, 352, true>", "k_ext_finish", "k_compact" };   // (the DP instances of reads up to 256 bases with the default scores: two cells per lane; bench.py resolves the name against the committed profile)
+                                             "", "k_ext_prep", "", "", "", "k_ext_dp<8, 256, 128, true>", "k_ext_dp<12, 256, 192, true>", "k_ext_dp<16, 256, 256, true>", "k_ext_dp<22, 256, 352, true>", "k_ext_finish", "", "k_compact" };   // (the DP instances of reads up to 256 bases with the default scores: two cells per lane; bench.py resolves the name against the committed profile)
 extern "C" const char *al_stage_kernel(int i) { return i >= 0 && i < ST_N ? g_stage_kernels[i] : ""; }
 extern "C" const char *al_stage_name(int i) { return i >= 0 && i < ST_N ? g_stage_names[i] : ""; }
 
@@ -1385,7 +1385,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 4, 0, 8 * sizeof(unsigned long long), c->stream));     // [4..11]: stage statistics, error words, arena cursor
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 14, 0, sizeof(unsigned long long), c->stream));
 	}
-	if ((al_tag_kind(c->opt.flag) || (c->opt.flag & AL_F_EQX)) && al_run_tags(c)) return failed();
+	if (!al_map_only(c->opt.flag) && (al_tag_kind(c->opt.flag) || (c->opt.flag & AL_F_EQX)) && al_run_tags(c)) return failed();
 	for (int i = 0; i < ST_N; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) != hipSuccess) ms = 0; c->ms_stage[i] = ms; }
 	float tot = 0; (void)hipEventElapsedTime(&tot, c->ev[0], c->ev[ST_N]); c->ms_total = tot;
 	{ float a = 0, b = 0; if (hipEventElapsedTime(&a, c->ev_side[0], c->ev_side[1]) != hipSuccess) a = 0; if (c->n_rechain == 0 || hipEventElapsedTime(&b, c->ev_side[2], c->ev_side[3]) != hipSuccess) b = 0; c->ms_side = a + b; (void)hipGetLastError(); }

@@ -24,6 +24,7 @@
 #include "al_io.h"
 #include "al_stream.h"
 #include "al_dev_sam.h"
+#include "al_dev_paf.h"
 
 #define NL_TILE 4096
 
@@ -309,6 +310,46 @@ k_sam_bulk(const AlBulk *__restrict__ bulk, uint64_t n_desc, const char *__restr
 	}
 }
 
+// ---- PAF text (al_dev_paf.h): the same two passes over the same frame -- a lane per read counts its lines' bytes, the scan gives every read
+// its offset, the second pass writes.  A line has no SEQ / QUAL, so there are no bulk descriptors: a tag value is copied by its record's lane.
+__global__ void __launch_bounds__(256)
+k_paf_len(SamIn I, uint32_t *__restrict__ sam_len, uint32_t *__restrict__ sam_nrec)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i > I.n_reads) return;
+	if (i == I.n_reads) { sam_len[i] = 0; sam_nrec[i] = 0; return; }
+	const AlSamRead me = d_sam_read(I, i);
+	AlSamCountSink o; o.C = &I.C; o.text = (I.two_files && (I.rd_info[i] & AL_RI_SEG1)) ? I.t1 : I.t0; o.tag_off = I.tag_off;
+	const int n = al_paf_read_records(o, I.C, me, I.frag_rep[I.rd_frag[i]]);
+	sam_len[i] = (uint32_t)o.n; sam_nrec[i] = (uint32_t)n;
+}
+struct PafWriteSink {
+	const AlSamCfg *C; const char *text; char *p; const uint64_t *tag_off; const char *tag_txt;
+	__device__ __forceinline__ void ch(char c) { *p++ = c; }
+	__device__ __forceinline__ void lit(const char *s) { while (*s) *p++ = *s++; }
+	__device__ __forceinline__ void num(long long v)
+	{
+		unsigned long long x = v < 0 ? 0ULL - (unsigned long long)v : (unsigned long long)v;
+		const int l = al_num_len(v); char *e = p + l;
+		do { *--e = (char)('0' + (int)(x % 10)); x /= 10; } while (x);
+		if (v < 0) *--e = '-';
+		p += l;
+	}
+	__device__ __forceinline__ void txt(uint32_t off, uint32_t len) { for (uint32_t i = 0; i < len; ++i) p[i] = text[off + i]; p += len; }
+	__device__ __forceinline__ void cname(int rid) { const uint32_t a = C->name_off[rid], b = C->name_off[rid + 1]; for (uint32_t i = a; i < b; ++i) *p++ = C->names[i]; }
+	__device__ __forceinline__ void tag(uint64_t k) { const uint64_t a = tag_off[k], len = tag_off[k + 1] - a; for (uint64_t j = 0; j < len; ++j) p[j] = tag_txt[a + j]; p += len; }
+};
+__global__ void __launch_bounds__(256)
+k_paf_write(SamIn I, const uint64_t *__restrict__ sam_off, char *__restrict__ sam)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= I.n_reads) return;
+	if (sam_off[i + 1] == sam_off[i]) return;                          // (a read without lines)
+	const AlSamRead me = d_sam_read(I, i);
+	PafWriteSink o; o.C = &I.C; o.text = (I.two_files && (I.rd_info[i] & AL_RI_SEG1)) ? I.t1 : I.t0; o.p = sam + sam_off[i]; o.tag_off = I.tag_off; o.tag_txt = I.tag_txt;
+	al_paf_read_records(o, I.C, me, I.frag_rep[I.rd_frag[i]]);
+}
+
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 struct CastU64s { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
 static int scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
@@ -510,16 +551,23 @@ int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id)
 	I.C.names = S.names.p; I.C.name_off = S.name_off.p; I.C.rg_id = S.rg.p; I.C.rg_len = S.rg_len;
 	I.C.no_print_2nd = (c->opt.flag & AL_F_NO_PRINT_2ND) ? 1 : 0; I.C.hit_only = (c->opt.flag & AL_F_SAM_HIT_ONLY) ? 1 : 0; I.C.pe_ori = c->opt.pe_ori;
 	I.C.softclip = (c->opt.flag & AL_F_SOFTCLIP) ? 1 : 0; I.C.tag_kind = R.tag_kind; I.C.tag_reg0 = R.out; I.tag_off = R.tag_kind ? R.tag_off : nullptr; I.tag_txt = R.tag_kind ? R.tag : nullptr;
+	const bool paf = (c->opt.flag & AL_F_OUT_PAF) != 0;
+	I.C.ctg_len = c->di.seq_len; I.C.out_cg = (c->opt.flag & AL_F_OUT_CG) ? 1 : 0; I.C.paf_no_hit = (c->opt.flag & AL_F_PAF_NO_HIT) ? 1 : 0;
 	const uint64_t n_slot = R.tag_kind ? 3 : 2;                      // bulk descriptors per record
 	if (S.sam_len.ensure((size_t)nr + 2) || S.sam_nrec.ensure((size_t)nr + 2) || S.sam_off.ensure((size_t)nr + 2) || S.rec_off.ensure((size_t)nr + 2)) return -1;
-	hipLaunchKernelGGL(k_sam_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
+	if (paf) hipLaunchKernelGGL(k_paf_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
+	else hipLaunchKernelGGL(k_sam_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
 	if (scan_excl_u64(S, S.sam_len.p, S.sam_off.p, (size_t)nr + 1, s) || scan_excl_u64(S, S.sam_nrec.p, S.rec_off.p, (size_t)nr + 1, s)) return -1;
 	uint64_t tot[2] = {0, 0};
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[0], S.sam_off.p + nr, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[1], S.rec_off.p + nr, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
-	if (S.sam.ensure(tot[0] + 64) || S.bulk.ensure(n_slot * tot[1] + 2)) return -1;
-	if (tot[1]) {
+	if (S.sam.ensure(tot[0] + 64) || (!paf && S.bulk.ensure(n_slot * tot[1] + 2))) return -1;
+	if (tot[1] && paf) {
+		hipLaunchKernelGGL(k_paf_write, dim3((nr + 255) / 256), dim3(256), 0, s, I, S.sam_off.p, S.sam.p);
+		AL_HIP_CHECK(hipEventRecord(S.ev, s));
+		AL_HIP_CHECK(hipStreamWaitEvent(S.io, S.ev, 0));
+	} else if (tot[1]) {
 		AL_HIP_CHECK(hipMemsetAsync(S.bulk.p, 0, n_slot * tot[1] * sizeof(AlBulk), s));
 		hipLaunchKernelGGL(k_sam_write, dim3((nr + 255) / 256), dim3(256), 0, s, I, S.sam_off.p, S.rec_off.p, S.sam.p, S.bulk.p);
 		hipLaunchKernelGGL(k_sam_bulk, dim3((unsigned)((n_slot * tot[1] + 3) / 4)), dim3(256), 0, s, S.bulk.p, n_slot * tot[1], I.t0, I.t1, S.tabs.p, S.sam.p, R.tag_kind ? R.tag : (const char *)nullptr);

@@ -38,6 +38,12 @@ extern "C" {
 #define AL_F_SOFTCLIP      0x80000
 #define AL_F_OUT_MD        0x1000000
 #define AL_F_EQX           0x4000000
+/* PAF output (main.c:158, 211; format.c:304-330).  The fork writes PAF whenever MM_F_OUT_SAM is clear; here callers of al_set_opt never set
+ * AL_F_OUT_SAM and get SAM, so PAF has a flag of its own above the fork's 32 bits.  Only under AL_F_OUT_PAF is AL_F_CIGAR looked at: clear = no
+ * base-level alignment (the fork's `-x sr` without -a / -c, map.c:262, 404): chaining, per-mate hits and MAPQ only; records carry n_cigar == 0. */
+#define AL_F_OUT_CG        0x020            /* -c: cg:Z: CIGAR in PAF */
+#define AL_F_PAF_NO_HIT    0x8000000        /* --paf-no-hit: a `name len 0 0 * * 0 0 0 0 0 0` line for a read without hits */
+#define AL_F_OUT_PAF       0x100000000LL    /* --paf (no analogue in the fork: its default) */
 
 /* replaces mm_idxopt_t (minimap.h:101-105) */
 typedef struct {
@@ -229,6 +235,8 @@ int  al_dbg_fastq_selftest(const char *fn, int n_threads);
  * n_frag random fragments formatted by it and by al_write_sam, `de:f:%.4f` checked against printf; returns the number of
  * differences (0 = identical); needs no GPU. */
 int  al_dbg_sam_selftest(uint64_t seed, int n_frag);
+/* The same for the PAF formatter (k_paf_len / k_paf_write; mm_write_paf3, format.c:304-330) against al_write_paf. */
+int  al_dbg_paf_selftest(uint64_t seed, int n_frag);
 
 /* ---- device-resident batch API (bench / multi-GPU harness; inputs already in HBM when timing starts) ---- */
 /* Pack + upload a batch; returns 0.  The batch stays resident until the next upload. */
@@ -325,6 +333,12 @@ int  al_write_sam_hdr(FILE *out, const al_idx_t *mi, const char *rg, char *rg_id
 int  al_write_sam(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const char *seq, const char *qual,
                   int seg_idx, int reg_idx, int n_seg, const int *n_regss, const al_reg1_t *const *regss,
                   const char *rg_id, int rep_len);
+
+/* mm_write_paf3 (format.c:304-330) for one hit r of the read `qname` (l_seq bases) as al_map_frag returned it; r == NULL: the line of a read
+ * without hits (--paf-no-hit).  opt_flag: AL_F_OUT_CG prints cg:Z:, AL_F_OUT_MD / AL_F_OUT_CS name the tag `tag` holds (the value al_gen_MD /
+ * al_gen_cs made, or NULL for none); both only on a record with a CIGAR.  rep_len < 0 leaves rl:i: out.  The line ends with '\n' (the fork's
+ * mm_err_puts adds it).  Returns the length, -1 if cap is too small. */
+int  al_write_paf(char *buf, size_t cap, const al_idx_t *mi, const char *qname, int l_seq, const al_reg1_t *r, int64_t opt_flag, int rep_len, const char *tag);
 
 /* mm_gen_cs / mm_gen_MD (minimap.h:363-364, format.c:137-214): the cs:Z / MD:Z value (no tag prefix) of one record r as al_map_frag
  * returned it, for the read `seq` in sequencing orientation.  no_iden != 0: short cs (":len"), else long ("=BASES").  *buf is malloc()ed /
