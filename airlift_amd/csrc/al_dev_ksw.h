@@ -33,7 +33,7 @@ __device__ __forceinline__ void d_ksw_reg(LT &L, const int gl, GroupWs &ws, int 
 {
 	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
 	if (q2 + e2 < q + e) { int t = q; q = q2; q2 = t; t = e; e = e2; e2 = t; }
-	const int qe = q + e;
+	const int qe = P.q + P.e;   // (ksw2_extd2_sse.c:60 takes q + e before the swap of the gap models and H[0][0] keeps that value)
 	const int8_t qe_ = (int8_t)(q + e), qe2_ = (int8_t)(q2 + e2);
 	const int8_t sc_mch = (int8_t)P.a, sc_mis = (int8_t)(-P.b), sc_amb = (int8_t)(P.sc_ambi > 0 ? -P.sc_ambi : P.sc_ambi);
 	const int8_t sc_N = sc_amb == 0 ? (int8_t)(-e2) : sc_amb;

@@ -146,7 +146,7 @@ __device__ __forceinline__ void d_ksw_lds(GroupLds<TMAX, QMAX> &L, const int gl,
 	d_ez_reset(ez);
 	if (qlen <= 0 || tlen <= 0) return;
 	if (q2 + e2 < q + e) { int t = q; q = q2; q2 = t; t = e; e = e2; e2 = t; }
-	const int qe = q + e;
+	const int qe = P.q + P.e;   // (ksw2_extd2_sse.c:60 takes q + e before the swap of the gap models and H[0][0] keeps that value)
 	const int8_t qe_ = (int8_t)(q + e), qe2_ = (int8_t)(q2 + e2);
 	const int8_t sc_mch = (int8_t)P.a, sc_mis = (int8_t)(-P.b), sc_amb = (int8_t)(P.sc_ambi > 0 ? -P.sc_ambi : P.sc_ambi);
 	const int8_t sc_N = sc_amb == 0 ? (int8_t)(-e2) : sc_amb;
@@ -1790,6 +1790,16 @@ k_align_long(const uint32_t *__restrict__ rd_seq, const uint64_t *__restrict__ r
 	d_align_frags<AL_LONG_TMAX, AL_LONG_QMAX>(state[(size_t)blockIdx.x * AL_GPB + g], g, gl, rd_seq, rd_off, rd_len, frag_first, frag_rep, W, G, lt, gws, gws_stride, p_bytes, cig_words, n_frag, P, frag_list, n_list);
 }
 
+// Where the arithmetic of the two-cells-per-lane form (al_dev_ksw2.h) holds: the permute's constant 0xff is the score of an N, scores within +-16
+// (int16 H of the 352 x 512 tile), and gap models in the order the reference does not swap (with q + e > q2 + e2 its H[0][0] keeps the q + e of before
+// the swap, ksw2_extd2_sse.c:60,70: the one-cell forms follow that, d_ksw_pk and its early exit do not).  Asked by the align stage's class table and
+// by the al_dbg_ksw tap: everything else takes the one-cell form.
+__host__ __device__ inline bool d_pk_ok(const AlParams &P)
+{
+	const int sc_amb = P.sc_ambi > 0 ? -P.sc_ambi : P.sc_ambi, sc_N = sc_amb == 0 ? -(P.e2 < P.e ? P.e2 : P.e) : sc_amb;
+	return sc_N == -1 && P.a > 0 && P.a <= 16 && P.b >= 0 && P.b <= 16 && P.q + P.e <= P.q2 + P.e2 && P.q2 + P.e2 <= 64 && P.q >= 0 && P.e >= 0 && P.q2 >= 0 && P.e2 >= 0;
+}
+
 // Tap for the parity tests: the extension DP alone on caller-supplied (target, query) pairs, one 16-lane group per pair -- what the
 // reference's --print-aln-seq tap shows per ksw call (align.c:313-339): sequences as passed to ksw_extd2_sse, flag; out: ez->score, CIGAR.
 struct DbgKswJob { uint32_t toff, qoff; int32_t tlen, qlen, flag, pad; };
@@ -1824,7 +1834,7 @@ k_dbg_ksw(const uint8_t *__restrict__ seqs, const DbgKswJob *__restrict__ jobs, 
 		GSYNC();
 		EzD ez;
 		const int eb = (jb.flag & EZ_EXTZ_ONLY) ? P.end_bonus : -1;                      // align.c: extensions pass opt->end_bonus, the core re-alignment -1
-		if (((P.dbg >> 20) & 1) && jb.tlen <= 352) {
+		if (((P.dbg >> 20) & 1) && jb.tlen <= 352 && d_pk_ok(P)) {
 			DbgPkLds &K = pk[g];
 			const int nb = (jb.tlen + 15) / 16, np = nb <= 4 ? 2 : nb <= 8 ? 4 : nb <= 12 ? 6 : nb <= 16 ? 8 : 11, pad = 32 * np;
 			for (int i = gl; i < jb.tlen; i += GW) K.tbuf[i] = L.tbuf[i];
@@ -1907,6 +1917,22 @@ __device__ __forceinline__ int d_job_class(int qlen, int tlen, int lane_ok)
 	if (lane_ok && qlen <= AL_LANE_QC && b <= 2) return b <= 1 ? 0 : 1;   // (class 2, targets <= 64, measured slower than the group DP: LDS-bound)
 	return b <= 1 ? 3 : b <= 2 ? 4 : b <= 4 ? 5 : b <= 8 ? 6 : b <= 22 ? 7 : b <= 32 ? 8 : 9;
 }
+// Sort key of a job of class cls: class | 16-cell blocks of the target | direction | size -- inside a class the jobs are ordered by block count first, so that
+// the 9 ... 22-block class can be launched as three kernels (12, 16, 22 register blocks: a row costs every instantiated block a skip test and two selects),
+// (round 5) then by direction (kind 0, the left extensions, have right-aligned gaps, align.c:694-704): a wavefront of the DP kernels holds four jobs of one direction
+__device__ __forceinline__ uint32_t d_job_key(int cls, int qlen, int tlen, int kind)
+{
+	const uint32_t b = (uint32_t)min(63, (tlen + 15) / 16);
+	return cls < AL_NCLS ? ((uint32_t)cls << 20 | b << 14 | (uint32_t)kind << 13 | (uint32_t)min(0x1fff, qlen + tlen)) : 0xffffffffu;
+}
+// ... and its share of the counts the launches are sized from (a block's shared counters: [0..AL_NCLS] jobs per class, jobs of class 7 with <= 12 / 13 ... 16 blocks, target bases per class)
+__device__ __forceinline__ void d_job_tally(int cls, int tlen, unsigned *s_hist, unsigned *s_sub, unsigned *s_tl)
+{
+	const int b = min(63, (tlen + 15) / 16);
+	atomicAdd(&s_hist[cls], 1u);
+	if (cls == 7 && b <= 16) atomicAdd(&s_sub[b <= 12 ? 0 : 1], 1u);
+	if (cls < AL_NCLS) atomicAdd(&s_tl[cls], (unsigned)tlen);
+}
 
 // One fragment's share of k_ext_prep.  WAVE = false: the calling lane walks the fragment's hits one after the other.  WAVE = true: the 64 lanes
 // of the calling wavefront take a hit each (fragments with many hits: a lane per fragment ran 6 ms on them while the rest of the batch was done
@@ -1928,7 +1954,8 @@ __device__ __forceinline__ void d_ext_prep_frag(const int f, const int lane, con
 	AlReg *const mreg0 = fw.mreg[0], *const mreg1 = fw.mreg[1];
 	AlAnchor *const sa0 = fw.seg_a[0], *const sa1 = n_segs == 2 ? fw.seg_a[0] + W.seg_na[r0] : nullptr;
 	const int ge1 = P.q + P.e, ge2 = P.q2 + P.e2;
-	const bool diag_ok = P.a > 0 && P.b > 0 && P.a + P.b < (ge1 < ge2 ? ge1 : ge2) && (P.zdrop < 0 || P.zdrop >= P.b + (ge1 > ge2 ? ge1 : ge2));
+	// (ge1 <= ge2: with the gap models swapped the reference's scores lie ge1 - ge2 lower, ksw2_extd2_sse.c:60 -- those flanks take the DP kernels)
+	const bool diag_ok = P.a > 0 && P.b > 0 && ge1 <= ge2 && P.a + P.b < (ge1 < ge2 ? ge1 : ge2) && (P.zdrop < 0 || P.zdrop >= P.b + (ge1 > ge2 ? ge1 : ge2));
 	// one hit: 0 = jobs in x / jl / jr, 1 = needs the monolithic kernel, 2 = the same because its window exceeds the tiles (counted)
 	auto hit = [&](const uint32_t s, const int i, const AlReg *regs, const AlAnchor *a, const int qlen, const uint32_t *seq, const uint32_t jb, RegExt &x, ExtJob &jl, ExtJob &jr) -> int {
 		const AlReg *r = &regs[i];
@@ -2049,16 +2076,8 @@ __device__ __forceinline__ void d_ext_prep_frag(const int f, const int lane, con
 		E.rext[B2 + (uint64_t)s * fw.cap + i] = x;
 		E.jobs[jb] = jl; E.jobs[jb + 1] = jr;
 		const int c0 = (jl.qlen && !jl.pad0) ? d_job_class(jl.qlen, jl.tlen, lane_ok) : AL_NCLS, c1 = (jr.qlen && !jr.pad0) ? d_job_class(jr.qlen, jr.tlen, lane_ok) : AL_NCLS;
-		// key: class | 16-cell blocks of the target | size -- inside a class the jobs are ordered by block count first, so that the 9 ... 22-block class
-		// can be launched as three kernels (12, 16, 22 register blocks: a row costs every instantiated block a skip test and two selects)
-		const uint32_t b0 = (uint32_t)std::min(63, (jl.tlen + 15) / 16), b1 = (uint32_t)std::min(63, (jr.tlen + 15) / 16);
-		// (round 5) ... then by direction (left extensions have right-aligned gaps, align.c:694-704): a wavefront of the DP kernels holds four jobs of one direction
-		E.job_key[jb] = c0 < AL_NCLS ? ((uint32_t)c0 << 20 | b0 << 14 | 0u << 13 | (uint32_t)std::min(0x1fff, jl.qlen + jl.tlen)) : 0xffffffffu;
-		E.job_key[jb + 1] = c1 < AL_NCLS ? ((uint32_t)c1 << 20 | b1 << 14 | 1u << 13 | (uint32_t)std::min(0x1fff, jr.qlen + jr.tlen)) : 0xffffffffu;
-		atomicAdd(&s_hist[c0], 1u); atomicAdd(&s_hist[c1], 1u);
-		if (c0 == 7 && b0 <= 16) atomicAdd(&s_sub[b0 <= 12 ? 0 : 1], 1u);
-		if (c1 == 7 && b1 <= 16) atomicAdd(&s_sub[b1 <= 12 ? 0 : 1], 1u);
-		if (c0 < AL_NCLS) atomicAdd(&s_tl[c0], (unsigned)jl.tlen); if (c1 < AL_NCLS) atomicAdd(&s_tl[c1], (unsigned)jr.tlen);
+		E.job_key[jb] = d_job_key(c0, jl.qlen, jl.tlen, 0); E.job_key[jb + 1] = d_job_key(c1, jr.qlen, jr.tlen, 1);
+		d_job_tally(c0, jl.tlen, s_hist, s_sub, s_tl); d_job_tally(c1, jr.tlen, s_hist, s_sub, s_tl);
 	};
 	auto do_seg = [&](const uint32_t s, const AlReg *regs, const AlAnchor *a) {
 		const int qlen = (int)rd_len[r0 + s], n = (int)W.reg_cnt[r0 + s];
@@ -2293,7 +2312,7 @@ k_ext_dp_lane(const uint32_t *__restrict__ rd_seq, const uint64_t *__restrict__ 
 #define LQ(i) sQ[(i) * 64 + lane]
 	int q = P.q, e = P.e, q2 = P.q2, e2 = P.e2;
 	if (q2 + e2 < q + e) { int t = q; q = q2; q2 = t; t = e; e = e2; e2 = t; }
-	const int qe = q + e;
+	const int qe = P.q + P.e;   // (ksw2_extd2_sse.c:60 takes q + e before the swap of the gap models and H[0][0] keeps that value)
 	const int8_t qe_ = (int8_t)(q + e), qe2_ = (int8_t)(q2 + e2);
 	const int8_t sc_mch = (int8_t)P.a, sc_mis = (int8_t)(-P.b), sc_amb = (int8_t)(P.sc_ambi > 0 ? -P.sc_ambi : P.sc_ambi);
 	const int8_t sc_N = sc_amb == 0 ? (int8_t)(-e2) : sc_amb;
@@ -2824,6 +2843,152 @@ void al_align_state_free(al_ctx_t *c)
 	delete s; g_states.erase(it);
 }
 
+// The job list by key (d_job_key): A->job_idx (0 .. nj - 1) -> A->job_idx2
+static int ext_dp_sort_jobs(al_ctx_t *c, AlignState *A, uint32_t nj, hipStream_t s)
+{
+	(void)c;
+	size_t bytes = 0;
+	AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
+	if (A->sort_tmp.ensure(bytes + 16)) return -1;
+	AL_HIP_CHECK(rocprim::radix_sort_pairs(A->sort_tmp.p, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
+	return 0;
+}
+
+// The extension DP's launches: one per job class over its slice of the sorted job list A->job_idx2 (the order of k_ext_prep's keys, d_job_key), with
+// the classes' workspace ranges, the 12 / 16 / 22-block split of class 7, the instance by query length and the choice between the one-cell and the
+// two-cells-per-lane form.  hist: jobs per class, sub7: jobs of class 7 with <= 12 / 13 ... 16 blocks (both as k_ext_prep counted them).  Called by
+// the align stage and by the al_dbg_ext_dp tap, so that the tests' jobs take the launches a batch's jobs take.
+struct DpGeom { int Lmax, tmax; size_t stride, p_bytes, cig_words; };   // longest read of the batch, LDS tile of the stage, workspace of a group of the LDS-row class
+static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &G, const ExtShared &E, hipStream_t s, const unsigned long long *hist, const unsigned long long *sub7, const DpGeom &geom)
+{
+	const int Lmax = geom.Lmax, tmax = geom.tmax; const size_t stride = geom.stride, p_bytes = geom.p_bytes, cig_words = geom.cig_words;
+	// one launch per job class over its slice of the sorted job list
+	static const int NBs[6] = {1, 2, 4, 8, 22, 32};
+	uint32_t first = 0;
+	// (round 5) A small batch's classes do not fill the chip (C2: 32 000 jobs of 9 ... 22 blocks over three kernels, 8 blocks per CU) and every class ends in the
+	// tail of its longest job (the 22-block kernel: 0.85 ms whatever the batch): below AL_DP_CONC jobs (default 700 000; 0: never) the class kernels run side by
+	// side on four streams, each on a workspace range of its own; the per-class intervals of the stage table then hold launch order only.
+	static const long long conc_thr = getenv("AL_DP_CONC") ? atoll(getenv("AL_DP_CONC")) : 700000;
+	long long n_real = 0; for (int cls = 0; cls < AL_NCLS; ++cls) n_real += (long long)hist[cls];                   // (nj counts two slots per hit, most of them empty)
+	const bool dp_conc = n_real < conc_thr;
+	size_t ws_off[AL_NCLS + 1]; ws_off[0] = 0;
+	{   // one workspace range for every class of this batch: sized for the largest now, not grown class by class (a regrow frees -- and waits for -- what the running class uses)
+		size_t need = 0;
+		for (int cls = 0; cls < AL_NCLS; ++cls) {
+			const uint32_t cnt = (uint32_t)hist[cls];
+			size_t b = 0;
+			if (cnt == 0) b = 0;
+			else if (cls < 3) { const int TC = 16 << cls; int nw = (int)((cnt + 63) / 64); if (nw > 1024) nw = 1024; b = (size_t)nw * ((size_t)(AL_LANE_QC + TC) * (size_t)(TC + 16) * 64); }
+			else if (cls < 9) {
+				const int NB = NBs[cls - 3];
+				const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
+				const int cap = NB <= 4 ? (getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096) : NB <= 8 ? (getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096) : NB <= 22 ? (getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072) : 2048;
+				const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap;   // (side by side the ranges add up: slightly fewer blocks each keep the sum near what the largest range was)
+				int nbj = (int)((cnt + 3) / 4); if (nbj > cap_eff) nbj = cap_eff;
+				b = (size_t)nbj * 4 * st2;
+				if (cls == 7) { const unsigned long long c12 = std::min<unsigned long long>(sub7[0], cnt), c16 = std::min<unsigned long long>(sub7[1], cnt - c12), c22 = cnt - c12 - c16;
+				                if (c22 > 0 && c22 <= 8192) b += (size_t)std::min<unsigned long long>((c22 + 3) / 4, (unsigned long long)nbj) * 4 * st2; }   // (a thin 22-block kernel beside the other two of its class: its own range behind theirs)
+			} else { int nbj = (int)cnt; if (nbj > 2048) nbj = 2048; b = (size_t)nbj * stride; }
+			b = (b + 255) / 256 * 256;
+			ws_off[cls + 1] = dp_conc ? ws_off[cls] + b : 0;
+			if (dp_conc) need += b; else if (b > need) need = b;
+		}
+		if (need && A->gws.ensure(need + 64)) return -1;
+	}
+	hipStream_t dps[4] = {s, c->aux[0], c->aux[1], c->aux[2]}; int dpk = 0;
+	if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0)); }
+	hipStream_t const s_main = s;
+	bool g12_done = false, thin22_join = false; hipStream_t thin22_stream = nullptr;
+	// two cells per lane (al_dev_ksw2.h) where its arithmetic holds (d_pk_ok); AL_DP_PK=0: the one-cell form everywhere (tests, A/B)
+	static const int pk_env = getenv("AL_DP_PK") ? atoi(getenv("AL_DP_PK")) : 1;
+	const bool dp_pk = pk_env != 0 && d_pk_ok(c->P);
+	for (int cls = 0; cls < AL_NCLS; ++cls) {
+		const uint32_t cnt = (uint32_t)hist[cls];
+		if (cls == 3) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_LANE + 1], s));
+		if (cls == 6) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G4 + 1], s));
+		if (cls == 7) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G8 + 1], s));
+		if (cls == 8 && !g12_done) { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s)); AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s)); g12_done = true; }
+		if (cnt == 0) continue;
+		unsigned char *const gbase = A->gws.p + ws_off[cls];
+		hipStream_t s = dp_conc ? dps[dpk++ & 3] : s_main;                 // (shadows the stage's stream inside the class)
+		if (cls < 3) {                                                    // lane-per-job
+			const int TC = 16 << cls;
+			const size_t tbs = (size_t)(AL_LANE_QC + TC) * (size_t)(TC + 16) * 64;
+			int nw = (int)((cnt + 63) / 64); if (nw > 1024) nw = 1024;
+			if (cls == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<16, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
+			else if (cls == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<32, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
+			else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<64, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
+		} else if (cls < 9) {
+			const int NB = NBs[cls - 3];
+			const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
+			int nbj = (int)((cnt + 3) / 4); { static const int caps[3] = { getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096, getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096, getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072 };
+			  const int cap = NB <= 4 ? caps[0] : NB <= 8 ? caps[1] : NB <= 22 ? caps[2] : 2048; const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap; if (nbj > cap_eff) nbj = cap_eff; }
+#define LAUNCH_DP(NBV) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P)
+// (queries of up to 256 bases -- every short-read set -- get the instance with the smaller query arrays: 12 instead of 14 KB of LDS per block at 16 blocks, a third wavefront per SIMD)
+#define LAUNCH_DPK(NBV) do { if (Lmax <= 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 256, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); \
+	                         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); } while (0)
+			if (NB == 1) LAUNCH_DP(1); else if (NB == 2) LAUNCH_DP(2); else if (NB == 4) LAUNCH_DP(4); else if (NB == 8) { if (dp_pk) LAUNCH_DPK(8); else LAUNCH_DP(8); } else if (NB == 32) { static const bool pk32 = !(getenv("AL_DP_PK32") && atoi(getenv("AL_DP_PK32")) == 0); if (dp_pk && pk32) LAUNCH_DPK(32); else LAUNCH_DP(32); }
+			else {   // 9 ... 22 blocks: the sorted slice holds the jobs of <= 12 blocks first, then 13 ... 16, then the rest
+				static const bool split = !getenv("AL_DP_NO_SPLIT");
+				const uint32_t c12 = split ? (uint32_t)std::min<unsigned long long>(sub7[0], cnt) : 0u, c16 = split ? (uint32_t)std::min<unsigned long long>(sub7[1], cnt - c12) : 0u, c22 = cnt - c12 - c16;
+				const uint32_t first0 = first, cnt0 = cnt;
+#define LAUNCH_DPS(NBV, F, N) do { if ((N) > 0) { int nb2 = (int)(((N) + 3) / 4); if (nb2 > nbj) nb2 = nbj; \
+					if (dp_pk && Lmax <= 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 256, NBV * 16, true>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); \
+					else if (dp_pk) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16, true>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); \
+					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); gw_used += nb2; } } while (0)
+				// (the three kernels run one after the other on this stream: they may share the workspace range)
+				int gw_used = 0;
+				{
+					// few 22-block jobs (C4: a few hundred): the kernel is the tail of its longest job, 0.85 ms alone at the end of the stage -- it starts first, on a side stream, beside the other two.
+					// (Side by side with the other classes the three kernels of this one still run one after the other and share a range: a range each cost 6.8 GB per context.)
+					hipStream_t const s_cls = s;
+					const bool thin22 = c22 > 0 && c22 <= 8192u && split;
+					if (thin22) { hipStream_t const s22 = s_cls == c->aux[1] ? c->aux[2] : c->aux[1]; AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s_cls)); AL_HIP_CHECK(hipStreamWaitEvent(s22, c->ev_fj[0], 0)); s = s22; gw_used = nbj; LAUNCH_DPS(22, first0 + c12 + c16, c22); s = s_cls; gw_used = 0; thin22_join = true; thin22_stream = s22; }
+					LAUNCH_DPS(12, first0, c12); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); gw_used = 0; LAUNCH_DPS(16, first0 + c12, c16); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); gw_used = 0;
+					if (!thin22) LAUNCH_DPS(22, first0 + c12 + c16, c22);
+					if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); }
+				}
+				g12_done = true;
+				(void)cnt0;
+#undef LAUNCH_DPS
+			}
+#undef LAUNCH_DP
+#undef LAUNCH_DPK
+		} else {
+			int nbj = (int)cnt; if (nbj > 2048) nbj = 2048;
+			if (tmax <= 512) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<512, 256>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
+			else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<1024, 512>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
+		}
+		if (getenv("AL_TRACE")) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: DP class %d (%u jobs) -> %s\n", cls, cnt, hipGetErrorName(e)); }
+		first += cnt;
+	}
+	if (dp_conc) for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
+	if (thin22_join && !dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[1], thin22_stream)); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[1], 0)); }   // (side by side: the join above covers every aux stream)
+	return 0;
+}
+
+// Geometry of the extension stage for the resident batch: the longest window a flank can ask for (align.c:613-620), the traceback area and CIGAR
+// buffer of a 16-lane group, the LDS tile.  One statement of it for the align stage and the al_dbg_ext_dp tap.
+struct ExtGeom { DpGeom dp; int tbound, qmax; bool long_mode; };
+static ExtGeom ext_geometry(const al_ctx_t *c)
+{
+	ExtGeom g;
+	const int Lmax = c->max_rd_len;
+	const al_mapopt_t &o = c->opt;
+	int ext = Lmax; { int l = Lmax; ext = l + (l * o.a + o.end_bonus > o.q ? (l * o.a + o.end_bonus - o.q) / o.e : 0); }
+	const int tbound = std::max(2 * Lmax + 16, ext + 16);
+	const int bw = (int)(o.bw * 1.5 + 1.);
+	const int ncol = ((std::min(Lmax, bw + 1) + 15) / 16 + 1);
+	g.dp.Lmax = Lmax; g.tbound = tbound;
+	g.dp.p_bytes = ((size_t)(Lmax + tbound) * ncol * 16 + 63) / 64 * 64;
+	g.dp.cig_words = ((size_t)(Lmax + tbound) + 16 + 15) / 16 * 16;
+	g.dp.stride = g.dp.p_bytes + g.dp.cig_words * 8 + AL_PAIR_SC_CAP * 8;
+	g.dp.tmax = (Lmax <= 160 && tbound <= 336) ? 336 : (Lmax <= 256 && tbound <= 512) ? 512 : (Lmax <= 512 && tbound <= 1024) ? 1024 : 0;
+	g.qmax = g.dp.tmax == 336 ? 160 : g.dp.tmax == 512 ? 256 : 512;
+	g.long_mode = g.dp.tmax == 0;              // reads beyond the LDS tiles: the whole batch through k_align_long (state blocks in HBM)
+	return g;
+}
+
 int al_run_align_stage(al_ctx_t *c)
 {
 	hipStream_t s = c->stream;
@@ -3010,15 +3175,9 @@ int al_run_align_stage(al_ctx_t *c)
 		return 0;
 	}
 	// extension stage geometry
-	const int Lmax = c->max_rd_len;
-	const al_mapopt_t &o = c->opt;
-	int ext = Lmax; { int l = Lmax; ext = l + (l * o.a + o.end_bonus > o.q ? (l * o.a + o.end_bonus - o.q) / o.e : 0); }
-	const int tbound = std::max(2 * Lmax + 16, ext + 16);
-	const int bw = (int)(o.bw * 1.5 + 1.);
-	const int ncol = ((std::min(Lmax, bw + 1) + 15) / 16 + 1);
-	const size_t p_bytes = ((size_t)(Lmax + tbound) * ncol * 16 + 63) / 64 * 64;
-	const size_t cig_words = ((size_t)(Lmax + tbound) + 16 + 15) / 16 * 16;
-	const size_t stride = p_bytes + cig_words * 8 + AL_PAIR_SC_CAP * 8;
+	const ExtGeom eg = ext_geometry(c);
+	const int Lmax = eg.dp.Lmax, tbound = eg.tbound;
+	const size_t p_bytes = eg.dp.p_bytes, cig_words = eg.dp.cig_words, stride = eg.dp.stride;
 	int nb = (nf + AL_GPB - 1) / AL_GPB; const int nb_max = Lmax > 512 ? 16 : 256 * 16; if (nb > nb_max) nb = nb_max;   // reads beyond the LDS tiles: few groups (megabytes of traceback each)
 	const uint64_t arena_cap = ((uint64_t)nr * 12 + 4096 + (uint64_t)c->n_bases / 8) * A->arena_scale;
 	if (A->arena.ensure(arena_cap)) return -1;
@@ -3027,9 +3186,8 @@ int al_run_align_stage(al_ctx_t *c)
 	AL_HIP_CHECK(hipMemsetAsync(A->dbgbuf.p, 0, 640 * 8, s));
 	G.dbg = A->dbgbuf.p;
 	AlLogTab lt; lt.t = A->logtab.p; lt.n = A->logtab_n; lt.miss = c->counters.p + 8;
-	const int tmax = (Lmax <= 160 && tbound <= 336) ? 336 : (Lmax <= 256 && tbound <= 512) ? 512 : (Lmax <= 512 && tbound <= 1024) ? 1024 : 0;
-	const int qmax = tmax == 336 ? 160 : tmax == 512 ? 256 : 512;
-	const bool long_mode = tmax == 0;              // reads beyond the LDS tiles: the whole batch through k_align_long (state blocks in HBM)
+	const int tmax = eg.dp.tmax, qmax = eg.qmax;
+	const bool long_mode = eg.long_mode;              // reads beyond the LDS tiles: the whole batch through k_align_long (state blocks in HBM)
 	if (long_mode && (Lmax > AL_LONG_QMAX || tbound > AL_LONG_TMAX)) { fprintf(stderr, "[airlift] reads longer than %d bp (or an extension window longer than %d bp: read length + (read length * A + end bonus - O) / E + 16) are not supported by the device extension kernels (max read length in batch: %d, window %d)\n", AL_LONG_QMAX, AL_LONG_TMAX, Lmax, tbound); return -3; }
 	if (long_mode) {   // few groups: each needs a state block of ~1.3 MB and a traceback area of (Lmax + window) * band columns bytes
 		if (nb > 16) nb = 16;
@@ -3107,10 +3265,7 @@ int al_run_align_stage(al_ctx_t *c)
 		if (nj == 0) { AL_HIP_CHECK(hipStreamSynchronize(s)); if (early_mono()) return -1; }
 		if (nj > 0) {
 			hipLaunchKernelGGL(k_iota, dim3((nj + 255) / 256), dim3(256), 0, s, A->job_idx.p, nj);
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
-			if (A->sort_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(A->sort_tmp.p, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
+			if (ext_dp_sort_jobs(c, A, nj, s)) return -1;
 			AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_SORT + 1], s));
 			unsigned long long sub7[2] = {0, 0};
 			AL_HIP_CHECK(hipMemcpyAsync(hist, A->hist.p, (AL_NCLS + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -3121,110 +3276,8 @@ int al_run_align_stage(al_ctx_t *c)
 			if (early_mono()) return -1;
 			if (getenv("AL_TRACE")) fprintf(stderr, "[airlift] trace: prep + job sort done\n");
 			if ((c->P.dbg >> 30) & 1) { fprintf(stderr, "[airlift] DP jobs per class (lane16 lane32 lane64 g1 g2 g4 g8 g22 g32 lds | empty):"); for (int i = 0; i <= AL_NCLS; ++i) fprintf(stderr, " %llu", hist[i]); fprintf(stderr, "\n"); }
-			// one launch per job class over its slice of the sorted job list
-			static const int NBs[6] = {1, 2, 4, 8, 22, 32};
-			uint32_t first = 0;
-			// (round 5) A small batch's classes do not fill the chip (C2: 32 000 jobs of 9 ... 22 blocks over three kernels, 8 blocks per CU) and every class ends in the
-			// tail of its longest job (the 22-block kernel: 0.85 ms whatever the batch): below AL_DP_CONC jobs (default 700 000; 0: never) the class kernels run side by
-			// side on four streams, each on a workspace range of its own; the per-class intervals of the stage table then hold launch order only.
-			static const long long conc_thr = getenv("AL_DP_CONC") ? atoll(getenv("AL_DP_CONC")) : 700000;
-			long long n_real = 0; for (int cls = 0; cls < AL_NCLS; ++cls) n_real += (long long)hist[cls];                   // (nj counts two slots per hit, most of them empty)
-			const bool dp_conc = n_real < conc_thr;
-			size_t ws_off[AL_NCLS + 1]; ws_off[0] = 0;
-			{   // one workspace range for every class of this batch: sized for the largest now, not grown class by class (a regrow frees -- and waits for -- what the running class uses)
-				size_t need = 0;
-				for (int cls = 0; cls < AL_NCLS; ++cls) {
-					const uint32_t cnt = (uint32_t)hist[cls];
-					size_t b = 0;
-					if (cnt == 0) b = 0;
-					else if (cls < 3) { const int TC = 16 << cls; int nw = (int)((cnt + 63) / 64); if (nw > 1024) nw = 1024; b = (size_t)nw * ((size_t)(AL_LANE_QC + TC) * (size_t)(TC + 16) * 64); }
-					else if (cls < 9) {
-						const int NB = NBs[cls - 3];
-						const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
-						const int cap = NB <= 4 ? (getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096) : NB <= 8 ? (getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096) : NB <= 22 ? (getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072) : 2048;
-						const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap;   // (side by side the ranges add up: slightly fewer blocks each keep the sum near what the largest range was)
-						int nbj = (int)((cnt + 3) / 4); if (nbj > cap_eff) nbj = cap_eff;
-						b = (size_t)nbj * 4 * st2;
-						if (cls == 7) { const unsigned long long c12 = std::min<unsigned long long>(sub7[0], cnt), c16 = std::min<unsigned long long>(sub7[1], cnt - c12), c22 = cnt - c12 - c16;
-						                if (c22 > 0 && c22 <= 8192) b += (size_t)std::min<unsigned long long>((c22 + 3) / 4, (unsigned long long)nbj) * 4 * st2; }   // (a thin 22-block kernel beside the other two of its class: its own range behind theirs)
-					} else { int nbj = (int)cnt; if (nbj > 2048) nbj = 2048; b = (size_t)nbj * stride; }
-					b = (b + 255) / 256 * 256;
-					ws_off[cls + 1] = dp_conc ? ws_off[cls] + b : 0;
-					if (dp_conc) need += b; else if (b > need) need = b;
-				}
-				if (need && A->gws.ensure(need + 64)) return -1;
-			}
-			hipStream_t dps[4] = {s, c->aux[0], c->aux[1], c->aux[2]}; int dpk = 0;
-			if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0)); }
-			hipStream_t const s_main = s;
-			bool g12_done = false, thin22_join = false; hipStream_t thin22_stream = nullptr;
-			// two cells per lane (al_dev_ksw2.h) where its arithmetic holds: the permute's constant 0xff is the score of an N, scores within +-16
-			// (int16 H of the 352 x 512 tile); AL_DP_PK=0: the one-cell form everywhere (tests, A/B)
-			static const int pk_env = getenv("AL_DP_PK") ? atoi(getenv("AL_DP_PK")) : 1;
-			const int sc_amb_ = c->P.sc_ambi > 0 ? -c->P.sc_ambi : c->P.sc_ambi, sc_N_ = sc_amb_ == 0 ? -std::min(c->P.e2, c->P.e) : sc_amb_;
-			const bool dp_pk = pk_env != 0 && sc_N_ == -1 && c->P.a > 0 && c->P.a <= 16 && c->P.b >= 0 && c->P.b <= 16 && c->P.q + c->P.e <= 64 && c->P.q2 + c->P.e2 <= 64 && c->P.q >= 0 && c->P.e >= 0 && c->P.q2 >= 0 && c->P.e2 >= 0;
-			for (int cls = 0; cls < AL_NCLS; ++cls) {
-				const uint32_t cnt = (uint32_t)hist[cls];
-				if (cls == 3) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_LANE + 1], s));
-				if (cls == 6) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G4 + 1], s));
-				if (cls == 7) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G8 + 1], s));
-				if (cls == 8 && !g12_done) { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s)); AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s)); g12_done = true; }
-				if (cnt == 0) continue;
-				unsigned char *const gbase = A->gws.p + ws_off[cls];
-				hipStream_t s = dp_conc ? dps[dpk++ & 3] : s_main;                 // (shadows the stage's stream inside the class)
-				if (cls < 3) {                                                    // lane-per-job
-					const int TC = 16 << cls;
-					const size_t tbs = (size_t)(AL_LANE_QC + TC) * (size_t)(TC + 16) * 64;
-					int nw = (int)((cnt + 63) / 64); if (nw > 1024) nw = 1024;
-					if (cls == 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<16, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
-					else if (cls == 1) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<32, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
-					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lane<64, AL_LANE_QC>), dim3(nw), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, tbs, c->P);
-				} else if (cls < 9) {
-					const int NB = NBs[cls - 3];
-					const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
-					int nbj = (int)((cnt + 3) / 4); { static const int caps[3] = { getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096, getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096, getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072 };
-					  const int cap = NB <= 4 ? caps[0] : NB <= 8 ? caps[1] : NB <= 22 ? caps[2] : 2048; const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap; if (nbj > cap_eff) nbj = cap_eff; }
-#define LAUNCH_DP(NBV) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P)
-// (queries of up to 256 bases -- every short-read set -- get the instance with the smaller query arrays: 12 instead of 14 KB of LDS per block at 16 blocks, a third wavefront per SIMD)
-#define LAUNCH_DPK(NBV) do { if (Lmax <= 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 256, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); \
-	                         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); } while (0)
-					if (NB == 1) LAUNCH_DP(1); else if (NB == 2) LAUNCH_DP(2); else if (NB == 4) LAUNCH_DP(4); else if (NB == 8) { if (dp_pk) LAUNCH_DPK(8); else LAUNCH_DP(8); } else if (NB == 32) { static const bool pk32 = !(getenv("AL_DP_PK32") && atoi(getenv("AL_DP_PK32")) == 0); if (dp_pk && pk32) LAUNCH_DPK(32); else LAUNCH_DP(32); }
-					else {   // 9 ... 22 blocks: the sorted slice holds the jobs of <= 12 blocks first, then 13 ... 16, then the rest
-						static const bool split = !getenv("AL_DP_NO_SPLIT");
-						const uint32_t c12 = split ? (uint32_t)std::min<unsigned long long>(sub7[0], cnt) : 0u, c16 = split ? (uint32_t)std::min<unsigned long long>(sub7[1], cnt - c12) : 0u, c22 = cnt - c12 - c16;
-						const uint32_t first0 = first, cnt0 = cnt;
-#define LAUNCH_DPS(NBV, F, N) do { if ((N) > 0) { int nb2 = (int)(((N) + 3) / 4); if (nb2 > nbj) nb2 = nbj; \
-							if (dp_pk && Lmax <= 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 256, NBV * 16, true>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); \
-							else if (dp_pk) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16, true>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); \
-							else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16>), dim3(nb2), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, (F), (N), gbase + (size_t)gw_used * 4 * st2, st2, pb, cw, c->P); gw_used += nb2; } } while (0)
-						// (the three kernels run one after the other on this stream: they may share the workspace range)
-						int gw_used = 0;
-						{
-							// few 22-block jobs (C4: a few hundred): the kernel is the tail of its longest job, 0.85 ms alone at the end of the stage -- it starts first, on a side stream, beside the other two.
-							// (Side by side with the other classes the three kernels of this one still run one after the other and share a range: a range each cost 6.8 GB per context.)
-							hipStream_t const s_cls = s;
-							const bool thin22 = c22 > 0 && c22 <= 8192u && split;
-							if (thin22) { hipStream_t const s22 = s_cls == c->aux[1] ? c->aux[2] : c->aux[1]; AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s_cls)); AL_HIP_CHECK(hipStreamWaitEvent(s22, c->ev_fj[0], 0)); s = s22; gw_used = nbj; LAUNCH_DPS(22, first0 + c12 + c16, c22); s = s_cls; gw_used = 0; thin22_join = true; thin22_stream = s22; }
-							LAUNCH_DPS(12, first0, c12); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); gw_used = 0; LAUNCH_DPS(16, first0 + c12, c16); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); gw_used = 0;
-							if (!thin22) LAUNCH_DPS(22, first0 + c12 + c16, c22);
-							if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); }
-						}
-						g12_done = true;
-						(void)cnt0;
-#undef LAUNCH_DPS
-					}
-#undef LAUNCH_DP
-#undef LAUNCH_DPK
-				} else {
-					int nbj = (int)cnt; if (nbj > 2048) nbj = 2048;
-					if (tmax <= 512) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<512, 256>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
-					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<1024, 512>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
-				}
-				if (getenv("AL_TRACE")) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: DP class %d (%u jobs) -> %s\n", cls, cnt, hipGetErrorName(e)); }
-				first += cnt;
-			}
-			if (dp_conc) for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
-			if (thin22_join && !dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[1], thin22_stream)); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[1], 0)); }   // (side by side: the join above covers every aux stream)
+			const DpGeom geom = {Lmax, tmax, stride, p_bytes, cig_words};
+			if (ext_dp_launch_classes(c, A, G, E, s, hist, sub7, geom)) return -1;
 		}
 		else { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_SORT + 1], s)); for (int i = ST_EXT_DP_LANE; i < ST_EXT_DP_G22; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); }   // (no jobs: empty intervals)
 		AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G22 + 1], s));
@@ -3282,6 +3335,113 @@ int al_run_align_stage(al_ctx_t *c)
 }
 
 // --MD / --cs: the tag stage on the final records (after the arena-overflow re-runs, so it sees the CIGARs that stay)
+// Tap for the parity tests: caller-supplied extension jobs through the align stage's own DP launches.  The jobs are keyed and counted as k_ext_prep
+// keys and counts its own (d_job_class, d_job_key, d_job_tally), sorted with the stage's sort call and handed to ext_dp_launch_classes(): every
+// production DP kernel instance is reached by the size, direction and number of the jobs alone.  Queries come from the resident batch's reads
+// (rd_seq), targets from the index's packed reference, as an ExtJob's do.
+struct DbgExtIn { uint64_t toff; uint32_t read, qoff; uint16_t qlen, tlen; uint8_t rev, kind, pad0, pad1; uint32_t pad2; };   // == ExtJob
+extern "C" __global__ void __launch_bounds__(256)
+k_dbg_ext_key(const DbgExtIn *__restrict__ in, int n, ExtShared E, int lane_ok)
+{
+	__shared__ unsigned s_hist[AL_NCLS + 1], s_tl[AL_NCLS + 1], s_sub[2];
+	if (threadIdx.x <= AL_NCLS) { s_hist[threadIdx.x] = 0; s_tl[threadIdx.x] = 0; }
+	if (threadIdx.x < 2) s_sub[threadIdx.x] = 0;
+	__syncthreads();
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j < n) {
+		const DbgExtIn d = in[j];
+		ExtJob jb; jb.toff = d.toff; jb.read = d.read; jb.qoff = d.qoff; jb.qlen = d.qlen; jb.tlen = d.tlen; jb.rev = d.rev; jb.kind = d.kind; jb.pad0 = jb.pad1 = 0; jb.pad2 = 0;
+		E.jobs[j] = jb;
+		const int cls = d_job_class(jb.qlen, jb.tlen, lane_ok);
+		E.job_key[j] = d_job_key(cls, jb.qlen, jb.tlen, jb.kind);
+		d_job_tally(cls, jb.tlen, s_hist, s_sub, s_tl);
+	}
+	__syncthreads();
+	if (threadIdx.x <= AL_NCLS && s_hist[threadIdx.x]) atomicAdd(&E.hist[threadIdx.x], (unsigned long long)s_hist[threadIdx.x]);
+	if (threadIdx.x <= AL_NCLS && s_tl[threadIdx.x]) atomicAdd(&E.hist[24 + threadIdx.x], (unsigned long long)s_tl[threadIdx.x]);
+	if (threadIdx.x < 2 && s_sub[threadIdx.x]) atomicAdd(&E.hist[36 + threadIdx.x], (unsigned long long)s_sub[threadIdx.x]);
+}
+extern "C" __global__ void __launch_bounds__(256)
+k_dbg_ext_gather(ExtShared E, AlignShared G, int n, int lane_ok, int32_t *__restrict__ out9, uint32_t *__restrict__ cig_out, int cig_cap)
+{
+	const int j = blockIdx.x * blockDim.x + threadIdx.x;
+	if (j >= n) return;
+	const ExtOut o = E.outs[j]; const ExtJob jb = E.jobs[j];
+	const int cls = d_job_class(jb.qlen, jb.tlen, lane_ok), nc = (int)(o.flags_ncig >> 8);
+	// a CIGAR the kernels could not keep: the arena was full, or a lane-per-job kernel's register buffer (the stage re-does such a fragment from scratch)
+	const bool lost = nc > 6 && (o.cig_off == 0xffffffffu || (cls < 3 && nc > AL_FCIG));
+	int32_t *r = out9 + (size_t)j * 9;
+	r[0] = o.max; r[1] = o.max_q; r[2] = o.max_t; r[3] = o.mqe_t; r[4] = (int32_t)(o.flags_ncig & 1); r[5] = (int32_t)(o.flags_ncig >> 1 & 1); r[6] = nc; r[7] = cls; r[8] = lost || nc > cig_cap ? 1 : 0;
+	if (!lost) for (int i = 0; i < nc && i < cig_cap; ++i) cig_out[(size_t)j * cig_cap + i] = nc <= 6 ? o.cig[i] : G.arena[(size_t)o.cig_off + i];
+}
+extern "C" int al_dbg_ext_dp(al_ctx_t *c, int n, const int64_t *jobs8 /* read, rev, kind, qoff, qlen, contig, tpos, tlen per job */, int32_t *out9, uint32_t *cig_out, int cig_cap, uint64_t *shadow8)
+{
+	if (!c || !jobs8 || !out9 || !cig_out || n <= 0 || cig_cap <= 0) return -1;
+	if (c->dev_batch || c->n_reads <= 0 || (int)c->h_rd_len.size() < c->n_reads || !c->rd_seq.p || c->mi->seq.empty()) { fprintf(stderr, "[airlift] al_dbg_ext_dp: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	if (al_map_only(c->opt.flag)) return -1;
+	AL_HIP_CHECK(hipSetDevice(c->device));
+	hipStream_t s = c->stream;
+	AlignState *A = get_state(c);
+	const ExtGeom eg = ext_geometry(c);
+	if (eg.long_mode) { fprintf(stderr, "[airlift] al_dbg_ext_dp: with reads of %d bases and these scores the stage runs no DP jobs (windows beyond the LDS tiles)\n", eg.dp.Lmax); return -3; }
+	// every job inside what k_ext_prep can emit (the kernels' buffers are sized for exactly that) and inside its read and its contig
+	std::vector<DbgExtIn> in((size_t)n); uint64_t cig_sum = 0;
+	for (int j = 0; j < n; ++j) {
+		const int64_t *q = jobs8 + (size_t)j * 8;
+		const int64_t read = q[0], rev = q[1], kind = q[2], qoff = q[3], qlen = q[4], rid = q[5], tpos = q[6], tlen = q[7];
+		bool ok = read >= 0 && read < c->n_reads && (rev == 0 || rev == 1) && (kind == 0 || kind == 1) && rid >= 0 && rid < (int64_t)c->mi->seq.size() &&
+		          qlen >= 1 && qlen <= eg.qmax && tlen >= 1 && tlen <= eg.dp.tmax && tlen <= eg.tbound;
+		if (ok) {
+			const int64_t rl = c->h_rd_len[read], cl = c->mi->seq[rid].len;
+			ok = kind == 0 ? (qoff < rl && qoff - (qlen - 1) >= 0 && tpos < cl && tpos - (tlen - 1) >= 0) : (qoff >= 0 && qoff + qlen <= rl && tpos >= 0 && tpos + tlen <= cl);
+		}
+		if (!ok) { fprintf(stderr, "[airlift] al_dbg_ext_dp: job %d (read %lld rev %lld kind %lld qoff %lld qlen %lld contig %lld tpos %lld tlen %lld) is outside its read, its contig or the stage's limits (query <= %d, target <= %d)\n",
+		                   j, (long long)read, (long long)rev, (long long)kind, (long long)qoff, (long long)qlen, (long long)rid, (long long)tpos, (long long)tlen, eg.qmax, std::min(eg.dp.tmax, eg.tbound)); return -2; }
+		DbgExtIn &d = in[j]; memset(&d, 0, sizeof(d));
+		d.toff = c->mi->seq[rid].offset + (uint64_t)tpos; d.read = (uint32_t)read; d.qoff = (uint32_t)qoff; d.qlen = (uint16_t)qlen; d.tlen = (uint16_t)tlen; d.rev = (uint8_t)rev; d.kind = (uint8_t)kind;
+		cig_sum += (uint64_t)(qlen + tlen);
+	}
+	const uint32_t nj = (uint32_t)n;
+	const uint64_t arena_cap = cig_sum + 4096;
+	if (A->jobs.ensure(nj + 1) || A->outs.ensure(nj + 1) || A->job_key.ensure(nj + 1) || A->job_key2.ensure(nj + 1) || A->job_idx.ensure(nj + 1) || A->job_idx2.ensure(nj + 1) ||
+	    A->hist.ensure(AL_HIST_N) || A->arena.ensure(arena_cap) || A->dbgbuf.ensure(640)) return -1;
+	DbgExtIn *d_in = nullptr; int32_t *d_out = nullptr; uint32_t *d_cig = nullptr;
+	int rc = -1;
+	auto run = [&]() -> int {
+		AL_HIP_CHECK(hipMalloc((void **)&d_in, (size_t)n * sizeof(DbgExtIn))); AL_HIP_CHECK(hipMalloc((void **)&d_out, (size_t)n * 36)); AL_HIP_CHECK(hipMalloc((void **)&d_cig, (size_t)n * cig_cap * 4 + 16));
+		AL_HIP_CHECK(hipMemcpyAsync(d_in, in.data(), (size_t)n * sizeof(DbgExtIn), hipMemcpyHostToDevice, s));
+		AL_HIP_CHECK(hipMemsetAsync(d_cig, 0, (size_t)n * cig_cap * 4, s));
+		AL_HIP_CHECK(hipMemsetAsync(A->hist.p, 0, AL_HIST_N * 8, s));
+		AL_HIP_CHECK(hipMemsetAsync(A->outs.p, 0xff, (size_t)nj * sizeof(ExtOut), s));            // (a job no kernel took comes back as n_cigar 0xffffff)
+		AL_HIP_CHECK(hipMemsetAsync(A->dbgbuf.p, 0, 640 * 8, s));
+		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 11, 0, 8, s));                                // the arena's cursor
+		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 24, 0, 64, s));                               // the early exit's shadow counts
+		AlignShared G; G.S4 = c->di.S4; G.seq_off = c->di.seq_off; G.seq_len = c->di.seq_len; G.arena = A->arena.p; G.arena_cnt = c->counters.p + 11; G.arena_cap = arena_cap; G.counters = c->counters.p; G.dbg = A->dbgbuf.p;
+		ExtShared E; E.jobs = A->jobs.p; E.outs = A->outs.p; E.rext = A->rext.p; E.job_off = A->job_off.p; E.frag_slow = A->frag_slow.p; E.job_key = A->job_key.p; E.hist = A->hist.p;
+		const int lane_ok = !((c->P.dbg >> 29) & 1);
+		hipLaunchKernelGGL(k_dbg_ext_key, dim3((nj + 255) / 256), dim3(256), 0, s, (const DbgExtIn *)d_in, n, E, lane_ok);
+		hipLaunchKernelGGL(k_iota, dim3((nj + 255) / 256), dim3(256), 0, s, A->job_idx.p, nj);
+		if (ext_dp_sort_jobs(c, A, nj, s)) return -1;
+		unsigned long long hist[16] = {0}, sub7[2] = {0, 0};
+		AL_HIP_CHECK(hipMemcpyAsync(hist, A->hist.p, (AL_NCLS + 1) * 8, hipMemcpyDeviceToHost, s));
+		AL_HIP_CHECK(hipMemcpyAsync(sub7, A->hist.p + 36, 16, hipMemcpyDeviceToHost, s));
+		AL_HIP_CHECK(hipStreamSynchronize(s));
+		for (int i = 0; i < AL_NCLS; ++i) c->stat_dp_jobs[i] = c->stat.dp_jobs[i] = hist[i];
+		if (ext_dp_launch_classes(c, A, G, E, s, hist, sub7, eg.dp)) return -1;
+		hipLaunchKernelGGL(k_dbg_ext_gather, dim3((nj + 255) / 256), dim3(256), 0, s, E, G, n, lane_ok, d_out, d_cig, cig_cap);
+		AL_HIP_CHECK(hipGetLastError());
+		AL_HIP_CHECK(hipMemcpyAsync(out9, d_out, (size_t)n * 36, hipMemcpyDeviceToHost, s));
+		AL_HIP_CHECK(hipMemcpyAsync(cig_out, d_cig, (size_t)n * cig_cap * 4, hipMemcpyDeviceToHost, s));
+		if (shadow8) AL_HIP_CHECK(hipMemcpyAsync(shadow8, c->counters.p + 24, 64, hipMemcpyDeviceToHost, s));
+		AL_HIP_CHECK(hipStreamSynchronize(s));
+		return 0;
+	};
+	rc = run();
+	if (rc) (void)hipDeviceSynchronize();
+	(void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_cig);
+	return rc;
+}
+
 int al_run_tags(al_ctx_t *c)
 {
 	AlignState *A = get_state(c);

@@ -217,8 +217,24 @@ int  al_extract_to_memory(const char *bam_fn, const char *bed_fn, int read_size,
 /* Tap (parity tests): the extension DP alone -- ksw_extd2_sse's result for n caller-supplied pairs, as the reference's --print-aln-seq
  * shows them (align.c:313-339).  seqs: nt4 codes (0..4); jobs6: {target offset, query offset, tlen, qlen, ksw flag, 0} per pair (the
  * sequences as passed to ksw, i.e. already reversed for left extensions); out9 per pair: score, max, max_q, max_t, mqe, mqe_t, zdropped,
- * reach_end, n_cigar (-1: pair larger than 1024 x 512); cig_out: cig_cap words per pair.  Uses the context's options. */
+ * reach_end, n_cigar (-1: pair larger than 1024 x 512); cig_out: cig_cap words per pair.  Uses the context's options.
+ * Runs the DP's device functions on LDS rows of its own, not the align stage's kernels: the one-cell-per-lane forms (register blocks up to
+ * 22 x 16 target bases, LDS rows above), with AL_DBG bit 20 the two-cells-per-lane form on pairs of up to 352 target bases where the
+ * align stage would use it too (scores inside that form's arithmetic), without the early exit.  tests/test_gpu_dp_directed.py compares every
+ * field with ksw_extd2_sse; the align stage's own kernels are reached through al_dbg_ext_dp. */
 int  al_dbg_ksw(al_ctx_t *ctx, int n, const uint8_t *seqs, size_t n_seq_bytes, const int32_t *jobs6, int32_t *out9, uint32_t *cig_out, int cig_cap);
+/* Tap (parity tests): n caller-supplied extension jobs through the align stage's DP kernels -- keyed into classes, counted, sorted and launched
+ * by the code the stage runs for the jobs of a batch, so which kernel instance a job takes follows from its size, its direction and the list
+ * around it exactly as in a batch.  Needs a batch uploaded with al_batch_upload (the queries are read from its reads) and run once.
+ * jobs8 per job: read index, rev (1: the read's reverse complement), kind (0 = left extension: query and target are walked downwards from
+ * qoff / tpos and the ksw flags are EXTZ_ONLY | RIGHT | REV_CIGAR; 1 = right extension: upwards, EXTZ_ONLY), qoff (into the read as oriented
+ * by rev), qlen, contig, tpos (into the contig), tlen.  out9 per job: max, max_q, max_t, mqe_t, reach_end, zdropped, n_cigar, the job's class
+ * (0, 1 lane per job with targets <= 16 / 32; 3 ... 8 group DP of 1, 2, 4, 8, 22, 32 target blocks; 9 LDS rows), 1 if the CIGAR did not fit
+ * cig_cap words or the kernels' own buffers.  cig_out: cig_cap words per job.  shadow8 (may be NULL): the early exit's shadow counts of this
+ * call (AL_DBG2 bit 5): jobs, jobs whose exit-row state differs from the full run's, rows, rows needed, ...  The per-class job counts are left
+ * in al_batch_stat's dp_jobs.  Returns 0; -2: a job lies outside its read, its contig or what the stage can emit for this batch (nothing ran);
+ * -3: the batch's reads are too long for the stage to run DP jobs at all. */
+int  al_dbg_ext_dp(al_ctx_t *ctx, int n, const int64_t *jobs8, int32_t *out9, uint32_t *cig_out, int cig_cap, uint64_t *shadow8);
 
 /* Self-test of the multi-lane output path (offset exchange + pwrite, or ordered turns) with synthetic blocks; needs no GPU. */
 int  al_dbg_ordered_out_selftest(const char *path, int n_lanes, int n_batches, int use_offsets);

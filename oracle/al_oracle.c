@@ -825,8 +825,7 @@ void o_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *target
 
 	ksw_reset(ez);
 	if (m <= 1 || qlen <= 0 || tlen <= 0) return;
-	if (q2 + e2 < q + e) t = q, q = q2, q2 = t, t = e, e = e2, e2 = t;
-	qe = q + e;
+	if (q2 + e2 < q + e) t = q, q = q2, q2 = t, t = e, e = e2, e2 = t;   /* qe keeps q + e of before the swap (ksw2_extd2_sse.c:60,70): H[0][0] is v[0] - qe */
 	qe_ = I8(q + e); qe2_ = I8(q2 + e2);
 	sc_mch = mat[0]; sc_mis = mat[1];
 	sc_N = mat[m*m-1] == 0? I8(-e2) : mat[m*m-1];
