@@ -49,7 +49,9 @@ __device__ __forceinline__ unsigned long long d_grp_any(unsigned long long b) { 
 // reach_end, mqe_t when reach_end, the CIGAR from the chosen end cell); only k_ext_dp asks for it, every other caller keeps the full DP and its
 // zdropped / score.  The rule and its proof are in DESIGN.md §4.  xcnt (shadow mode, AL_DBG2 bit 5): the rule is evaluated, the state at the
 // first row where it holds is compared with the full run's, and the counts go to xcnt[0..7].
-template <int NP, class LT, int DIR = 2, bool EXIT = false>
+// EXIT == 2 (the 8-block class): E3 without its first alternative -- the group leaves only where no later row can z-drop or have an empty band, so
+// its zdropped bit stays the full run's as well (that class's jobs are checked on it: tests/test_gpu_dp_directed.py).
+template <int NP, class LT, int DIR = 2, int EXIT = 0>
 __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE, const uint8_t *__restrict__ selO, const int gl, GroupWs &ws, int qlen, int tlen, const AlParams &P,
                                          int w, int zdrop, int end_bonus, int flag, EzD &ez, bool do_bt = true, unsigned long long *xcnt = nullptr)
 {
@@ -108,6 +110,7 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 	const bool no_empty = tlen - 1 <= ((qlen + tlen - 2 + w) >> 1);            // E3(a): no later row has an empty band (st - en grows from row qlen - 1 on)
 	const uint32_t ATT = (uint32_t)(sc_mch * 2 * gl) | (uint32_t)(sc_mch * (2 * gl + 1)) << 16;   // a t of this lane's two cells in superblock 0
 	int f_prev = KSW_NEG_INF;
+	const int xs = P.dp_exit_stride - 1;                                        // rows r = xs (mod S) are tested; F(r - 1) and F(r) are all the test reads
 	if constexpr (EXIT) if (shadow && gl == 0) L.ezc[5] = 0xffffffffu;          // (shadow mode: the exit row, in LDS -- no register for it in the row loop)
 	for (r = 0; r < n_rows; ++r) {
 		int st, en;
@@ -154,7 +157,8 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 		}
 		uint32_t bkey = 0x80008000u, bcc = 0;                                   // per half: best 2 H + (end cell) of this lane's cells, and its superblock
 		uint32_t gacc = 0x80008000u;                                            // (EXIT) per half: largest H + a t of this lane's cells in the row
-		const bool acc_row = EXIT && __ballot(ex_on && r >= qlen - 1) != 0;   // (wavefront-uniform: a scalar branch per superblock)
+		// (the rule is sound at whatever row it is evaluated: it is, in every S-th row (AL_DP_EXIT_STRIDE), and only that row and the one before it accumulate F)
+		const bool acc_row = EXIT && (r & xs) >= xs - 1 && __ballot(ex_on && r >= qlen - 1) != 0;   // (wavefront-uniform: r alone gates it; a scalar branch per superblock)
 		// the cell recurrence (:177-265) on two cells: left neighbours (xt1, vt1, x2t1), the cells' own u, y, y2 and score -> new state and traceback byte
 		auto cell = [&](const uint32_t xt1, const uint32_t vt1, const uint32_t x2t1, const uint32_t uo, const uint32_t yo, const uint32_t y2o, const uint32_t so,
 		                uint32_t &xn, uint32_t &vn, uint32_t &x2n, uint32_t &un, uint32_t &yn, uint32_t &y2n, uint32_t &d) {
@@ -307,7 +311,7 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_HALF_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
 			{ const int o = __builtin_amdgcn_update_dpp(k, k, DPP_ROW_MIRROR, 0xf, 0xf, false); k = o > k ? o : k; }
 			const int f_row = k == -32768 ? KSW_NEG_INF : k + sc_mch * (qlen - 1 - r);   // F(r)
-			if (ex_on && r >= qlen) {
+			if (ex_on && r >= qlen && (r & xs) == xs) {
 				const int t1 = r + 1, gb = min(q + e * t1, q2 + e2 * t1);
 				const int bnd = t1 <= tlen - 1 && t1 <= w ? sc_mch * (1 + min(qlen - 1, tlen - 2 - r)) - gb : KSW_NEG_INF;   // B(r): cells (t, 0), t > r
 				const int U = max(max(f_row, f_prev), bnd);
@@ -318,7 +322,7 @@ __device__ __forceinline__ void d_ksw_pk(LT &L, const uint8_t *__restrict__ selE
 				// from the max cell by k diagonal steps (>= -|worst score| each) and d = t_C - max_t - k >= 0 deletions, so its row's best B has
 				// max - H_B <= k |worst| + q2 + e2 d, and B (i_B <= qlen - 1, t_B >= t_C) lies l >= d off the max cell's diagonal.
 				const int kq = qlen - 1 - ez.max_q;
-				const bool c3 = ez.mqe + end_bonus <= ez.max || (no_empty && (zdrop < 0 || (ez.max_t >= 0 && kq * bmax + q2 <= zdrop && ez.max_t + kq <= tlen - 1 && r + 2 - qlen - ez.max_t - kq >= 0)));
+				const bool c3 = (EXIT != 2 && ez.mqe + end_bonus <= ez.max) || (no_empty && (zdrop < 0 || (ez.max_t >= 0 && kq * bmax + q2 <= zdrop && ez.max_t + kq <= tlen - 1 && r + 2 - qlen - ez.max_t - kq >= 0)));
 				if (wok && c1 && c2 && c3) {                                     // E1, E2, E3
 					if (!shadow) break;
 					if ((int)L.ezc[5] < 0 && gl == 0) { L.ezc[0] = (uint32_t)ez.max; L.ezc[1] = (uint32_t)ez.max_t; L.ezc[2] = (uint32_t)ez.max_q; L.ezc[3] = (uint32_t)ez.mqe; L.ezc[4] = (uint32_t)ez.mqe_t; L.ezc[5] = (uint32_t)r; }   // (L.ezc is free until the backtrack)

@@ -89,6 +89,7 @@ struct AlParams {             // kernel parameter block (copy of the options the
 	int dbg2;                 // more of the same (AL_DBG2 env): bit 3 cycle counters of the lane chaining kernels' phases (printed per batch), bit 20 the seed / sort / chain stages only
 	                          // (bit 5, shadow mode of the extension DP's early exit, leaves the results valid: counts printed per batch)
 	int dp_exit;              // the extension DP's early exit (al_dev_ksw2.h): on unless AL_DP_EXIT=0
+	int dp_exit_stride;       // ... evaluated every S-th anti-diagonal, S = 1, 2, 4 or 8 (AL_DP_EXIT_STRIDE)
 };
 
 struct AlMatch {              // one query minimizer that passed the occurrence filter (mm_match_t, map.c:82-88)

@@ -113,9 +113,25 @@ __device__ __forceinline__ void d_cig_flush(CigW &w) { if (w.cur != 0xffffffffu)
 
 __device__ __forceinline__ void d_backtrack(const uint8_t *p, int n_col, int qlen, int tlen, int w, int is_rev, int i0, int j0, CigW &cw)
 {   // ksw_backtrack, ksw2.h:119-151 (is_rot = 1, min_intron_len = 0); off[]/off_end[] are recomputed from r
+	// A diagonal run is taken in one step of the 16-lane group: in state 0 lane k looks at cell (i - k, j - k), the run is as long as the leading
+	// lanes that find a match there (inside the matrix, not forced, low three bits 0), and the cell that ends it takes the serial step below.
+	// Lanes behind the run's end look at cells the serial walk never reads: their index is clamped (an unconditional load), their verdict unused.
 	int i = i0, j = j0, state = 0;
 	cw.n = 0; cw.cur = 0xffffffffu;
+	const int lane = (int)__lane_id(), gk = lane & (GW - 1), gsh = lane & ~(GW - 1);
 	while (i >= 0 && j >= 0) {
+		if (state == 0) {
+			int st, en; const int ik = i - gk, jk = j - gk, rk = ik + jk;
+			d_row_bounds(rk, qlen, tlen, w, st, en);
+			const int off = st / 16 * 16, off_end = (en + 16) / 16 * 16 - 1;
+			const bool in = ik >= 0 && jk >= 0 && ik >= off && ik <= off_end;
+			const uint32_t tmp = p[in ? (size_t)rk * n_col + ik - off : (size_t)0];
+			const uint32_t m = (uint32_t)(__ballot(in && (tmp & 7) == 0) >> gsh) & 0xffffu;
+			const int n = __builtin_ctz(~m);
+			if (n > 0) { d_push_cigar(cw, 0, n); i -= n; j -= n; }
+			if (n == GW) continue;
+			if (i < 0 || j < 0) break;
+		}
 		int force_state = -1, st, en; const int r = i + j;
 		d_row_bounds(r, qlen, tlen, w, st, en);
 		const int off = st / 16 * 16, off_end = (en + 16) / 16 * 16 - 1;
@@ -2208,13 +2224,86 @@ template <int QMAXJ, int TMAXJ, bool PK = false> struct JobLds {
 	// traceback tile: jobs of more than 64 target bases have more than 40 rows of at least 32 bytes -- they never fit it, and without it twice
 	// as many wavefronts fit a CU (the kernel waits on LDS reads and byte stores with 3.5 waves per SIMD)
 	static constexpr int kPtb = TMAXJ <= 64 && !PK ? AL_LPTB : 0;   // (the two-cells-per-lane form has no LDS traceback tile: al_dev_ksw2.h)
-	uint8_t sq[QMAXJ + 2 * TMAXJ + 32];      // TMAXJ bytes of front pad, the reversed query, zeros up to qlen + TMAXJ + 16 (al_dev_ksw.h)
-	uint8_t selO[PK ? QMAXJ + 2 * TMAXJ + 32 : 1];   // two-cells-per-lane form (al_dev_ksw2.h): sq holds the score permute's selector bytes for a cell in the low half, selO for one in the high half
+	// (sq, selO and tbuf are staged sixteen bytes per store: d_stage_job)
+	uint8_t __attribute__((aligned(16))) sq[QMAXJ + 2 * TMAXJ + 32];      // TMAXJ bytes of front pad, the reversed query, zeros up to qlen + TMAXJ + 16 (al_dev_ksw.h)
+	uint8_t __attribute__((aligned(16))) selO[PK ? QMAXJ + 2 * TMAXJ + 32 : 16];   // two-cells-per-lane form (al_dev_ksw2.h): sq holds the score permute's selector bytes for a cell in the low half, selO for one in the high half
 	uint32_t __attribute__((aligned(8))) wtab[PK ? TMAXJ : 2];   // ... and the score tables of the target bases, two words per lane and superblock
-	uint8_t tbuf[TMAXJ + 16];
+	uint8_t __attribute__((aligned(16))) tbuf[TMAXJ + 16];
 	uint32_t ezc[AL_LCIG];
 	uint8_t ptb[kPtb > 0 ? kPtb : 4];
 };
+
+// ---- staging of a job (k_ext_dp): eight bases per pair of loads, sixteen bytes per store
+// Eight codes R(p .. p + 7) of a read in mapping orientation (nibble k = position p + k), for ANY p: the two loads are clamped to the read's own
+// words, positions outside [0, qlen) come out as garbage (ReadAcc::win8 without its precondition at either end of the read).
+__device__ __forceinline__ uint32_t d_read8(const uint32_t *__restrict__ seq, const int qlen, const int rev, const int p)
+{
+	const int src = rev ? qlen - 8 - p : p, wl = qlen > 0 ? (qlen - 1) >> 3 : 0, w = src >> 3, sh = (src & 7) << 2;
+	const uint32_t lo = seq[min(max(w, 0), wl)], hi = seq[min(max(w + 1, 0), wl)];
+	uint32_t v = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+	if (rev) {                                         // reverse the nibble order, complement codes < 4
+		v = ((v & 0x0f0f0f0fu) << 4) | ((v >> 4) & 0x0f0f0f0fu); v = __builtin_bswap32(v);
+		const uint32_t amb = (v >> 2) & 0x11111111u;
+		v ^= 0x33333333u & ~(amb * 3u);
+	}
+	return v;
+}
+// Eight reference codes from base a on (a may lie below 0: the clamped words then give garbage for the bases that do not exist)
+__device__ __forceinline__ uint32_t d_ref8(const uint32_t *__restrict__ S4, const int64_t a)
+{
+	const int64_t w = a >> 3; const int sh = (int)(a & 7) << 2;
+	const uint32_t lo = S4[w < 0 ? 0 : w], hi = S4[w + 1 < 0 ? 0 : w + 1];
+	return (uint32_t)((((uint64_t)hi << 32) | lo) >> sh);
+}
+__device__ __forceinline__ uint32_t d_nibrev8(uint32_t v) { v = ((v & 0x0f0f0f0fu) << 4) | ((v >> 4) & 0x0f0f0f0fu); return __builtin_bswap32(v); }   // nibble k <-> nibble 7 - k
+__device__ __forceinline__ uint32_t d_nibkeep(const uint32_t v, const int n) { return n >= 8 ? v : n <= 0 ? 0u : v & ((1u << (4 * n)) - 1u); }                 // the first n codes, base 0 behind them
+__device__ __forceinline__ uint32_t d_nib4(uint32_t h) { h &= 0xffffu; h = (h | h << 8) & 0x00ff00ffu; return (h | h << 4) & 0x0f0f0f0fu; }               // four codes -> four bytes
+// selector bytes of the score permute (al_dev_ksw2.h) from four base codes: E(base) = base, O(base) = 4 + base, E(N) = O(N) = 0x0d
+__device__ __forceinline__ void d_sel4(const uint32_t x, uint32_t &E, uint32_t &O)
+{
+	const uint32_t am = (((x >> 2) | (x >> 3)) & 0x01010101u) * 0xffu;      // 0xff in the bytes of the codes >= 4
+	E = (x & ~am) | (0x0d0d0d0du & am); O = ((x + 0x04040404u) & ~am) | (0x0d0d0d0du & am);
+}
+// The job's query goes in reversed (ksw2_extd2_sse.c:118: qr[t] = query[qlen - 1 - t]) behind the front pad, base 0 after it up to qlen + TMAXJ + 16;
+// a left extension has both sequences reversed (mm_seq_rev, align.c:694-695: query[i] = Q(qoff - i), target[i] = S(toff - i)), so its qr ascends
+// in read position and its target descends, a right extension's the other way round.  A lane makes sixteen bytes per step: two windows of eight
+// codes, or the pad's constants.  The packed form gets its selector bytes (sq: E, selO: O) straight from the codes.
+template <bool PK, int TMAXJ, class LT>
+__device__ __forceinline__ void d_stage_job(LT &L, const int gl, const uint32_t *__restrict__ seq, const int rqlen, const uint32_t *__restrict__ S4,
+                                            const int ql, const int tl, const int qoff, const uint64_t toff, const int rev, const bool left)
+{
+	uint4 *const q16 = reinterpret_cast<uint4 *>(L.sq + TMAXJ), *const o16 = reinterpret_cast<uint4 *>(L.selO + (PK ? TMAXJ : 0)), *const t16 = reinterpret_cast<uint4 *>(L.tbuf);
+	const int p0 = left ? qoff - (ql - 1) : qoff + ql - 1;                  // the read position of qr[0]
+	for (int c = gl; 16 * c < ql + TMAXJ + 16; c += GW) {
+		uint32_t x[4] = {0u, 0u, 0u, 0u};
+		if (16 * c < ql) {
+#pragma unroll
+			for (int h = 0; h < 2; ++h) {
+				const int t0 = 16 * c + 8 * h;
+				uint32_t v = left ? d_read8(seq, rqlen, rev, p0 + t0) : d_nibrev8(d_read8(seq, rqlen, rev, p0 - t0 - 7));
+				v = d_nibkeep(v, ql - t0);
+				x[2 * h] = d_nib4(v); x[2 * h + 1] = d_nib4(v >> 16);
+			}
+		}
+		if constexpr (PK) {
+			uint32_t E[4], O[4];
+#pragma unroll
+			for (int k = 0; k < 4; ++k) d_sel4(x[k], E[k], O[k]);
+			q16[c] = make_uint4(E[0], E[1], E[2], E[3]); o16[c] = make_uint4(O[0], O[1], O[2], O[3]);
+		} else q16[c] = make_uint4(x[0], x[1], x[2], x[3]);
+	}
+	for (int c = gl; 16 * c < tl; c += GW) {
+		uint32_t x[4];
+#pragma unroll
+		for (int h = 0; h < 2; ++h) {
+			const int i0 = 16 * c + 8 * h, ic = min(i0, tl - 1);            // (a window wholly behind the target: loaded from the last base, kept out below)
+			uint32_t v = left ? d_nibrev8(d_ref8(S4, (int64_t)toff - ic - 7)) : d_ref8(S4, (int64_t)toff + ic);
+			v = d_nibkeep(v, tl - i0);
+			x[2 * h] = d_nib4(v); x[2 * h + 1] = d_nib4(v >> 16);
+		}
+		t16[c] = make_uint4(x[0], x[1], x[2], x[3]);
+	}
+}
 
 // DP jobs of one block-count class: 4 jobs per wavefront, all running d_ksw_reg<NB>
 #ifndef AL_WPE_DP
@@ -2234,6 +2323,9 @@ k_ext_dp(const uint32_t *__restrict__ rd_seq, const uint64_t *__restrict__ rd_of
 	const int bw = (int)(P.bw * 1.5 + 1.);
 	// jobs are handed out largest first from a shared cursor, four neighbours of the size-sorted list per wavefront:
 	// the grid is as large as the chip holds resident and no wavefront is left with a long tail
+	if constexpr (PK) {   // the front pad's selector bytes (base 0) once: no job writes there, its words are read and unused
+		for (int c = gl; 16 * c < TMAXJ; c += GW) { reinterpret_cast<uint4 *>(L.sq)[c] = make_uint4(0u, 0u, 0u, 0u); reinterpret_cast<uint4 *>(L.selO)[c] = make_uint4(0x04040404u, 0x04040404u, 0x04040404u, 0x04040404u); }
+	}
 	unsigned long long *cursor = E.hist + 12 + (NB == 1 ? 0 : NB == 2 ? 1 : NB == 4 ? 2 : NB == 8 ? 3 : NB == 22 ? 4 : NB == 32 ? 5 : NB == 12 ? 6 : 7);
 	for (;;) {
 		unsigned long long base = 0;
@@ -2246,33 +2338,20 @@ k_ext_dp(const uint32_t *__restrict__ rd_seq, const uint64_t *__restrict__ rd_of
 		const ExtJob job = E.jobs[j];
 		const int ql = job.qlen, tl = job.tlen;
 		const uint32_t *seq = rd_seq + rd_off[job.read]; const int rqlen = (int)rd_len[job.read];
-		// the query goes in reversed (ksw2_extd2_sse.c:118: qr[t] = query[qlen - 1 - t]) behind the front pad, zeros after it
-		uint8_t *const qr = L.sq + TMAXJ;
-		if (job.kind == 0) {                                                  // left: both reversed (mm_seq_rev, align.c:694-695): query[i] = Q(qoff - i)
-			const ReadAcc Q{seq, rqlen, job.rev, 0};
-			for (int t = gl; t < ql + TMAXJ + 16; t += GW) qr[t] = t < ql ? (uint8_t)Q((int)job.qoff - (ql - 1 - t)) : 0;
-			for (int i = gl; i < tl; i += GW) L.tbuf[i] = (uint8_t)d_seq4(G.S4, job.toff - (uint64_t)i);
-		} else {
-			const ReadAcc Q{seq, rqlen, job.rev, (int)job.qoff};
-			for (int t = gl; t < ql + TMAXJ + 16; t += GW) qr[t] = t < ql ? (uint8_t)Q(ql - 1 - t) : 0;
-			for (int i = gl; i < tl; i += GW) L.tbuf[i] = (uint8_t)d_seq4(G.S4, job.toff + (uint64_t)i);
-		}
+		d_stage_job<PK, TMAXJ>(L, gl, seq, rqlen, G.S4, ql, tl, (int)job.qoff, job.toff, job.rev, job.kind == 0);
 		GSYNC();
 		EzD ez; d_ez_reset(ez);
 		const int flag = job.kind == 0 ? (EZ_EXTZ_ONLY | EZ_RIGHT | EZ_REV_CIGAR) : EZ_EXTZ_ONLY;
 		static_assert(TMAXJ == 16 * NB, "the query pad of JobLds is one block row");
 		if constexpr (PK) {
 			static_assert(NB % 2 == 0, "two blocks per superblock");
-			// selector words of the score permute, from the staged bytes (front pad included: whatever it holds, its words are in bounds and unused)
-			for (int i = gl; i < ql + 2 * TMAXJ + 16; i += GW) { const uint32_t b0 = L.sq[i]; L.selO[i] = (uint8_t)(b0 < 4 ? 4u + b0 : 0x0du); L.sq[i] = (uint8_t)(b0 < 4 ? b0 : 0x0du); }
-			GSYNC();
 			// the job list is ordered by direction inside a block count (k_ext_prep's key): nearly every wavefront holds jobs of one direction and takes the form compiled for it
 			const unsigned long long w_act = __ballot(1), w_right = __ballot((flag & EZ_RIGHT) != 0);
 			unsigned long long *const xcnt = ((P.dbg2 >> 5) & 1) ? G.counters + 24 : nullptr;   // AL_DBG2 bit 5: the early exit in shadow mode
-			// (the early exit from 12 target blocks up: on the 8-block class its bookkeeping cost more than the rows it saved)
-			if (w_right == 0) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 0, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
-			else if (w_right == w_act) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 1, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
-			else d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 2, (NB >= 12)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
+			// (the early exit: from 12 target blocks up as DESIGN.md §4 states it, on the 8-block class in the form that keeps zdropped exact)
+			if (w_right == 0) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 0, (NB >= 12 ? 1 : NB >= 8 ? 2 : 0)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
+			else if (w_right == w_act) d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 1, (NB >= 12 ? 1 : NB >= 8 ? 2 : 0)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
+			else d_ksw_pk<NB / 2, JobLds<QMAXJ, TMAXJ, PK>, 2, (NB >= 12 ? 1 : NB >= 8 ? 2 : 0)>(L, L.sq + TMAXJ, L.selO + TMAXJ, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez, true, xcnt);
 		} else
 		d_ksw_reg<NB>(L, gl, ws, ql, tl, P, bw, P.zdrop, P.end_bonus, flag, ez);
 		ExtOut o;

@@ -458,6 +458,8 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 	{ const char *d = getenv("AL_DBG"); P.dbg = d ? atoi(d) : 0; if (P.dbg) fprintf(stderr, "[airlift] AL_DBG=%d: timing experiment, results are NOT valid\n", P.dbg); }
 	{ const char *d = getenv("AL_DBG2"); P.dbg2 = d ? atoi(d) : 0; if (P.dbg2 & ~32) fprintf(stderr, "[airlift] AL_DBG2=%d: timing experiment, results are NOT valid\n", P.dbg2); }
 	{ const char *d = getenv("AL_DP_EXIT"); P.dp_exit = d ? atoi(d) != 0 : 1; }
+	{ const char *d = getenv("AL_DP_EXIT_STRIDE"); const int v = d ? atoi(d) : 8; const bool ok = v == 1 || v == 2 || v == 4 || v == 8; P.dp_exit_stride = ok ? v : 8;
+	  if (!ok) fprintf(stderr, "[airlift] AL_DP_EXIT_STRIDE=%s is not 1, 2, 4 or 8: using 8\n", d); }
 	memset(&c->stat, 0, sizeof(c->stat));
 	return c;
 }
