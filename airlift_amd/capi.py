@@ -131,6 +131,8 @@ def load():
     L.al_write_sam.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, cs, cs, ci, ci, ci, C.POINTER(ci), C.POINTER(C.POINTER(Reg)), cs, ci]; L.al_write_sam.restype = ci
     L.al_write_paf.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, C.POINTER(Reg), C.c_int64, ci, cs]; L.al_write_paf.restype = ci
     L.al_dbg_paf_selftest.argtypes = [C.c_uint64, ci]; L.al_dbg_paf_selftest.restype = ci
+    L.al_dbg_bam_selftest.argtypes = [C.c_uint64, ci]; L.al_dbg_bam_selftest.restype = ci
+    L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci

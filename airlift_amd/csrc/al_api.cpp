@@ -545,3 +545,150 @@ extern "C" int al_dbg_paf_selftest(uint64_t seed, int n_frag)
 	}
 	return bad;
 }
+
+// The BAM twin: the device formatter of al_dev_bam.h compiled for the CPU against al_write_bam_rec (al_bam.cpp) on random fragments -- hits with inline and
+// arena CIGARs, supplementary and secondary records, flipped mates, unmapped reads with and without a mapped mate, -Y, MD / cs, a read group, reads of
+// 1 .. 4 bases and of odd and even lengths, reads without quality, IUPAC codes, lowercase, U and bytes >= 128 in SEQ.  Every record's bytes, the length
+// pass, and for a third of the fragments the coordinate-sorted form (unmapped records left out, keys).  Returns the number of differences.
+#include "al_bam.h"
+#include "al_dev_bam.h"
+namespace {
+struct HostBamSink {
+	const AlSamCfg *C; const char *text; std::string out; size_t rec0 = 0; uint32_t bad_name = 0;
+	std::vector<uint64_t> keys; std::vector<uint32_t> off, len;
+	char peek(uint32_t o) const { return text[o]; }
+	void name_too_long() { ++bad_name; }
+	void begin_record() { rec0 = out.size(); }
+	void end_record(uint64_t key) { const uint32_t bs = (uint32_t)(out.size() - rec0) - 4; for (int i = 0; i < 4; ++i) out[rec0 + i] = (char)(bs >> (8 * i)); keys.push_back(key); off.push_back((uint32_t)rec0); len.push_back(bs + 4); }
+	void u8(uint8_t x) { out.push_back((char)x); }
+	void u16(uint16_t x) { out.push_back((char)x); out.push_back((char)(x >> 8)); }
+	void u32(uint32_t x) { for (int i = 0; i < 4; ++i) out.push_back((char)(x >> (8 * i))); }
+	void ch(char c) { out.push_back(c); }
+	void num(long long v) { out += std::to_string(v); }
+	void txt(uint32_t o, uint32_t l) { out.append(text + o, l); }
+	void mem(const char *s, int l) { out.append(s, (size_t)l); }
+	void cname(int rid) { out.append(C->names + C->name_off[rid], C->name_off[rid + 1] - C->name_off[rid]); }
+	uint8_t base(uint32_t o, int l, int rev, int i) const
+	{   // what k_bam_bulk does with base i of the field
+		const unsigned char *ct = al_comp();
+		unsigned char c = (unsigned char)text[o + (uint32_t)(rev ? l - 1 - i : i)];
+		if (c == 'u' || c == 'U') --c;
+		if (rev && c < 128) c = ct[c];
+		return al_bam_code16(c);
+	}
+	void seq4(uint32_t o, int l, int rev) { for (int i = 0; i < l; i += 2) out.push_back((char)(base(o, l, rev, i) << 4 | (i + 1 < l ? base(o, l, rev, i + 1) : 0))); }
+	void qual(uint32_t o, int l, int rev) { for (int i = 0; i < l; ++i) out.push_back((char)((unsigned char)text[o + (uint32_t)(rev ? l - 1 - i : i)] - 33)); }
+	void fill(uint8_t b, int l) { if (l > 0) out.append((size_t)l, (char)b); }
+	const uint64_t *tag_off = nullptr; const char *tag_txt = nullptr;
+	void tag(uint64_t k) { out.append(tag_txt + tag_off[k], tag_off[k + 1] - tag_off[k]); }
+};
+}
+extern "C" uint32_t al_dbg_bam_de_bits(uint64_t q) { const float f = al_bam_de(false, q); uint32_t u; memcpy(&u, &f, 4); return u; }
+
+extern "C" int al_dbg_bam_selftest(uint64_t seed, int n_frag)
+{
+	int bad = 0;
+	Rng R{seed * 2654435761ULL + 88172645463325252ULL};
+	// (1) the 4-bit code table against the host writer's: every byte, through a one-base record below; here the function's own contract
+	{ const char *c16 = "=ACMGRSVTWYHKDBN"; for (int c = 0; c < 256; ++c) { int e = 15; for (int i = 0; i < 16; ++i) if (c == c16[i] || (c16[i] != '=' && c == (c16[i] | 0x20))) e = i; if (al_bam_code16((uint8_t)c) != e) ++bad; } }
+	al_idx_t mi; const char *cn[3] = {"chr1", "contig_two", "c"};
+	for (int i = 0; i < 3; ++i) { AlSeq s; s.name = cn[i]; s.offset = 0; s.len = 300000000; mi.seq.push_back(s); }
+	std::string names; std::vector<uint32_t> noff; for (int i = 0; i < 3; ++i) { noff.push_back((uint32_t)names.size()); names += cn[i]; } noff.push_back((uint32_t)names.size());
+	const char bases[] = "ACGTNUacgtunRYSWKMBDHVrykm=.*-X\x80\xc1\xff";
+	const uint32_t n_bases = (uint32_t)sizeof(bases) - 1;
+	for (int f = 0; f < n_frag && bad < 20; ++f) {
+		const int n_seg = 1 + (int)R.below(2), rep_len = (int)R.below(3) == 0 ? -1 : (int)R.below(200);
+		const bool with_qual = R.below(5) != 0; const bool with_rg = R.below(2) != 0; const int sorted = R.below(3) == 0 ? 1 : 0;
+		const bool plain = R.below(3) != 0;                          // most reads: A C G T N only
+		std::string text; AlSamRead rd[2]; std::vector<AlReg> regs[2]; std::vector<uint32_t> arena; std::string nm[2];
+		for (int j = 0; j < n_seg; ++j) {
+			const int L = R.below(8) == 0 ? 1 + (int)R.below(4) : 30 + (int)R.below(221);
+			nm[j] = "read" + std::to_string(f) + (R.below(3) == 0 ? "/" + std::to_string(j + 1) : std::string());
+			if (R.below(300) == 0) nm[j] = std::string(250 + R.below(8), 'n') + (R.below(2) ? "/1" : "");    // around the 254 bytes l_read_name can hold
+			rd[j].name = (uint32_t)text.size(); rd[j].name_len = (uint32_t)nm[j].size(); text += nm[j]; text.push_back('\n');
+			rd[j].seq = (uint32_t)text.size(); for (int i = 0; i < L; ++i) text.push_back(bases[R.below(plain ? 5u : n_bases)]); text.push_back('\n');
+			rd[j].qual = ~0u; if (with_qual) { rd[j].qual = (uint32_t)text.size(); for (int i = 0; i < L; ++i) text.push_back((char)(33 + R.below(94))); text.push_back('\n'); }
+			rd[j].qlen = L; rd[j].flip = n_seg == 2 && j == 1 ? 1 : (int)R.below(4) == 0;
+			const int n = (int)R.below(5) == 0 ? 0 : 1 + (int)R.below(4);
+			int pri = n ? (int)R.below((uint32_t)n + 1) : 0;          // == n: no sam_pri record at all
+			for (int k = 0; k < n; ++k) {
+				AlReg r; memset(&r, 0, sizeof(r));
+				r.id = k; r.parent = R.below(3) == 0 && k > 0 ? (int)R.below((uint32_t)k) : k; r.rid = (int)R.below(3); r.cnt = 1 + (int)R.below(30); r.score = (int)R.below(300);
+				r.qs = (int)R.below((uint32_t)std::max(1, L / 2)); r.qe = r.qs + 1 + (int)R.below((uint32_t)(L - r.qs));
+				r.rs = R.below(4) == 0 ? (int)R.below(1 << 14) * (int)(1u << R.below(15)) + (int)R.below(3) - 1 : (int)R.below(250000000);   // (positions next to the bin boundaries of reg2bin)
+				if (r.rs < 0) r.rs = 0;
+				r.re = r.rs + (r.qe - r.qs) + (int)R.below(7) - 3; if (r.re <= r.rs) r.re = r.rs + 1;
+				r.subsc = (int)R.below(200); r.mlen = (int)R.below(200); r.blen = r.mlen + (int)R.below(30); r.n_sub = (int)R.below(4); r.mapq = R.below(61); r.hash = (uint32_t)R.next();
+				r.dp_score = (int)R.below(300); r.dp_max = (int)R.below(300); r.dp_max2 = (int)R.below(300); r.n_ambi = R.below(3);
+				r.flags = R.below(4) == 0 ? R.below(4) : 0;               // split
+				if (R.below(2)) r.flags |= ALR_REV; if (k == pri && r.parent == r.id) r.flags |= ALR_SAM_PRI; if (R.below(2)) r.flags |= ALR_PROPER;
+				if (R.below(8) != 0) {
+					r.flags |= ALR_HAS_P; r.n_cigar = 1 + R.below(R.below(4) == 0 ? 9u : 3u);
+					uint32_t *cg;
+					if (r.n_cigar <= 4) { r.cigar_off = AL_CIG_INLINE; cg = r.cig_inl; } else { r.cigar_off = (uint32_t)arena.size(); arena.resize(arena.size() + r.n_cigar); cg = arena.data() + r.cigar_off; }
+					int bl = 0, ml = 0;
+					for (uint32_t i = 0; i < r.n_cigar; ++i) { cg[i] = (1 + R.below(R.below(6) == 0 ? 70000u : 120u)) << 4 | (i % 2 == 0 ? (R.below(4) == 0 ? 7u + R.below(2) : 0u) : 1u + R.below(3)); bl += (int)(cg[i] >> 4); const uint32_t op = cg[i] & 0xf; if (op == 0 || op == 7 || op == 8) ml += (int)(cg[i] >> 4); }
+					r.blen = bl; r.mlen = R.below(6) == 0 ? ml : (int)R.below((uint32_t)ml + 1);      // (mlen == the matched columns and no gap: de:f is 0)
+				}
+				regs[j].push_back(r);
+			}
+		}
+		for (int j = 0; j < n_seg; ++j) { rd[j].regs = regs[j].data(); rd[j].n_regs = (int)regs[j].size(); rd[j].arena = arena.data(); }
+		al_mapopt_t mo; memset(&mo, 0, sizeof(mo)); if (R.below(2)) mo.flag |= AL_F_NO_PRINT_2ND; if (R.below(3) == 0) mo.flag |= AL_F_SAM_HIT_ONLY;
+		AlSamCfg C; C.names = names.data(); C.name_off = noff.data(); C.rg_id = "grp1"; C.rg_len = with_rg ? 4 : 0; C.no_print_2nd = (mo.flag & AL_F_NO_PRINT_2ND) ? 1 : 0; C.hit_only = (mo.flag & AL_F_SAM_HIT_ONLY) ? 1 : 0; C.pe_ori = 1;
+		if (R.below(2)) { const uint32_t o = 1 + R.below(5); if (o & 1) mo.flag |= AL_F_SOFTCLIP; if (o >= 2) mo.flag |= o >= 4 ? AL_F_OUT_MD : AL_F_OUT_CS; }
+		C.softclip = (mo.flag & AL_F_SOFTCLIP) ? 1 : 0; C.tag_kind = al_tag_kind(mo.flag);
+		std::string tags[2]; std::vector<uint64_t> tag_off[2];
+		for (int j = 0; j < n_seg; ++j) {
+			tag_off[j].push_back(0);
+			for (size_t k = 0; k < regs[j].size(); ++k) { const int l = (int)R.below(R.below(4) == 0 ? 90u : 30u); for (int i = 0; i < l; ++i) tags[j].push_back("0123456789ACGT^*:=+-acgt"[R.below(24)]); tag_off[j].push_back(tags[j].size()); }
+		}
+		// the host records al_write_bam_rec takes: AlReg -> al_reg1_t with the un-flip of al_reg_from_raw
+		std::vector<al_reg1_t> hr[2]; int n_regss[2] = {0, 0}; const al_reg1_t *regss[2] = {nullptr, nullptr};
+		for (int j = 0; j < n_seg; ++j) {
+			for (const AlReg &r : regs[j]) {
+				al_reg1_t q; memset(&q, 0, sizeof(q));
+				q.id = r.id; q.cnt = r.cnt; q.rid = r.rid; q.score = r.score; q.qs = r.qs; q.qe = r.qe; q.rs = r.rs; q.re = r.re; q.parent = r.parent; q.subsc = r.subsc; q.mlen = r.mlen; q.blen = r.blen; q.n_sub = r.n_sub;
+				q.mapq = r.mapq & 0xff; q.split = r.flags & 3; q.rev = (r.flags & ALR_REV) ? 1 : 0; q.sam_pri = (r.flags & ALR_SAM_PRI) ? 1 : 0; q.proper_frag = (r.flags & ALR_PROPER) ? 1 : 0; q.hash = r.hash;
+				q.dp_score = r.dp_score; q.dp_max = r.dp_max; q.dp_max2 = r.dp_max2; q.n_ambi = r.n_ambi; q.n_cigar = (r.flags & ALR_HAS_P) ? r.n_cigar : 0;
+				q.cigar = q.n_cigar ? const_cast<uint32_t *>(r.cigar_off == AL_CIG_INLINE ? r.cig_inl : arena.data() + r.cigar_off) : nullptr;
+				if (rd[j].flip) { const int t = q.qs; q.qs = rd[j].qlen - q.qe; q.qe = rd[j].qlen - t; q.rev = !q.rev; }
+				hr[j].push_back(q);
+			}
+			n_regss[j] = (int)hr[j].size(); regss[j] = hr[j].data();
+		}
+		const int64_t ofl = mo.flag & (AL_F_SOFTCLIP | AL_F_OUT_MD | AL_F_OUT_CS | AL_F_OUT_CS_LONG);
+		for (int j = 0; j < n_seg; ++j) {
+			std::vector<char> exp; std::vector<uint64_t> ekeys; std::vector<uint32_t> eoff, elen; int ebad = 0;
+			std::string seq(text.data() + rd[j].seq, (size_t)rd[j].qlen); for (char &c : seq) if (c == 'u' || c == 'U') --c;       // what the host parsers hand over (bseq.c:72-74)
+			std::string qual; if (with_qual) qual.assign(text.data() + rd[j].qual, (size_t)rd[j].qlen);
+			auto emit = [&](int k) {   // as write_batch (al_pipeline.cpp) calls the host writer
+				uint64_t key = 0; int unm = 0; const size_t at = exp.size();
+				const int l = al_write_bam_rec(exp, &mi, nm[j].c_str(), rd[j].qlen, seq.c_str(), with_qual ? qual.c_str() : nullptr, j, k, n_seg, n_regss, regss, with_rg ? "grp1" : "", rep_len, &key, &unm, ofl,
+				                               k >= 0 && C.tag_kind ? tags[j].data() + tag_off[j][k] : nullptr, k >= 0 && C.tag_kind ? (int)(tag_off[j][k + 1] - tag_off[j][k]) : 0);
+				if (l < 0) { ++ebad; return; }
+				if (sorted && unm) { exp.resize(at); return; }
+				ekeys.push_back(key); eoff.push_back((uint32_t)at); elen.push_back((uint32_t)l);
+			};
+			if (n_regss[j] > 0) { for (int k = 0; k < n_regss[j]; ++k) { if ((mo.flag & AL_F_NO_PRINT_2ND) && hr[j][k].id != hr[j][k].parent) continue; emit(k); } }
+			else if (!(mo.flag & AL_F_SAM_HIT_ONLY)) emit(-1);
+			C.tag_reg0 = rd[j].regs;
+			HostBamSink o; o.C = &C; o.text = text.data(); o.tag_off = tag_off[j].data(); o.tag_txt = tags[j].data();
+			AlBamCountSink cnt; cnt.C = &C; cnt.text = text.data(); cnt.tag_off = tag_off[j].data();
+			const int n1 = al_bam_read_records(o, C, rd[j], n_seg == 2 ? &rd[1 - j] : nullptr, j, n_seg, rep_len, sorted);
+			const int n2 = al_bam_read_records(cnt, C, rd[j], n_seg == 2 ? &rd[1 - j] : nullptr, j, n_seg, rep_len, sorted);
+			if ((ebad != 0) != (cnt.bad_name != 0) || (ebad != 0) != (o.bad_name != 0)) { if (bad < 2) fprintf(stderr, "[airlift] bam selftest: fragment %d read %d: the host writer refuses %d names, the formatter %u\n", f, j, ebad, cnt.bad_name); ++bad; continue; }
+			if (ebad) continue;                                  // (the run fails there: nothing of it is compared)
+			const bool same = o.out.size() == exp.size() && (exp.empty() || memcmp(o.out.data(), exp.data(), exp.size()) == 0);
+			if (!same || cnt.n != exp.size() || n1 != (int)ekeys.size() || n2 != n1 || o.keys != ekeys || o.off != eoff || o.len != elen) {
+				if (bad < 3) {
+					size_t d = 0; while (d < exp.size() && d < o.out.size() && exp[d] == o.out[d]) ++d;
+					fprintf(stderr, "[airlift] bam selftest: fragment %d read %d differs: host %zu bytes in %zu records, formatter %zu bytes in %d records (counted %llu in %d), first difference at byte %zu%s\n",
+					        f, j, exp.size(), ekeys.size(), o.out.size(), n1, (unsigned long long)cnt.n, n2, d, o.keys != ekeys ? "; keys differ" : "");
+				}
+				++bad;
+			}
+		}
+	}
+	return bad;
+}

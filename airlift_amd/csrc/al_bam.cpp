@@ -8,6 +8,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <zlib.h>
+#include <chrono>
 #include <string>
 #include <thread>
 #include <vector>
@@ -201,6 +202,7 @@ static int bgzf_block(const char *src, size_t n, int level, std::vector<unsigned
 	return 0;
 }
 
+static inline double bgzf_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 int AlBgzf::write(const char *p, size_t n)
 {
 	while (n) {
@@ -215,7 +217,9 @@ int AlBgzf::flush_full()
 	const size_t nb = buf.size() / BGZF_IN;
 	if (nb == 0) return 0;
 	std::vector<std::vector<unsigned char>> blk(nb); std::vector<int> bad(n_threads > 1 ? n_threads : 1, 0);
+	const double t0 = bgzf_now();
 	al_parallel_for(n_threads, nb, [&](size_t lo, size_t hi, int t) { for (size_t b = lo; b < hi; ++b) if (bgzf_block(buf.data() + b * BGZF_IN, BGZF_IN, level, blk[b])) bad[t] = 1; });
+	t_deflate += bgzf_now() - t0;
 	for (int b : bad) if (b) return -1;
 	for (size_t b = 0; b < nb; ++b) if (fwrite(blk[b].data(), 1, blk[b].size(), out) != blk[b].size()) return -1;
 	buf.erase(buf.begin(), buf.begin() + nb * BGZF_IN);

@@ -9,6 +9,7 @@
 struct AlBgzf {                 // BGZF stream: bytes in, 64 KB blocks deflated on n_threads workers, written in order
 	FILE *out; int level, n_threads;
 	std::vector<char> buf; size_t cap;
+	double t_deflate = 0;        // seconds spent compressing (wall time of the worker rounds), for the drivers' AL_TIMING lines
 	AlBgzf(FILE *o, int lvl, int nt) : out(o), level(lvl), n_threads(nt > 1 ? nt : 1), cap((size_t)0xff00 * 64 * (size_t)(nt > 1 ? nt : 1)) { buf.reserve(cap); }
 	int write(const char *p, size_t n);
 	int finish();                // flushes the tail and appends the EOF block

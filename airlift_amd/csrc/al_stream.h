@@ -50,6 +50,7 @@ struct AlStreamSlot {
 	// output
 	DevBuf<char> names; DevBuf<uint32_t> name_off; DevBuf<char> rg;
 	DevBuf<uint32_t> sam_len, sam_nrec; DevBuf<uint64_t> sam_off, rec_off; DevBuf<AlBulk> bulk; DevBuf<char> sam;
+	DevBuf<uint64_t> bam_key; DevBuf<uint32_t> bam_roff, bam_rlen;   // --sorted-bam: sort key, offset and length of every record of the batch
 	uint64_t sam_bytes = 0, sam_records = 0;
 	bool cfg_ready = false; int rg_len = 0;
 	void release();
@@ -72,7 +73,11 @@ int  al_stream_setup(AlStreamSlot &S, al_ctx_t *c, uint32_t rec_lo, uint32_t rec
 int  al_stream_frag_starts(AlStreamSlot &S, const AlIngestResult &res, std::vector<uint32_t> &first);
 // SAM text of the batch context c has mapped (after al_batch_run) into S.sam (device): kernels on c's stream; the slot's stream is made
 // to wait for them and the call returns (c is free for its next batch); sets sam_bytes / sam_records.
-int  al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id);
+// bam: 0 SAM (or PAF) text; 1 BAM records in input order; 2 mapped BAM records with {key, offset, length} per record for the coordinate sort.
+// A read name BAM cannot store: the host writer's message, -3, nothing of the batch is made.
+int  al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id, int bam = 0);
+// (bam == 2) the batch's sam_records sort keys refID << 32 | pos, offsets into the batch's bytes and lengths, to host arrays; blocks
+int  al_stream_bam_index_fetch(AlStreamSlot &S, uint64_t *key, uint32_t *off, uint32_t *len);
 // bytes [off, off + n) of the text to a page-locked host buffer, on the slot's stream; `done` is recorded behind the copy
 int  al_stream_sam_fetch(AlStreamSlot &S, uint64_t off, uint64_t n, char *dst, hipEvent_t done);
 

@@ -9,6 +9,7 @@
 //   k_sam_len                lane per read: bytes and records of its SAM text (al_dev_sam.h, counting sink)
 //   k_sam_write              lane per read: every field but SEQ / QUAL, which are left as copy descriptors
 //   k_sam_bulk               wavefront per descriptor: SEQ / QUAL bytes, reversed / complemented as the record needs
+//   k_bam_len / k_bam_write / k_bam_bulk   the same three over the BAM record (al_dev_bam.h): --bam and --sorted-bam, which deflate on the host
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -25,6 +26,7 @@
 #include "al_stream.h"
 #include "al_dev_sam.h"
 #include "al_dev_paf.h"
+#include "al_dev_bam.h"
 
 #define NL_TILE 4096
 
@@ -310,6 +312,122 @@ k_sam_bulk(const AlBulk *__restrict__ bulk, uint64_t n_desc, const char *__restr
 	}
 }
 
+// ---- BAM records (al_dev_bam.h): the frame of the SAM text -- a lane per read counts, the scans place every read and every record, a lane per read
+// writes all but SEQ / QUAL (and a long tag value), which go through the bulk table.  sorted: the unmapped records are left out and every record
+// leaves {key, offset, length} for the coordinate sort, indexed by its number.
+__global__ void __launch_bounds__(256)
+k_bam_len(SamIn I, int sorted, uint32_t *__restrict__ sam_len, uint32_t *__restrict__ sam_nrec, unsigned long long *__restrict__ st)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i > I.n_reads) return;
+	if (i == I.n_reads) { sam_len[i] = 0; sam_nrec[i] = 0; return; }
+	const uint32_t info = I.rd_info[i];
+	const AlSamRead me = d_sam_read(I, i);
+	AlSamRead mt; const bool paired = (info & AL_RI_PAIRED) != 0;
+	if (paired) mt = d_sam_read(I, (info & AL_RI_SEG1) ? i - 1 : i + 1);
+	AlBamCountSink o; o.C = &I.C; o.text = (I.two_files && (info & AL_RI_SEG1)) ? I.t1 : I.t0; o.tag_off = I.tag_off;
+	const int n = al_bam_read_records(o, I.C, me, paired ? &mt : nullptr, (info & AL_RI_SEG1) ? 1 : 0, paired ? 2 : 1, I.frag_rep[I.rd_frag[i]], sorted);
+	sam_len[i] = (uint32_t)o.n; sam_nrec[i] = (uint32_t)n;
+	if (o.bad_name) { atomicAdd(st + 8, 1ULL); atomicMin(st + 9, (unsigned long long)i); }   // a name of more than 254 bytes: the driver fails the run
+}
+struct BamWriteSink {
+	const AlSamCfg *C; const char *text; char *p, *base, *rec0; AlBulk *bulk, *next; uint32_t file; int slot, n_slot; const uint64_t *tag_off; const char *tag_txt;
+	uint64_t rec; uint64_t *rkey; uint32_t *roff, *rlen;          // sorted: this record's number and the three arrays
+	__device__ __forceinline__ char peek(uint32_t off) const { return text[off]; }
+	__device__ __forceinline__ void name_too_long() {}            // (counted by k_bam_len: the driver does not get here)
+	__device__ __forceinline__ void begin_record() { bulk = next; next += n_slot; slot = 0; rec0 = p; }
+	__device__ __forceinline__ void end_record(uint64_t key)
+	{
+		const uint32_t bs = (uint32_t)(p - rec0) - 4;
+		rec0[0] = (char)bs; rec0[1] = (char)(bs >> 8); rec0[2] = (char)(bs >> 16); rec0[3] = (char)(bs >> 24);
+		if (rkey) { rkey[rec] = key; roff[rec] = (uint32_t)(rec0 - base); rlen[rec] = bs + 4; }
+		++rec;
+	}
+	__device__ __forceinline__ void u8(uint8_t x) { *p++ = (char)x; }
+	__device__ __forceinline__ void u16(uint16_t x) { p[0] = (char)x; p[1] = (char)(x >> 8); p += 2; }
+	__device__ __forceinline__ void u32(uint32_t x) { p[0] = (char)x; p[1] = (char)(x >> 8); p[2] = (char)(x >> 16); p[3] = (char)(x >> 24); p += 4; }
+	__device__ __forceinline__ void ch(char c) { *p++ = c; }
+	__device__ __forceinline__ void num(long long v)
+	{
+		unsigned long long x = v < 0 ? 0ULL - (unsigned long long)v : (unsigned long long)v;
+		const int l = al_num_len(v); char *e = p + l;
+		do { *--e = (char)('0' + (int)(x % 10)); x /= 10; } while (x);
+		if (v < 0) *--e = '-';
+		p += l;
+	}
+	__device__ __forceinline__ void txt(uint32_t off, uint32_t len) { for (uint32_t i = 0; i < len; ++i) p[i] = text[off + i]; p += len; }
+	__device__ __forceinline__ void mem(const char *s, int len) { for (int i = 0; i < len; ++i) p[i] = s[i]; p += len; }
+	__device__ __forceinline__ void cname(int rid) { const uint32_t a = C->name_off[rid], b = C->name_off[rid + 1]; for (uint32_t i = a; i < b; ++i) *p++ = C->names[i]; }
+	__device__ __forceinline__ void seq4(uint32_t off, int len, int rev)
+	{   // len bases -> (len + 1) / 2 bytes, by k_bam_bulk
+		if (len <= 0) return;
+		bulk[slot] = AlBulk{(uint64_t)(p - base), off, (uint32_t)len | file << 27 | 1u << 28 | (rev ? 1u << 29 | 1u << 30 : 0u)};
+		++slot; p += (len + 1) / 2;
+	}
+	__device__ __forceinline__ void qual(uint32_t off, int len, int rev)
+	{
+		if (len <= 0) return;
+		bulk[slot] = AlBulk{(uint64_t)(p - base), off, (uint32_t)len | file << 27 | (rev ? 1u << 30 : 0u)};
+		++slot; p += len;
+	}
+	__device__ __forceinline__ void fill(uint8_t b, int len) { for (int i = 0; i < len; ++i) p[i] = (char)b; if (len > 0) p += len; }   // (a read without quality: not in FASTQ input)
+	__device__ __forceinline__ void tag(uint64_t k)
+	{   // the record's MD:Z / cs:Z value: a short one copied here, a long one by k_bam_bulk (bit 31)
+		const uint64_t a = tag_off[k], len = tag_off[k + 1] - a;
+		if (len == 0) return;
+		if (len <= 32) { for (uint32_t j = 0; j < (uint32_t)len; ++j) p[j] = tag_txt[a + j]; p += len; return; }
+		bulk[slot] = AlBulk{(uint64_t)(p - base), (uint32_t)a, (uint32_t)len | 1u << 31};
+		++slot; p += len;
+	}
+};
+__global__ void __launch_bounds__(256)
+k_bam_write(SamIn I, int sorted, const uint64_t *__restrict__ sam_off, const uint64_t *__restrict__ rec_off, char *__restrict__ sam, AlBulk *__restrict__ bulk,
+            uint64_t *__restrict__ rkey, uint32_t *__restrict__ roff, uint32_t *__restrict__ rlen)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i >= I.n_reads) return;
+	if (sam_off[i + 1] == sam_off[i]) return;                          // (a read without records)
+	const uint32_t info = I.rd_info[i];
+	const AlSamRead me = d_sam_read(I, i);
+	AlSamRead mt; const bool paired = (info & AL_RI_PAIRED) != 0;
+	if (paired) mt = d_sam_read(I, (info & AL_RI_SEG1) ? i - 1 : i + 1);
+	const uint32_t file = (I.two_files && (info & AL_RI_SEG1)) ? 1u : 0u;
+	BamWriteSink o; o.C = &I.C; o.text = file ? I.t1 : I.t0; o.base = sam; o.p = sam + sam_off[i]; o.rec0 = o.p; o.file = file;
+	o.n_slot = I.C.tag_kind ? 3 : 2; o.tag_off = I.tag_off; o.tag_txt = I.tag_txt;
+	o.rec = rec_off[i]; o.rkey = sorted ? rkey : nullptr; o.roff = roff; o.rlen = rlen;
+	o.next = bulk + (uint64_t)o.n_slot * rec_off[i]; o.bulk = o.next; o.slot = 0;
+	al_bam_read_records(o, I.C, me, paired ? &mt : nullptr, (info & AL_RI_SEG1) ? 1 : 0, paired ? 2 : 1, I.frag_rep[I.rd_frag[i]], sorted);
+}
+// SEQ, QUAL or a tag value of a BAM record: a wavefront per descriptor, one output byte per lane and step.  A SEQ byte is two bases: both loads are
+// issued whatever the length (the second index clamped into the field), the odd tail's low nibble is zeroed afterwards.
+// tabs: nt4 (256 bytes), complement (256), 4-bit codes (256).
+__global__ void __launch_bounds__(256)
+k_bam_bulk(const AlBulk *__restrict__ bulk, uint64_t n_desc, const char *__restrict__ t0, const char *__restrict__ t1, const uint8_t *__restrict__ tabs, char *__restrict__ sam, const char *__restrict__ tag)
+{
+	const uint64_t d = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); const uint32_t l = threadIdx.x & 63;
+	if (d >= n_desc) return;
+	const AlBulk b = bulk[d];
+	const uint32_t len = b.len_flags & 0x7ffffffu; if (len == 0) return;
+	char *o = sam + b.dst;
+	if (b.len_flags >> 31) { const char *s = tag + b.src; for (uint32_t j = l; j < len; j += 64) o[j] = s[j]; return; }
+	const char *s = ((b.len_flags >> 27 & 1u) ? t1 : t0) + b.src;
+	const bool is_seq = b.len_flags >> 28 & 1u, rev = b.len_flags >> 30 & 1u;
+	if (!is_seq) { for (uint32_t j = l; j < len; j += 64) o[j] = (char)((uint8_t)s[rev ? len - 1 - j : j] - 33); return; }
+	const uint8_t *ct = tabs + 256, *c16 = tabs + 512;
+	const uint32_t nb = (len + 1) / 2;
+	for (uint32_t j = l; j < nb; j += 64) {
+		const uint32_t i0 = 2 * j, i1 = 2 * j + 1; const bool has1 = i1 < len;
+		const uint32_t i1c = has1 ? i1 : i0;                               // (i0 < len: j < nb)
+		uint8_t a = (uint8_t)s[rev ? len - 1 - i0 : i0], c = (uint8_t)s[rev ? len - 1 - i1c : i1c];
+		if (a == 'u' || a == 'U') --a;
+		if (c == 'u' || c == 'U') --c;
+		const uint8_t ca = ct[a & 127], cc = ct[c & 127];                   // (bytes >= 128 stay as they are, as on the host)
+		if (rev) { if (a < 128) a = ca; if (c < 128) c = cc; }
+		const uint32_t hi = c16[a], lo = has1 ? c16[c] : 0u;
+		o[j] = (char)(hi << 4 | lo);
+	}
+}
+
 // ---- PAF text (al_dev_paf.h): the same two passes over the same frame -- a lane per read counts its lines' bytes, the scan gives every read
 // its offset, the second pass writes.  A line has no SEQ / QUAL, so there are no bulk descriptors: a tag value is copied by its record's lane.
 __global__ void __launch_bounds__(256)
@@ -367,7 +485,7 @@ void AlStreamSlot::release()
 	for (int i = 0; i < 2; ++i) { txt[i].release(); ls[i].release(); frec[i].release(); }
 	tile_cnt.release(); tile_off.release(); rtxt.release(); rd_info.release(); rd_frag.release(); rd_words.release(); rd_mcnt.release();
 	se_key.release(); se_run.release(); se_fs.release(); se_fidx.release(); st.release(); tabs.release(); scan_tmp.release();
-	names.release(); name_off.release(); rg.release(); sam_len.release(); sam_nrec.release(); sam_off.release(); rec_off.release(); bulk.release(); sam.release();
+	names.release(); name_off.release(); rg.release(); sam_len.release(); sam_nrec.release(); sam_off.release(); rec_off.release(); bulk.release(); sam.release(); bam_key.release(); bam_roff.release(); bam_rlen.release();
 }
 
 int al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_files)
@@ -377,9 +495,9 @@ int al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_f
 	AL_HIP_CHECK(hipStreamCreateWithFlags(&S.io, hipStreamNonBlocking));
 	AL_HIP_CHECK(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
 	for (int i = 0; i < 2; ++i) AL_HIP_CHECK(hipEventCreateWithFlags(&S.ev_out[i], hipEventDisableTiming));
-	if (S.tabs.ensure(512) || S.st.ensure(16)) return -1;
-	uint8_t h[512]; memcpy(h, al_nt4(), 256); memcpy(h + 256, al_comp(), 256);
-	AL_HIP_CHECK(hipMemcpy(S.tabs.p, h, 512, hipMemcpyHostToDevice));
+	if (S.tabs.ensure(768) || S.st.ensure(16)) return -1;
+	uint8_t h[768]; memcpy(h, al_nt4(), 256); memcpy(h + 256, al_comp(), 256); for (int i = 0; i < 256; ++i) h[512 + i] = al_bam_code16((uint8_t)i);
+	AL_HIP_CHECK(hipMemcpy(S.tabs.p, h, 768, hipMemcpyHostToDevice));
 	std::string names; std::vector<uint32_t> off(mi->seq.size() + 1);
 	for (size_t i = 0; i < mi->seq.size(); ++i) { off[i] = (uint32_t)names.size(); names += mi->seq[i].name; }
 	off[mi->seq.size()] = (uint32_t)names.size();
@@ -531,7 +649,7 @@ int al_stream_setup(AlStreamSlot &S, al_ctx_t *c, uint32_t rec_lo, uint32_t rec_
 	return 0;
 }
 
-int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id)
+int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id, int bam)
 {
 	hipStream_t s = c->stream;
 	AL_HIP_CHECK(hipSetDevice(c->device));
@@ -551,20 +669,42 @@ int al_stream_sam(AlStreamSlot &S, al_ctx_t *c, const char *rg_id)
 	I.C.names = S.names.p; I.C.name_off = S.name_off.p; I.C.rg_id = S.rg.p; I.C.rg_len = S.rg_len;
 	I.C.no_print_2nd = (c->opt.flag & AL_F_NO_PRINT_2ND) ? 1 : 0; I.C.hit_only = (c->opt.flag & AL_F_SAM_HIT_ONLY) ? 1 : 0; I.C.pe_ori = c->opt.pe_ori;
 	I.C.softclip = (c->opt.flag & AL_F_SOFTCLIP) ? 1 : 0; I.C.tag_kind = R.tag_kind; I.C.tag_reg0 = R.out; I.tag_off = R.tag_kind ? R.tag_off : nullptr; I.tag_txt = R.tag_kind ? R.tag : nullptr;
-	const bool paf = (c->opt.flag & AL_F_OUT_PAF) != 0;
+	const bool paf = !bam && (c->opt.flag & AL_F_OUT_PAF) != 0;
 	I.C.ctg_len = c->di.seq_len; I.C.out_cg = (c->opt.flag & AL_F_OUT_CG) ? 1 : 0; I.C.paf_no_hit = (c->opt.flag & AL_F_PAF_NO_HIT) ? 1 : 0;
 	const uint64_t n_slot = R.tag_kind ? 3 : 2;                      // bulk descriptors per record
 	if (S.sam_len.ensure((size_t)nr + 2) || S.sam_nrec.ensure((size_t)nr + 2) || S.sam_off.ensure((size_t)nr + 2) || S.rec_off.ensure((size_t)nr + 2)) return -1;
-	if (paf) hipLaunchKernelGGL(k_paf_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
+	if (bam) {
+		AL_HIP_CHECK(hipMemsetAsync(S.st.p + 8, 0, 8, s)); AL_HIP_CHECK(hipMemsetAsync(S.st.p + 9, 0xff, 8, s));
+		hipLaunchKernelGGL(k_bam_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, bam == 2 ? 1 : 0, S.sam_len.p, S.sam_nrec.p, S.st.p);
+	}
+	else if (paf) hipLaunchKernelGGL(k_paf_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
 	else hipLaunchKernelGGL(k_sam_len, dim3((nr + 256) / 256), dim3(256), 0, s, I, S.sam_len.p, S.sam_nrec.p);
 	if (scan_excl_u64(S, S.sam_len.p, S.sam_off.p, (size_t)nr + 1, s) || scan_excl_u64(S, S.sam_nrec.p, S.rec_off.p, (size_t)nr + 1, s)) return -1;
 	uint64_t tot[2] = {0, 0};
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[0], S.sam_off.p + nr, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipMemcpyAsync(&tot[1], S.rec_off.p + nr, 8, hipMemcpyDeviceToHost, s));
+	unsigned long long bad_name[2] = {0, ~0ULL};
+	if (bam) AL_HIP_CHECK(hipMemcpyAsync(bad_name, S.st.p + 8, 16, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
+	if (bad_name[0]) {   // the host writer's message (al_write_bam_rec), for the first such read of the batch; nothing of the batch is written
+		char nm[48]; memset(nm, 0, sizeof(nm));
+		AlRdText t; uint8_t info = 0;
+		AL_HIP_CHECK(hipMemcpy(&t, S.rtxt.p + bad_name[1], sizeof(t), hipMemcpyDeviceToHost)); AL_HIP_CHECK(hipMemcpy(&info, S.rd_info.p + bad_name[1], 1, hipMemcpyDeviceToHost));
+		AL_HIP_CHECK(hipMemcpy(nm, (I.two_files && (info & AL_RI_SEG1) ? I.t1 : I.t0) + t.name, std::min<uint32_t>(40u, t.name_len), hipMemcpyDeviceToHost));
+		fprintf(stderr, "[ERROR] airlift: read name longer than 254 characters cannot be stored in BAM: %.40s...\n", nm);
+		return -3;
+	}
+	if (bam == 2 && tot[0] >= (1ULL << 32)) { fprintf(stderr, "[airlift] --sorted-bam: the records of one batch exceed 4 GB: use a smaller -K\n"); return -1; }
+	if (bam == 2 && (S.bam_key.ensure(tot[1] + 2) || S.bam_roff.ensure(tot[1] + 2) || S.bam_rlen.ensure(tot[1] + 2))) return -1;
 	if (S.sam.ensure(tot[0] + 64) || (!paf && S.bulk.ensure(n_slot * tot[1] + 2))) return -1;
 	if (tot[1] && paf) {
 		hipLaunchKernelGGL(k_paf_write, dim3((nr + 255) / 256), dim3(256), 0, s, I, S.sam_off.p, S.sam.p);
+		AL_HIP_CHECK(hipEventRecord(S.ev, s));
+		AL_HIP_CHECK(hipStreamWaitEvent(S.io, S.ev, 0));
+	} else if (tot[1] && bam) {
+		AL_HIP_CHECK(hipMemsetAsync(S.bulk.p, 0, n_slot * tot[1] * sizeof(AlBulk), s));
+		hipLaunchKernelGGL(k_bam_write, dim3((nr + 255) / 256), dim3(256), 0, s, I, bam == 2 ? 1 : 0, S.sam_off.p, S.rec_off.p, S.sam.p, S.bulk.p, S.bam_key.p, S.bam_roff.p, S.bam_rlen.p);
+		hipLaunchKernelGGL(k_bam_bulk, dim3((unsigned)((n_slot * tot[1] + 3) / 4)), dim3(256), 0, s, S.bulk.p, n_slot * tot[1], I.t0, I.t1, S.tabs.p, S.sam.p, R.tag_kind ? R.tag : (const char *)nullptr);
 		AL_HIP_CHECK(hipEventRecord(S.ev, s));
 		AL_HIP_CHECK(hipStreamWaitEvent(S.io, S.ev, 0));
 	} else if (tot[1]) {
@@ -584,6 +724,18 @@ int al_stream_sam_fetch(AlStreamSlot &S, uint64_t off, uint64_t n, char *dst, hi
 	AL_HIP_CHECK(hipSetDevice(S.device));
 	if (n) AL_HIP_CHECK(hipMemcpyAsync(dst, S.sam.p + off, n, hipMemcpyDeviceToHost, S.io));
 	AL_HIP_CHECK(hipEventRecord(done, S.io));
+	return 0;
+}
+
+int al_stream_bam_index_fetch(AlStreamSlot &S, uint64_t *key, uint32_t *off, uint32_t *len)
+{   // {key, offset, length} of the batch's sam_records records, behind the kernels that made them (the slot's stream waits for those)
+	const uint64_t n = S.sam_records;
+	if (n == 0) return 0;
+	AL_HIP_CHECK(hipSetDevice(S.device));
+	AL_HIP_CHECK(hipMemcpyAsync(key, S.bam_key.p, n * 8, hipMemcpyDeviceToHost, S.io));
+	AL_HIP_CHECK(hipMemcpyAsync(off, S.bam_roff.p, n * 4, hipMemcpyDeviceToHost, S.io));
+	AL_HIP_CHECK(hipMemcpyAsync(len, S.bam_rlen.p, n * 4, hipMemcpyDeviceToHost, S.io));
+	AL_HIP_CHECK(hipStreamSynchronize(S.io));
 	return 0;
 }
 

@@ -9,6 +9,8 @@
 //   mapper per slot   read arrays on the device (pack, name hash) -> al_batch_run -> SAM text by kernels -> page-locked host buffer
 //        |
 //   writer thread     write() in batch order = input order (the reference's step 2 is serial for the same reason, map.c:601-644)
+//                     --bam: the batch's record bytes go into the run's one BGZF stream (deflate on the host's worker threads) instead;
+//                     --sorted-bam: they become a buffer of the sort store, with the keys / offsets / lengths the device made
 //
 // A lane (one GPU) has several slots, so H2D + parsing of batch n+1 and SAM text + D2H of batch n-1 overlap the mapping kernels of
 // batch n; batches are dealt to the lanes round-robin.  The host touches no record: it moves file bytes.  Batch size: workspaces
@@ -39,6 +41,8 @@
 #include "al_runtime.h"
 #include "al_stream.h"
 #include "al_stream_pipe.h"
+#include "al_bam.h"
+#include "al_sorted_store.h"
 
 namespace {
 
@@ -131,6 +135,8 @@ struct Slot {                                           // text + SAM buffers of
 	AlIngestResult res;
 	std::atomic<size_t> held{0};                        // device bytes of its buffers
 	std::vector<std::vector<char>> chunks;              // SAM text of a batch that had to be cut (else it is in S.h_sam)
+	struct RecIdx { std::vector<uint64_t> key; std::vector<uint32_t> off, len; };
+	std::vector<RecIdx> chunk_idx;                      // --sorted-bam: the records of each such piece
 };
 struct Mapper {                                         // a mapping context and the thread that runs batches on it
 	al_ctx_t *ctx = nullptr; int lane = 0, device = 0, idx = 0;
@@ -159,6 +165,8 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	static const AlStreamRange whole;
 	if (!range) range = &whole;
 	if (getenv("AL_HOST_IO") || n_fn < 1 || n_fn > 2 || n_dev < 1) return AL_STREAM_NA;
+	const int bam = rs->bam_mode;                          // 0 text, 1 BAM, 2 coordinate-sorted BAM
+	if (bam && (n_dev != 1 || range != &whole || !rs->bgzf || (bam == 2 && !rs->store) || (opt->flag & AL_F_OUT_PAF))) return AL_STREAM_NA;
 	for (int i = 0; i < n_fn; ++i) if (!eligible_file(fn[i])) return AL_STREAM_NA;
 	const bool timing = getenv("AL_TIMING") != nullptr, trace = getenv("AL_TRACE") != nullptr;
 	const double T0 = now_s();
@@ -206,7 +214,9 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	}
 	const double T1 = now_s();
 	char rg_id[256]; rg_id[0] = 0;
-	if (rg != (const char *)-1 && !(opt->flag & AL_F_OUT_PAF)) {            // (PAF has no header: nothing goes ahead of batch 0, and -R has no effect)
+	if (bam == 2) rs->store->ctx = mappers[0]->ctx;       // the device that sorts the keys of a run
+	if (bam) { if (al_bam_header(*rs->bgzf, mi, rg == (const char *)-1 ? nullptr : rg, rg_id, bam == 2)) { destroy_all(); return -3; } }
+	else if (rg != (const char *)-1 && !(opt->flag & AL_F_OUT_PAF)) {            // (PAF has no header: nothing goes ahead of batch 0, and -R has no effect)
 		if (range->header) al_write_sam_hdr(out, mi, rg, rg_id);
 		else { FILE *nul = fopen("/dev/null", "w"); if (nul) { al_write_sam_hdr(nul, mi, rg, rg_id); fclose(nul); } }     // (the read group's ID still goes into every record)
 	}
@@ -270,7 +280,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 				}
 				AlStreamSlot &S = sl->S;
 				const AlIngestResult &res = sl->res;
-				sl->chunks.clear();
+				sl->chunks.clear(); sl->chunk_idx.clear();
 				std::vector<uint32_t> fstart;                  // single-file input, a batch that has to be cut: fragment -> first record
 				bool cut = false;
 				// fragments [flo, fhi): arrays -> mapping kernels -> SAM text.  A range whose workspaces do not fit (AL_ERR_NOMEM) is cut in two
@@ -295,12 +305,16 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 					}
 					if (r != 0) return r;
 					const double t2 = now_s();
-					if ((r = al_stream_sam(S, ctx, rg_id)) != 0) return r;
+					if ((r = al_stream_sam(S, ctx, rg_id, bam)) != 0) return r;
 					if (cut) {   // (rare: the pieces of a cut batch are kept on the host until its turn to be written)
 						OutRing &mr = mrings[(size_t)(mp->lane * n_ctx_lane + mp->idx)];
 						if (!mr.buf[0] && !ring_make(mr)) return -1;
 						sl->chunks.emplace_back(); std::vector<char> &dst = sl->chunks.back(); dst.reserve(S.sam_bytes);
 						if ((r = drain_sam(S, mr, [&](const char *p, size_t n) { dst.insert(dst.end(), p, p + n); return true; })) != 0) return r;
+						if (bam == 2) {
+							sl->chunk_idx.emplace_back(); Slot::RecIdx &ix = sl->chunk_idx.back(); ix.key.resize(S.sam_records); ix.off.resize(S.sam_records); ix.len.resize(S.sam_records);
+							if (al_stream_bam_index_fetch(S, ix.key.data(), ix.off.data(), ix.len.data())) return -1;
+						}
 					}
 					mp->t_sam += now_s() - t2;
 					return 0;
@@ -359,6 +373,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	long long woff = -1; int n_wr = 1;
 	{ struct stat sb; const int fl = fcntl(ofd, F_GETFL); const off_t at = lseek(ofd, 0, SEEK_CUR);
 	  if (fstat(ofd, &sb) == 0 && S_ISREG(sb.st_mode) && at >= 0 && fl >= 0 && !(fl & O_APPEND) && !getenv("AL_NO_PWRITE")) { woff = (long long)at; n_wr = std::max(1, std::min(16, n_threads / 2)); } }
+	if (bam) woff = -1;                                   // (BAM leaves through the BGZF stream's FILE)
 	uint64_t sink_rounds = 0;                             // rounds of the caller's sink this process has taken part in
 	const uint64_t pre_bytes = ranged && range->header && woff > 0 ? (uint64_t)woff : 0;   // (the header, already in the file)
 	std::thread writer([&]() {
@@ -376,7 +391,17 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 				if (off < 0 || woff < 0) { fail(-4); return; }
 				woff = off;
 			}
+			// --sorted-bam: a piece of record bytes with its index becomes one buffer of the store
+			auto store_add = [&](std::vector<char> &&buf, const Slot::RecIdx &ix) -> bool {
+				SortedStore &st = *rs->store; const uint32_t id = (uint32_t)st.bufs.size();
+				for (size_t i = 0; i < ix.key.size(); ++i) { st.keys.push_back(ix.key[i]); st.buf_id.push_back(id); st.off.push_back(ix.off[i]); st.len.push_back(ix.len[i]); }
+				st.bytes += buf.size(); st.bufs.push_back(std::move(buf));
+				return !(st.limit && st.held() > st.limit && st.spill());
+			};
+			std::vector<char> sbuf;                           // (--sorted-bam) the batch's bytes as they arrive
 			const std::function<bool(const char *, size_t)> put = [&](const char *p, size_t n) -> bool {
+				if (bam == 2) { sbuf.insert(sbuf.end(), p, p + n); return true; }
+				if (bam == 1) return rs->bgzf->write(p, n) == 0;
 				if (woff >= 0) {
 					std::atomic<bool> okw{true}; const long long base = woff;
 					al_parallel_for(n >= ((size_t)4 << 20) ? n_wr : 1, n, [&](size_t lo, size_t hi, int) { while (lo < hi) { const ssize_t w = pwrite(ofd, p + lo, hi - lo, (off_t)(base + (long long)lo)); if (w <= 0) { okw = false; return; } lo += (size_t)w; } });
@@ -387,11 +412,26 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 				return true;
 			};
 			bool ok = true;
-			if (!sl->chunks.empty()) { for (auto &c : sl->chunks) { ok = ok && put(c.data(), c.size()); bytes_out += c.size(); } sl->chunks.clear(); }
-			else { const int dr = drain_sam(sl->S, wring, put); ok = dr == 0; if (dr == -1) { fail(-1); return; } bytes_out += sl->S.sam_bytes; }
+			if (!sl->chunks.empty()) {
+				for (size_t ci = 0; ci < sl->chunks.size(); ++ci) {
+					std::vector<char> &c = sl->chunks[ci]; bytes_out += c.size();
+					if (bam == 2) ok = ok && store_add(std::move(c), sl->chunk_idx[ci]);
+					else ok = ok && put(c.data(), c.size());
+				}
+				sl->chunks.clear(); sl->chunk_idx.clear();
+			}
+			else {
+				if (bam == 2) sbuf.reserve(sl->S.sam_bytes);
+				const int dr = drain_sam(sl->S, wring, put); ok = dr == 0; if (dr == -1) { fail(-1); return; } bytes_out += sl->S.sam_bytes;
+				if (ok && bam == 2) {
+					Slot::RecIdx ix; ix.key.resize(sl->S.sam_records); ix.off.resize(sl->S.sam_records); ix.len.resize(sl->S.sam_records);
+					if (al_stream_bam_index_fetch(sl->S, ix.key.data(), ix.off.data(), ix.len.data())) { fail(-1); return; }
+					ok = store_add(std::move(sbuf), ix);
+				}
+			}
 			recs_out += sl->S.sam_records;
 			t_write += now_s() - t0;
-			if (!ok) { perror("[airlift] writing the SAM output failed"); fail(-3); return; }
+			if (!ok) { perror(bam ? "[airlift] writing the BAM output failed" : "[airlift] writing the SAM output failed"); fail(-3); return; }
 			{ std::lock_guard<std::mutex> l(m); sl->state = SL_FREE; }
 			cv.notify_all();
 		}
@@ -579,12 +619,30 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	}
 	if (woff >= 0) (void)lseek(ofd, (off_t)woff, SEEK_SET);           // whoever writes next (the host driver taking over, the caller) continues behind the text
 	for (auto &mp : mappers) mp->th.join();
+	double t_tail = 0;
+	if (bam) {
+		int okr; { std::lock_guard<std::mutex> l(m); okr = rc == 0 ? 1 : 0; }
+		if (okr && rs->resume) { if (bam == 2) rs->store->ctx = nullptr; }      // the host driver goes on into the same stream and store, and finishes them
+		else if (okr) {
+			const double ts = now_s();
+			if (bam == 2) {   // coordinate order: stable radix sort of the keys on the GPU (per run), then the records stream out
+				if (timing && !rs->store->runs.empty()) fprintf(stderr, "[airlift] --sorted-bam: merging %zu spilled runs + the tail\n", rs->store->runs.size());
+				if (rs->store->finish([&](const char *p, uint32_t l) { return rs->bgzf->write(p, l); })) fail(-3);
+				rs->store->ctx = nullptr;
+			}
+			{ std::lock_guard<std::mutex> l(m); okr = rc == 0 ? 1 : 0; }
+			if (okr && rs->bgzf->finish()) fail(-3);
+			t_tail = now_s() - ts;
+		}
+	}
 	const double T2 = now_s();
 	if (timing) {
 		double ts = 0, tr = 0, tm = 0; for (auto &mp : mappers) { ts += mp->t_setup; tr += mp->t_run; tm += mp->t_sam; }
-		fprintf(stderr, "[airlift] stream pipeline: %d lane(s) x (%d context(s), %d slots); init %.3f s; %llu fragments, %llu reads, %llu records, %.1f MB of SAM in %.3f s (%.2f M reads/s); ingest: wait-slot %.3f load %.3f (wait-read %.3f) parse+carry %.3f; mappers (sum): setup %.3f run %.3f sam %.3f; writer %.3f; total %.3f s\n",
-		        NL, n_ctx_lane, n_slots_lane, T1 - T0, (unsigned long long)n_frag_total, (unsigned long long)n_reads_total, (unsigned long long)recs_out, bytes_out / 1e6, T2 - T1, n_reads_total / std::max(1e-9, T2 - T1) / 1e6,
+		fprintf(stderr, "[airlift] stream pipeline: %d lane(s) x (%d context(s), %d slots); init %.3f s; %llu fragments, %llu reads, %llu records, %.1f MB of %s in %.3f s (%.2f M reads/s); ingest: wait-slot %.3f load %.3f (wait-read %.3f) parse+carry %.3f; mappers (sum): setup %.3f run %.3f sam %.3f; writer %.3f; total %.3f s\n",
+		        NL, n_ctx_lane, n_slots_lane, T1 - T0, (unsigned long long)n_frag_total, (unsigned long long)n_reads_total, (unsigned long long)recs_out, bytes_out / 1e6, bam == 2 ? "BAM records (coordinate-sorted)" : bam ? "BAM records" : "SAM", T2 - T1, n_reads_total / std::max(1e-9, T2 - T1) / 1e6,
 		        t_wait_slot, t_load, t_wait_read, t_parse, ts, tr, tm, t_write, T2 - T0);
+		if (bam) fprintf(stderr, "[airlift] stream pipeline: BAM output: deflate (level %d, %d threads) %.3f s in all%s; the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n",
+		                 rs->bgzf->level, rs->bgzf->n_threads, rs->bgzf->t_deflate, rs->resume ? " so far (the host driver continues)" : "", t_write, t_tail);
 		for (auto &mp : mappers) fprintf(stderr, "[airlift] pipeline lane %d (device %d): context %d: %d batches, wait %.3f setup %.3f run %.3f sam %.3f; workspaces %.1f MB; total %.3f s\n", mp->lane, mp->device, mp->idx, mp->n_batch, mp->t_wait, mp->t_setup, mp->t_run, mp->t_sam, mp->held.load() / 1e6, T2 - T1);
 		{ AlAllocStat &a = al_alloc_stat(); fprintf(stderr, "[airlift] allocation calls of the process so far: device %lld calls, %.1f GB, %.3f s (hipMalloc + hipFree); page-locked host %lld calls, %.1f MB, %.3f s\n", (long long)a.dev_calls, a.dev_bytes / 1e9, a.dev_ns / 1e9, (long long)a.host_calls, a.host_bytes / 1e6, a.host_ns / 1e9); }
 		size_t sh = 0; for (auto &sp : slots) sh += sp->held.load();

@@ -3,7 +3,10 @@
 #include <stdio.h>
 #include "../../include/airlift.h"
 #define AL_STREAM_NA 77          // not applicable: nothing was read or written, the caller uses the host driver
-struct AlStreamResume { bool resume = false; long long off[2] = {0, 0}; char rg_id[256] = {0}; };
+struct AlBgzf; struct SortedStore;
+// what the host driver needs to continue: where, the @RG id of the header that is out, and for BAM output (bam_mode 1: input order, 2: coordinate-sorted;
+// set by the caller) the open BGZF stream and record store, which the stream driver fills and, unless it hands over, finishes
+struct AlStreamResume { bool resume = false; long long off[2] = {0, 0}; char rg_id[256] = {0}; int bam_mode = 0; AlBgzf *bgzf = nullptr; SortedStore *store = nullptr; };
 // a byte range of every input file (a record starts at start[i]; end[i] < 0: to the end of the file) and whether the SAM header is
 // printed: what one process of a multi-process run takes (al_ranked.cpp)
 // (round 6) one process of a multi-process run writing into the ONE output file: the driver tells the size of every batch it has mapped and learns
@@ -18,7 +21,7 @@ struct AlStreamRange {
 	// common grid that are this process's -- and the sink that places each batch's text
 	bool list = false; int n_ranges = 0; const long long *rstart[2] = {nullptr, nullptr}, *rend[2] = {nullptr, nullptr}; const AlStreamBatchSink *sink = nullptr;   // (list with n_ranges == 0: no batch of its own, the rounds of the sink only)
 };
-// mm_map_file_frag (map.c:672-700) for plain uncompressed four-line FASTQ files -> SAM text.  0 = done (rs->resume: the rest of the
+// mm_map_file_frag (map.c:672-700) for plain uncompressed four-line FASTQ files -> SAM text, or BAM through rs->bgzf (one device, no range).  0 = done (rs->resume: the rest of the
 // input, from rs->off, is for the general reader; the header is out), AL_STREAM_NA, or a negative error.
 int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_mapopt_t *opt, int n_threads, FILE *out, const char *rg,
                         const int *devices, int n_dev, AlStreamResume *rs, const AlStreamRange *range = nullptr);

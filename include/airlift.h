@@ -253,6 +253,11 @@ int  al_dbg_fastq_selftest(const char *fn, int n_threads);
 int  al_dbg_sam_selftest(uint64_t seed, int n_frag);
 /* The same for the PAF formatter (k_paf_len / k_paf_write; mm_write_paf3, format.c:304-330) against al_write_paf. */
 int  al_dbg_paf_selftest(uint64_t seed, int n_frag);
+/* The same for the BAM record formatter (k_bam_len / k_bam_write; al_dev_bam.h) against al_write_bam_rec: every record's bytes, the counted
+ * length and, for the coordinate-sorted output, the records kept and their sort keys. */
+int  al_dbg_bam_selftest(uint64_t seed, int n_frag);
+/* The bits of the float that formatter stores as de:f for the "%.4f" digits q (the value q / 10000). */
+uint32_t al_dbg_bam_de_bits(uint64_t q);
 
 /* ---- device-resident batch API (bench / multi-GPU harness; inputs already in HBM when timing starts) ---- */
 /* Pack + upload a batch; returns 0.  The batch stays resident until the next upload. */
