@@ -132,6 +132,14 @@ def load():
     L.al_write_paf.argtypes = [C.c_char_p, C.c_size_t, vp, cs, ci, C.POINTER(Reg), C.c_int64, ci, cs]; L.al_write_paf.restype = ci
     L.al_dbg_paf_selftest.argtypes = [C.c_uint64, ci]; L.al_dbg_paf_selftest.restype = ci
     L.al_dbg_bam_selftest.argtypes = [C.c_uint64, ci]; L.al_dbg_bam_selftest.restype = ci
+    if hasattr(L, "al_dbg_bgzf_deflate"):   # (test taps of the BGZF compressor; a test that needs them fails by name on an older library)
+        szp = C.POINTER(C.c_size_t)
+        L.al_dbg_bgzf_deflate.argtypes = [ci, vp, C.c_size_t, ci, vp, C.c_size_t, szp, szp]; L.al_dbg_bgzf_deflate.restype = ci
+        L.al_dbg_bgzf_deflate_host.argtypes = [vp, C.c_size_t, ci, vp, C.c_size_t, szp, szp]; L.al_dbg_bgzf_deflate_host.restype = ci
+        L.al_dbg_bgzf_stream.argtypes = [ci, vp, C.c_size_t, C.c_size_t, ci, vp, C.c_size_t, szp]; L.al_dbg_bgzf_stream.restype = ci
+        L.al_dbg_bgzf_stream_dev.argtypes = [ci, vp, C.c_size_t, C.c_size_t, ci, C.c_size_t, ci, vp, C.c_size_t, szp]; L.al_dbg_bgzf_stream_dev.restype = ci
+        L.al_dbg_deflate_hist.argtypes = [vp, C.c_size_t, ci, C.POINTER(C.c_uint32)]; L.al_dbg_deflate_hist.restype = ci
+        L.al_dbg_deflate_selftest.argtypes = [C.c_uint64]; L.al_dbg_deflate_selftest.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

@@ -216,6 +216,7 @@ int AlBgzf::flush_full()
 {   // compress whole blocks of the staging buffer on the worker threads, write them in order
 	const size_t nb = buf.size() / BGZF_IN;
 	if (nb == 0) return 0;
+	if (dev_on) { if (deflate_dev(buf.data(), nb * BGZF_IN)) return -1; buf.erase(buf.begin(), buf.begin() + nb * BGZF_IN); return 0; }
 	std::vector<std::vector<unsigned char>> blk(nb); std::vector<int> bad(n_threads > 1 ? n_threads : 1, 0);
 	const double t0 = bgzf_now();
 	al_parallel_for(n_threads, nb, [&](size_t lo, size_t hi, int t) { for (size_t b = lo; b < hi; ++b) if (bgzf_block(buf.data() + b * BGZF_IN, BGZF_IN, level, blk[b])) bad[t] = 1; });
@@ -225,9 +226,61 @@ int AlBgzf::flush_full()
 	buf.erase(buf.begin(), buf.begin() + nb * BGZF_IN);
 	return 0;
 }
+AlBgzf::~AlBgzf() { if (dev) al_deflate_dev_close(dev); }
+static AlDeflateDev *bgzf_open_dev(AlBgzf &z)
+{
+	if (!z.dev && !(z.dev = al_deflate_dev_open(z.dev_id))) fprintf(stderr, "[ERROR] airlift: --gpu-deflate: no device for the BGZF compressor\n");
+	return z.dev;
+}
+static void bgzf_tell_nomem(AlBgzf &z, size_t nb)
+{   // once per stream; the line at the end has the count
+	if (!z.told_nomem) fprintf(stderr, "[airlift] --gpu-deflate: no device memory for %zu BGZF blocks; this flush is deflated on the host (further ones are counted in the AL_TIMING line)\n", nb);
+	z.told_nomem = true;
+}
+int AlBgzf::deflate_dev(const char *p, size_t n)
+{
+	if (!bgzf_open_dev(*this)) return -1;
+	const double t0 = bgzf_now();                  // (after the backend was opened: t_deflate is compression, with the buffers a first or larger flush obtains)
+	std::vector<unsigned char> z;
+	const int r = al_deflate_dev_run(dev, p, n, level, z, &n_stored, &t_kernel, &t_xfer);
+	if (r < 0) { fprintf(stderr, "[ERROR] airlift: --gpu-deflate: the device compressor failed\n"); return -1; }
+	if (r > 0) {   // AL_ERR_NOMEM: this flush is compressed by the host twin -- the same bytes
+		bgzf_tell_nomem(*this, (n + BGZF_IN - 1) / BGZF_IN);
+		const double th = bgzf_now();
+		if (al_deflate_host_run(p, n, level, n_threads, z, &n_stored)) return -1;
+		t_host += bgzf_now() - th; ++n_fallback;
+	}
+	n_blocks += (n + BGZF_IN - 1) / BGZF_IN;
+	t_deflate += bgzf_now() - t0;
+	return fwrite(z.data(), 1, z.size(), out) == z.size() ? 0 : -1;
+}
+int AlBgzf::write_device(const char *d_src, size_t n, hipStream_t st, char *const ring[2], size_t piece, hipEvent_t const ev[2])
+{
+	if (!dev_on || n == 0) return 1;
+	if (buf.size() >= BGZF_IN && flush_full()) return -1;          // whole blocks the host holds go first: the carry is what is left of them
+	if (buf.size() + n < BGZF_IN) return 1;
+	if (!bgzf_open_dev(*this)) return -1;
+	const double t0 = bgzf_now();
+	std::vector<char> tail;
+	const int r = al_deflate_dev_run_resident(dev, st, buf.data(), buf.size(), d_src, n, level, ring, piece, ev, out, tail, &n_stored, &t_kernel, &t_xfer);
+	if (r < 0) { fprintf(stderr, "[ERROR] airlift: --gpu-deflate: the device compressor failed\n"); return -1; }
+	if (r > 0) { bgzf_tell_nomem(*this, (buf.size() + n) / BGZF_IN); ++n_fallback; return 1; }   // (the caller's bytes take the host-held path, whose flush falls back in turn)
+	const size_t nb = (buf.size() + n) / BGZF_IN;
+	n_blocks += nb; n_resident += nb;
+	buf.assign(tail.begin(), tail.end());
+	t_deflate += bgzf_now() - t0;
+	return 0;
+}
+void AlBgzf::timing_line(FILE *f, const char *who) const
+{
+	const double rest = t_deflate - t_kernel - t_xfer - t_host;
+	fprintf(f, "[airlift] %s: BAM output: deflate (device, %s) %.3f s in all: kernels %.3f s, transfers %.3f s, host twin %.3f s, buffers and waits %.3f s; %zu blocks, %zu of them compressed where the batch lay, %zu stored, %zu flushes on the host\n",
+	        who, level ? "one compressor for every -l above 0" : "-l 0: stored blocks", t_deflate, t_kernel, t_xfer, t_host, rest > 0 ? rest : 0.0, n_blocks, n_resident, n_stored, n_fallback);
+}
 int AlBgzf::flush_all()
 {
 	if (flush_full()) return -1;
+	if (!buf.empty() && dev_on) { if (deflate_dev(buf.data(), buf.size())) return -1; buf.clear(); }
 	if (!buf.empty()) { std::vector<unsigned char> b; if (bgzf_block(buf.data(), buf.size(), level, b) || fwrite(b.data(), 1, b.size(), out) != b.size()) return -1; buf.clear(); }
 	return 0;
 }
@@ -247,6 +300,7 @@ int al_bgzf_blocks(const char *src, size_t n, int level, int n_threads, std::vec
 int AlBgzf::finish()
 {
 	if (flush_full()) return -1;
+	if (!buf.empty() && dev_on) { if (deflate_dev(buf.data(), buf.size())) return -1; buf.clear(); }
 	if (!buf.empty()) { std::vector<unsigned char> b; if (bgzf_block(buf.data(), buf.size(), level, b) || fwrite(b.data(), 1, b.size(), out) != b.size()) return -1; buf.clear(); }
 	return fwrite(BGZF_EOF, 1, 28, out) == 28 ? 0 : -1;
 }
@@ -269,4 +323,119 @@ int al_bam_header(AlBgzf &z, const al_idx_t *mi, const char *rg, char *rg_id, bo
 	w.u32((uint32_t)mi->seq.size());
 	for (const AlSeq &s : mi->seq) { w.u32((uint32_t)s.name.size() + 1); w.mem(s.name.c_str(), s.name.size() + 1); w.u32(s.len); }
 	return z.write(h.data(), h.size());
+}
+
+// ---- test taps of the BGZF compressor (airlift_amd/capi.py) -----------------------------------------------------------------------------------
+#include "al_dev_deflate.h"
+// n host bytes through the device backend: the members in dst (cap bytes), their size in *out_n, the number of stored blocks in *n_stored
+extern "C" int al_dbg_bgzf_deflate(int device, const void *src, size_t n, int level, void *dst, size_t cap, size_t *out_n, size_t *n_stored)
+{
+	AlDeflateDev *d = al_deflate_dev_open(device);
+	if (!d) return -1;
+	std::vector<unsigned char> z; size_t ns = 0; double tk = 0, tx = 0;
+	const int r = al_deflate_dev_run(d, (const char *)src, n, level, z, &ns, &tk, &tx);
+	al_deflate_dev_close(d);
+	if (r != 0 || z.size() > cap) return r != 0 ? r : -2;
+	memcpy(dst, z.data(), z.size()); *out_n = z.size(); if (n_stored) *n_stored = ns;
+	return 0;
+}
+// the host twin
+extern "C" int al_dbg_bgzf_deflate_host(const void *src, size_t n, int level, void *dst, size_t cap, size_t *out_n, size_t *n_stored)
+{
+	std::vector<unsigned char> z; size_t ns = 0;
+	if (al_deflate_host_run((const char *)src, n, level, 4, z, &ns) || z.size() > cap) return -2;
+	memcpy(dst, z.data(), z.size()); *out_n = z.size(); if (n_stored) *n_stored = ns;
+	return 0;
+}
+// the token histograms of the host twin's parse of one block (n <= 0xff00): 286 literal/length counts, then 30 distance counts
+extern "C" int al_dbg_deflate_hist(const void *src, size_t n, int level, uint32_t *hist)
+{
+	if (n == 0 || n > BGZF_IN) return -1;
+	std::vector<unsigned char> z(AL_DFL_SLOT); int st = 0;
+	al_deflate_block_host((const uint8_t *)src, (uint32_t)n, level, z.data(), &st, hist);
+	return st;
+}
+// a whole BGZF file (EOF block included) from AlBgzf with the device backend, the bytes handed to write() in calls of `piece`
+extern "C" int al_dbg_bgzf_stream(int device, const void *src, size_t n, size_t piece, int level, void *dst, size_t cap, size_t *out_n)
+{
+	char *mem = nullptr; size_t len = 0;
+	FILE *f = open_memstream(&mem, &len);
+	if (!f) return -1;
+	int rc = 0;
+	{
+		AlBgzf z(f, (level & 0xff) | 0x100, 2, device);
+		z.cap = (size_t)3 * BGZF_IN;                                  // a flush every three blocks: a stream of a few blocks goes through many
+		if (piece == 0) piece = n ? n : 1;
+		for (size_t o = 0; o < n && rc == 0; o += piece) rc = z.write((const char *)src + o, std::min(piece, n - o));
+		if (rc == 0) rc = z.finish();
+	}
+	fclose(f);
+	if (rc == 0 && len <= cap) { memcpy(dst, mem, len); *out_n = len; } else if (rc == 0) rc = -2;
+	free(mem);
+	return rc;
+}
+// CPU only: the CRC join against zlib's crc32 on random splits (zero-length parts among them), and the code-length builder on adversarial
+// histograms (Kraft sum, 15-bit limit, zero frequency <=> zero length, cost against the fixed code's).  0 = all hold; else the number of the check that failed.
+extern "C" int al_dbg_deflate_selftest(uint64_t seed)
+{
+	uint64_t x = seed * 0x9E3779B97F4A7C15ull + 1;
+	auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
+	std::vector<unsigned char> buf(200000);
+	for (auto &c : buf) c = (unsigned char)(rnd() >> 24);
+	for (int it = 0; it < 200; ++it) {
+		size_t cut[5] = {0, 0, 0, 0, buf.size()};
+		const size_t tot = it < 8 ? (size_t)it : (size_t)(rnd() % buf.size());
+		cut[4] = tot;
+		for (int k = 1; k < 4; ++k) cut[k] = tot ? (size_t)(rnd() % (tot + 1)) : 0;
+		if (it % 5 == 0) cut[2] = cut[1];                                                   // an empty part
+		std::sort(cut, cut + 5);
+		uint32_t reg = 0; bool first = true;
+		for (int k = 0; k < 4; ++k) {
+			const size_t a = cut[k], b = cut[k + 1];
+			uint32_t r = first && b > a ? 0xffffffffu : 0;                                   // the conditioning sits at the true first byte
+			if (b > a) first = false;
+			for (size_t i = a; i < b; ++i) r = al_dfl_crc_byte(r, buf[i]);
+			reg = al_dfl_crc_join(reg, r, b - a);
+		}
+		const uint32_t mine = tot ? ~reg : 0, ref = (uint32_t)crc32(crc32(0L, Z_NULL, 0), buf.data(), (uInt)tot);
+		if (mine != ref) return 1;
+		if (tot && al_dfl_crc32_host(buf.data(), tot) != ref) return 2;
+	}
+	for (int it = 0; it < 300; ++it) {
+		const int n = it % 3 == 2 ? AL_DFL_NDIST : AL_DFL_NLIT;
+		uint32_t f[AL_DFL_NLIT] = {0}, A[AL_DFL_NLIT]; uint16_t S[AL_DFL_NLIT], code[AL_DFL_NLIT]; uint8_t len[AL_DFL_NLIT];
+		const int kind = it % 7;
+		int nu = 1 + (int)(rnd() % (uint64_t)n);
+		if (it < 4) nu = it;                                                                 // 0, 1, 2, 3 used symbols
+		if (kind == 0 && it >= 7) nu = n;
+		uint64_t a = 1, b = 1;
+		for (int k = 0; k < nu; ++k) {
+			int s; do s = (int)(rnd() % (uint64_t)n); while (f[s]);
+			if (kind == 1) { f[s] = (uint32_t)a; const uint64_t c = a + b; a = b; b = c; if (b > 20000) a = b = 1; }   // Fibonacci weights: an unlimited code is deeper than 15
+			else if (kind == 2) f[s] = 1;                                                     // flat
+			else if (kind == 3) f[s] = k == 0 ? 60000 : 1;                                    // one heavy symbol
+			else if (kind == 4) f[s] = 1u << (k % 16);                                       // powers of two
+			else f[s] = 1 + (uint32_t)(rnd() % 65000) / (1 + (uint32_t)(rnd() % 64));
+		}
+		if (kind == 1 && n == AL_DFL_NLIT) { uint64_t t = 0; for (int s = 0; s < n; ++s) t += f[s]; if (t > 65281) continue; }
+		al_dfl_lengths(f, n, len, A, S);
+		uint64_t kraft = 0, cost = 0, fixed = 0; int used = 0;
+		for (int s = 0; s < n; ++s) {
+			if ((f[s] == 0) != (len[s] == 0)) return 10;
+			if (len[s] > 15) return 11;
+			if (len[s]) { kraft += 1u << (15 - len[s]); ++used; }
+			cost += (uint64_t)f[s] * len[s];
+			fixed += (uint64_t)f[s] * (n == AL_DFL_NDIST ? 5 : s < 144 ? 8 : s < 256 ? 9 : s < 280 ? 7 : 8);
+		}
+		if (kraft > (1u << 15)) return 12;
+		if (used >= 2 && kraft != (1u << 15)) return 13;
+		if (used == 1 && kraft != (1u << 14)) return 14;
+		if (used >= 2 && cost > fixed) return 15;
+		al_dfl_codes(len, n, code);
+		for (int s = 0; s < n; ++s) for (int t = s + 1; t < n; ++t) if (len[s] && len[t]) {    // prefix-free (codes are stored reversed: compare their low bits)
+			const int m = len[s] < len[t] ? len[s] : len[t];
+			if (((code[s] ^ code[t]) & ((1u << m) - 1)) == 0) return 16;
+		}
+	}
+	return 0;
 }

@@ -2,21 +2,43 @@
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
+#include <hip/hip_runtime_api.h>
 #include <algorithm>
 #include <vector>
 #include "al_internal.h"
 
-struct AlBgzf {                 // BGZF stream: bytes in, 64 KB blocks deflated on n_threads workers, written in order
+struct AlDeflateDev;             // al_deflate.hip: the device compressor's stream and buffers
+struct AlBgzf {                 // BGZF stream: bytes in, 64 KB blocks deflated on n_threads workers -- or, with AL_BAM_DEFLATE_DEVICE in the level, by the GPU -- written in order
 	FILE *out; int level, n_threads;
 	std::vector<char> buf; size_t cap;
 	double t_deflate = 0;        // seconds spent compressing (wall time of the worker rounds), for the drivers' AL_TIMING lines
-	AlBgzf(FILE *o, int lvl, int nt) : out(o), level(lvl), n_threads(nt > 1 ? nt : 1), cap((size_t)0xff00 * 64 * (size_t)(nt > 1 ? nt : 1)) { buf.reserve(cap); }
+	// the device backend (--gpu-deflate): whole flushes go up, through k_deflate and come back as members; opened at the first flush
+	bool dev_on = false; int dev_id = -1; AlDeflateDev *dev = nullptr;
+	double t_kernel = 0, t_xfer = 0, t_host = 0; size_t n_blocks = 0, n_resident = 0, n_stored = 0, n_fallback = 0; bool told_nomem = false;   // kernel seconds (HIP events), copy seconds, host-twin seconds; blocks, blocks compressed where the batch lay, stored blocks, flushes the host twin took
+	AlBgzf(FILE *o, int lvl, int nt, int device = -1) : out(o), level(lvl & 0xff), n_threads(nt > 1 ? nt : 1), cap((size_t)0xff00 * 64 * (size_t)(nt > 1 ? nt : 1)), dev_on((lvl & 0x100) != 0), dev_id(device) { buf.reserve(cap); }
+	~AlBgzf();
+	AlBgzf(const AlBgzf &) = delete; AlBgzf &operator=(const AlBgzf &) = delete;
 	int write(const char *p, size_t n);
 	int finish();                // flushes the tail and appends the EOF block
 	int flush_all();             // everything written so far goes out as whole blocks (the tail as a short one), no EOF block: what follows may come from other writers
+	// n bytes that lie in device memory (d_src, complete behind what stream st holds) as the stream's next bytes, compressed where they lie: the pending
+	// carry (< 0xff00 bytes, host) goes up into the backend's seam buffer and is the first segment of the first block, the kernels run on st, the members
+	// leave through the caller's two page-locked buffers of `piece` bytes (ev: their 'copied' events, of st's device) and are written, the tail
+	// (< 0xff00 bytes) comes back as the new carry.  0: done; 1: not taken (backend off, fewer bytes than a block, or no device memory: the caller hands
+	// the bytes to write() instead); -1: failed.
+	int write_device(const char *d_src, size_t n, hipStream_t st, char *const ring[2], size_t piece, hipEvent_t const ev[2]);
+	void timing_line(FILE *f, const char *who) const;   // the AL_TIMING line of the device backend
 private:
 	int flush_full();
+	int deflate_dev(const char *p, size_t n);    // n bytes as members, compressed by the device backend, written
 };
+// al_deflate.hip
+AlDeflateDev *al_deflate_dev_open(int device);
+void al_deflate_dev_close(AlDeflateDev *d);
+int al_deflate_dev_run(AlDeflateDev *d, const char *src, size_t n, int level, std::vector<unsigned char> &dst, size_t *n_stored, double *kernel_s, double *xfer_s);
+int al_deflate_dev_run_resident(AlDeflateDev *d, hipStream_t st, const char *carry, size_t n_carry, const char *d_src, size_t n, int level, char *const ring[2], size_t piece, hipEvent_t const ev[2],
+                                FILE *out, std::vector<char> &tail, size_t *n_stored, double *kernel_s, double *xfer_s);
+int al_deflate_host_run(const char *src, size_t n, int level, int n_threads, std::vector<unsigned char> &dst, size_t *n_stored);
 
 // n bytes of BAM records as a sequence of whole BGZF blocks (a record may span blocks), deflated on n_threads workers, appended to dst: a lane's
 // share of a batch becomes a byte range that can be written at any offset of the output ("BGZF blocks are rank-local")

@@ -78,7 +78,9 @@ static int usage()
 	                "       --eqx (=/X CIGAR operations instead of M), -Y (soft clips and full SEQ/QUAL on supplementary records),\n"
 	                "       --secondary=yes|no (secondary alignments; the sr preset leaves them out)\n"
 	                "PAF:   --paf (PAF instead of SAM: chaining and MAPQ only, no base-level alignment, unless -c or --cs is given), -c (cg:Z CIGAR),\n"
-	                "       --paf-no-hit (a line for reads without hits); not with mem / samse / aln / tokens, --bam, --sorted-bam, --count-candidates\n");
+	                "       --paf-no-hit (a line for reads without hits); not with mem / samse / aln / tokens, --bam, --sorted-bam, --count-candidates\n"
+	                "BAM:   --bam | --sorted-bam [-l LEVEL] [--sort-mem BYTES]; --gpu-deflate (BGZF blocks deflated on the GPU: one compressor for every -l above 0,\n"
+	                "       -l 0 stores; one device, one process: not with --devices of several lanes, --world, --rank, --ranked)\n");
 	return 1;
 }
 
@@ -86,7 +88,7 @@ int main(int argc, char **argv)
 {
 	al_idxopt_t io; al_mapopt_t mo;
 	struct timespec tsm; clock_gettime(CLOCK_MONOTONIC, &tsm);
-	std::vector<const char *> pos; const char *rg = nullptr; int n_threads = 3, device = -1; std::vector<int> devices; bool count_only = false; int bam_mode = 0, bam_level = 5;
+	std::vector<const char *> pos; const char *rg = nullptr; int n_threads = 3, device = -1; std::vector<int> devices; bool count_only = false; int bam_mode = 0, bam_level = 5; bool gpu_deflate = false;
 	enum { MODE_MEM, MODE_ALN, MODE_SAMSE, MODE_MM2, MODE_TOKENS } mode = MODE_MM2; int tok_size = 0, tok_skip = 1;
 	bool prefilter = false; int pf[4] = {3, 3, 5, 3};          // adjacency e, GreedySnake e, k-mer size, rounds
 	const char *dump_fn = nullptr;
@@ -196,6 +198,7 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--bam")) bam_mode = 1;
 		else if (!strcmp(a, "--sorted-bam")) bam_mode = 2;
 		else if (!strcmp(a, "-l") && i + 1 < argc) bam_level = atoi(argv[++i]);
+		else if (!strcmp(a, "--gpu-deflate")) gpu_deflate = true;
 		else if (!strcmp(a, "--sort-mem") && i + 1 < argc) setenv("AL_SORT_MEM", std::to_string(parse_num(argv[++i], "--sort-mem")).c_str(), 1);   // --sorted-bam: bytes held before a sorted run is spilled (samtools sort -m)
 		else if (!strcmp(a, "--device") && i + 1 < argc) device = atoi(argv[++i]);
 		else if (!strcmp(a, "--rank") && i + 1 < argc) rank = atoi(argv[++i]);             // one process per GPU: --rank r --world R -o OUT (al_map_file_frag_ranked)
@@ -226,6 +229,14 @@ int main(int argc, char **argv)
 		return 1;
 	}
 	apply_out_sel(mo, sel);
+	if (gpu_deflate) {                                                  // (decided before any device is opened)
+		const bool ranked = world > 1 || rank >= 0;
+		const char *why = !bam_mode ? "it needs --bam or --sorted-bam" : devices.size() > 1 ? "it cannot be combined with --devices of more than one lane" : ranked ? "it cannot be combined with --world / --rank / --ranked" : nullptr;
+		if (why) { fprintf(stderr, "[ERROR] --gpu-deflate deflates the one BGZF stream of a BAM on one device, in one process: %s\n", why); return 1; }
+		if (bam_level < 0 || bam_level > 9) bam_level = 5;
+		fprintf(stderr, "[airlift] --gpu-deflate: BGZF blocks are %s\n", bam_level == 0 ? "stored (-l 0)" : "deflated on the device; there is one device compressor, whatever -l above 0 says");
+		bam_level |= AL_BAM_DEFLATE_DEVICE;
+	}
 	// one process per GPU?  (--world, or --rank / --ranked with the launcher's WORLD_SIZE.)  Anything else -- also WORLD_SIZE = 1, or WORLD_SIZE set
 	// without --rank / --ranked -- is a single process and writes -o FILE itself (main.c:183-190).
 	if (world <= 0 && rank >= 0 && getenv("WORLD_SIZE")) world = atoi(getenv("WORLD_SIZE"));

@@ -427,6 +427,7 @@ extern "C" int al_map_file_frag_ranked(const al_idx_t *mi, int n_fn, const char 
 extern "C" int al_map_file_frag_ranked_bam(const al_idx_t *mi, int n_fn, const char **fn, const al_mapopt_t *opt, int n_threads, const char *out_path, const char *rg,
                                            int device, int rank, int world, const char *rendezvous, double timeout_s, int bam_level)
 {
+	if (bam_level > 0 && (bam_level & AL_BAM_DEFLATE_DEVICE)) { fprintf(stderr, "[ERROR] airlift: AL_BAM_DEFLATE_DEVICE compresses the one BGZF stream of one process: it cannot be combined with ranks\n"); return -1; }
 	return map_ranked(mi, n_fn, fn, opt, n_threads, out_path, rg, device, rank, world, rendezvous, timeout_s, 1, bam_level);
 }
 static int map_ranked(const al_idx_t *mi, int n_fn, const char **fn, const al_mapopt_t *opt, int n_threads, const char *out_path, const char *rg,

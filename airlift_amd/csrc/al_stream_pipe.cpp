@@ -422,7 +422,11 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			}
 			else {
 				if (bam == 2) sbuf.reserve(sl->S.sam_bytes);
-				const int dr = drain_sam(sl->S, wring, put); ok = dr == 0; if (dr == -1) { fail(-1); return; } bytes_out += sl->S.sam_bytes;
+				// --bam --gpu-deflate: the batch is compressed where it lies, on the slot's stream, and its members leave through the ring; the
+				// writer is the stream's in-order point, so the carry between batches is AlBgzf's.  1 = not taken (a batch shorter than a block, no device memory)
+				const int wd = bam == 1 && rs->bgzf->dev_on ? rs->bgzf->write_device(sl->S.sam.p, sl->S.sam_bytes, sl->S.io, wring.buf, CH, sl->S.ev_out) : 1;
+				if (wd < 0) { fail(-3); return; }
+				const int dr = wd == 0 ? 0 : drain_sam(sl->S, wring, put); ok = dr == 0; if (dr == -1) { fail(-1); return; } bytes_out += sl->S.sam_bytes;
 				if (ok && bam == 2) {
 					Slot::RecIdx ix; ix.key.resize(sl->S.sam_records); ix.off.resize(sl->S.sam_records); ix.len.resize(sl->S.sam_records);
 					if (al_stream_bam_index_fetch(sl->S, ix.key.data(), ix.off.data(), ix.len.data())) { fail(-1); return; }
@@ -641,7 +645,8 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 		fprintf(stderr, "[airlift] stream pipeline: %d lane(s) x (%d context(s), %d slots); init %.3f s; %llu fragments, %llu reads, %llu records, %.1f MB of %s in %.3f s (%.2f M reads/s); ingest: wait-slot %.3f load %.3f (wait-read %.3f) parse+carry %.3f; mappers (sum): setup %.3f run %.3f sam %.3f; writer %.3f; total %.3f s\n",
 		        NL, n_ctx_lane, n_slots_lane, T1 - T0, (unsigned long long)n_frag_total, (unsigned long long)n_reads_total, (unsigned long long)recs_out, bytes_out / 1e6, bam == 2 ? "BAM records (coordinate-sorted)" : bam ? "BAM records" : "SAM", T2 - T1, n_reads_total / std::max(1e-9, T2 - T1) / 1e6,
 		        t_wait_slot, t_load, t_wait_read, t_parse, ts, tr, tm, t_write, T2 - T0);
-		if (bam) fprintf(stderr, "[airlift] stream pipeline: BAM output: deflate (level %d, %d threads) %.3f s in all%s; the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n",
+		if (bam && rs->bgzf->dev_on) { rs->bgzf->timing_line(stderr, "stream pipeline"); fprintf(stderr, "[airlift] stream pipeline: BAM output: the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n", t_write, t_tail); }
+		else if (bam) fprintf(stderr, "[airlift] stream pipeline: BAM output: deflate (level %d, %d threads) %.3f s in all%s; the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n",
 		                 rs->bgzf->level, rs->bgzf->n_threads, rs->bgzf->t_deflate, rs->resume ? " so far (the host driver continues)" : "", t_write, t_tail);
 		for (auto &mp : mappers) fprintf(stderr, "[airlift] pipeline lane %d (device %d): context %d: %d batches, wait %.3f setup %.3f run %.3f sam %.3f; workspaces %.1f MB; total %.3f s\n", mp->lane, mp->device, mp->idx, mp->n_batch, mp->t_wait, mp->t_setup, mp->t_run, mp->t_sam, mp->held.load() / 1e6, T2 - T1);
 		{ AlAllocStat &a = al_alloc_stat(); fprintf(stderr, "[airlift] allocation calls of the process so far: device %lld calls, %.1f GB, %.3f s (hipMalloc + hipFree); page-locked host %lld calls, %.1f MB, %.3f s\n", (long long)a.dev_calls, a.dev_bytes / 1e9, a.dev_ns / 1e9, (long long)a.host_calls, a.host_bytes / 1e6, a.host_ns / 1e9); }

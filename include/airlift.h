@@ -172,6 +172,12 @@ int  al_map_file_frag(const al_idx_t *mi, int n_segs, const char **fn, const al_
  * `| samtools view -h -F4 | samtools sort -l5` (src/0-align_reads.sh:13, run_pipeline.sh:82-87). */
 int  al_map_file_frag_bam(const al_idx_t *mi, int n_segs, const char **fn, const al_mapopt_t *opt, int n_threads,
                           FILE *out, const char *rg, int device, int sorted, int level);
+/* OR-ed into `level` of al_map_file_frag_bam: the BGZF blocks are deflated on `device` instead of the host's worker threads (the CLI's
+ * --gpu-deflate).  Level 0 stores; every other level selects the one device compressor.  The uncompressed stream and its cut into blocks
+ * are those of the host-deflated file; the compressed bytes are a function of each block's bytes alone.  Without the bit nothing changes (a
+ * level outside 0-9 means 5).  One device, one process: al_map_file_frag_multi with n_dev > 1 and al_map_file_frag_ranked_bam return -1
+ * with a message when the bit is set. */
+#define AL_BAM_DEFLATE_DEVICE 0x100
 
 /* Several GPUs of one node (the reference's analogue is kt_for over the fragments of a mini-batch, map.c:592, with
  * its serial ordered writer, map.c:601-644): lane r is a mapping context on devices[r] (a device may appear twice: two lanes
