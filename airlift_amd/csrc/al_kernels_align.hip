@@ -2974,8 +2974,8 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 		}
 		if (need && A->gws.ensure(need + 64)) return -1;
 	}
-	hipStream_t dps[4] = {s, c->aux[0], c->aux[1], c->aux[2]}; int dpk = 0;
-	if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0)); }
+	hipStream_t dps[4] = {s, c->on(AL_ROLE_AUX0), c->on(AL_ROLE_AUX1), c->on(AL_ROLE_AUX2)}; int dpk = 0;
+	if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0)); }
 	hipStream_t const s_main = s;
 	bool g12_done = false, thin22_join = false; hipStream_t thin22_stream = nullptr;
 	// two cells per lane (al_dev_ksw2.h) where its arithmetic holds (d_pk_ok); AL_DP_PK=0: the one-cell form everywhere (tests, A/B)
@@ -3022,7 +3022,7 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 					// (Side by side with the other classes the three kernels of this one still run one after the other and share a range: a range each cost 6.8 GB per context.)
 					hipStream_t const s_cls = s;
 					const bool thin22 = c22 > 0 && c22 <= 8192u && split;
-					if (thin22) { hipStream_t const s22 = s_cls == c->aux[1] ? c->aux[2] : c->aux[1]; AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s_cls)); AL_HIP_CHECK(hipStreamWaitEvent(s22, c->ev_fj[0], 0)); s = s22; gw_used = nbj; LAUNCH_DPS(22, first0 + c12 + c16, c22); s = s_cls; gw_used = 0; thin22_join = true; thin22_stream = s22; }
+					if (thin22) { hipStream_t const s22 = s_cls == c->on(AL_ROLE_AUX1) ? c->on(AL_ROLE_AUX2) : c->on(AL_ROLE_AUX1); AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s_cls)); AL_HIP_CHECK(hipStreamWaitEvent(s22, c->ev_fj[0], 0)); s = s22; gw_used = nbj; LAUNCH_DPS(22, first0 + c12 + c16, c22); s = s_cls; gw_used = 0; thin22_join = true; thin22_stream = s22; }
 					LAUNCH_DPS(12, first0, c12); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); gw_used = 0; LAUNCH_DPS(16, first0 + c12, c16); if (!dp_conc) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); gw_used = 0;
 					if (!thin22) LAUNCH_DPS(22, first0 + c12 + c16, c22);
 					if (dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G12 + 1], s_main)); AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_G16 + 1], s_main)); }
@@ -3041,7 +3041,7 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 		if (getenv("AL_TRACE")) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: DP class %d (%u jobs) -> %s\n", cls, cnt, hipGetErrorName(e)); }
 		first += cnt;
 	}
-	if (dp_conc) for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
+	if (dp_conc) for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
 	if (thin22_join && !dp_conc) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[1], thin22_stream)); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[1], 0)); }   // (side by side: the join above covers every aux stream)
 	return 0;
 }
@@ -3138,19 +3138,19 @@ int al_run_align_stage(al_ctx_t *c)
 		static const int split = getenv("AL_REGS_SPLIT") ? atoi(getenv("AL_REGS_SPLIT")) : 1;   // bit 0: 257 ... 1024 chains sorted and passed over by two kernels as well (4.6 + 2.2 ms against 7.7 in one: the pass alone fits twelve blocks a CU)
 #define LSEL(CAPV, PH, NT, A, B, ST) do { if ((B) > (A)) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_regs_select<CAPV, PH>), dim3((B) - (A)), dim3(NT), 0, ST, c->chained.p, c->u.p, c->uo.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, ord + (A), (int)((B) - (A)), c->P, regs_n0); } while (0)
 		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s));
-		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0));
+		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
 		// (round 6) the 4097 ... 8192 class on a side stream BESIDE the chip-filling classes (its sort, then its one-wavefront pass k_regs_select<-2>), launched first:
 		// 6.5 ms beside the others instead of 4.3 ms before them (regs 16.5 -> 15.7 ms; round 4 had measured 20 ms beside them, with the sort and the pass in one kernel)
-		LSEL(8192, 1, 512, lb[5], lb[3], c->aux[0]);
-		LSEL(-2, 0, 64, lb[5], lb[3], c->aux[0]);
-		LSEL(4096, 0, 256, lb[4], lb[5], c->aux[1]);
-		LSEL(-1, 0, 1024, lb[3], (uint32_t)nf, c->aux[1]);
-		LSEL(2048, 0, 256, lb[2], lb[4], c->aux[2]);
+		LSEL(8192, 1, 512, lb[5], lb[3], c->on(AL_ROLE_AUX0));
+		LSEL(-2, 0, 64, lb[5], lb[3], c->on(AL_ROLE_AUX0));
+		LSEL(4096, 0, 256, lb[4], lb[5], c->on(AL_ROLE_AUX1));
+		LSEL(-1, 0, 1024, lb[3], (uint32_t)nf, c->on(AL_ROLE_AUX1));
+		LSEL(2048, 0, 256, lb[2], lb[4], c->on(AL_ROLE_AUX2));
 		if (split & 1) { LSEL(1024, 1, 256, lb[6], lb[2], s); LSEL(-2, 0, 64, lb[6], lb[2], s); } else LSEL(1024, 0, 256, lb[6], lb[2], s);
 		LSEL(256, 0, 64, lb[1], lb[6], s);
 		LSEL(0, 0, 64, lb[0], lb[1], s);
 #undef LSEL
-		for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
+		for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
 	}
 	uint32_t hv_cnt[5] = {0, 0, 0, 0, 0};
 	const HeavyCls HT{{12, 24, 48, 72, 200}, {256, 512, 768, 1024, 2048}};
@@ -3184,17 +3184,17 @@ int al_run_align_stage(al_ctx_t *c)
 			AL_HIP_CHECK(hipFuncSetAttribute((const void *)k_regs_heavy<72, 1024, 48, 768>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_s));
 			c->attr_regs_heavy = true;
 		}
-		hipStream_t sd = c->side;
+		hipStream_t sd = c->on(AL_ROLE_SIDE);
 		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(sd, c->ev_fj[0], 0));
 #define LHV(K, RC, AC, RCL, ACL, LDS, ST) do { if (hv_cnt[K] > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_regs_heavy<RC, AC, RCL, ACL>), dim3(hv_cnt[K]), dim3(64), LDS, ST, c->chained.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, (const uint32_t *)A->heavy_list.p + (size_t)(K) * heavy_n, (int)hv_cnt[K], c->P, c->counters.p, regs_n0); } while (0)
-		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0));
-		LHV(3, 72, 1024, 48, 768, lds_s, sd); LHV(2, 48, 768, 24, 512, lds_b, c->aux[0]); LHV(4, 200, 2048, 72, 1024, lds_l, c->aux[1]); LHV(0, 12, 256, 0, 0, lds_a, c->aux[2]);
+		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
+		LHV(3, 72, 1024, 48, 768, lds_s, sd); LHV(2, 48, 768, 24, 512, lds_b, c->on(AL_ROLE_AUX0)); LHV(4, 200, 2048, 72, 1024, lds_l, c->on(AL_ROLE_AUX1)); LHV(0, 12, 256, 0, 0, lds_a, c->on(AL_ROLE_AUX2));
 		// (round 6) every fragment that is not one of these kernels' candidates: k_regs beside them, behind the shortest class (1.8 ms that used to follow the longest, 4 ms)
-		hipLaunchKernelGGL(k_regs, dim3((nf + 255) / 256), dim3(256), 0, c->aux[2], c->chained.p, c->u.p, c->uo.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, nf, c->P, c->counters.p, (const uint32_t *)regs_n0, 1);
+		hipLaunchKernelGGL(k_regs, dim3((nf + 255) / 256), dim3(256), 0, c->on(AL_ROLE_AUX2), c->chained.p, c->u.p, c->uo.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, nf, c->P, c->counters.p, (const uint32_t *)regs_n0, 1);
 		regs_part = 2;
 		AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], sd));
 		LHV(1, 24, 512, 12, 256, lds_t, s);                                       // (the fifth tile size on the main stream, beside the other four)
-		for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
+		for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
 #undef LHV
 		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0));
 	}
@@ -3317,9 +3317,9 @@ int al_run_align_stage(al_ctx_t *c)
 		static const int heavy_env = getenv("AL_PREP_HEAVY") ? atoi(getenv("AL_PREP_HEAVY")) : AL_PREP_HEAVY;      // (0: every fragment on a lane)
 		const int heavy_jobs = frag_ord ? heavy_env : 0;
 		if (heavy_jobs > 0) {
-			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fj[0], 0));
-			hipLaunchKernelGGL(k_ext_prep_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->side, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, W, G, E, nf, c->P, tmax, qmax, frag_ord, heavy_jobs);
-			AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], c->side));
+			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_fj[0], 0));
+			hipLaunchKernelGGL(k_ext_prep_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->on(AL_ROLE_SIDE), c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, W, G, E, nf, c->P, tmax, qmax, frag_ord, heavy_jobs);
+			AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], c->on(AL_ROLE_SIDE)));
 		}
 		hipLaunchKernelGGL(k_ext_prep, dim3((nf + 255) / 256), dim3(256), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, W, G, E, nf, c->P, tmax, qmax, frag_ord, heavy_jobs);
 		if (heavy_jobs > 0) AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0));
@@ -3335,9 +3335,9 @@ int al_run_align_stage(al_ctx_t *c)
 			if (n_early == 0) return 0;
 			int nbs = ((int)n_early + AL_GPB - 1) / AL_GPB; if (nbs > 1024) nbs = 1024;
 			if (A->gws2.ensure((size_t)nbs * AL_GPB * stride + 64)) return -1;
-			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_fj[0], 0));
-			if (launch_mono(A->early_list.p, (int)n_early, c->side, A->gws2.p, nbs)) return -1;
-			AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], c->side));
+			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_fj[0], 0));
+			if (launch_mono(A->early_list.p, (int)n_early, c->on(AL_ROLE_SIDE), A->gws2.p, nbs)) return -1;
+			AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], c->on(AL_ROLE_SIDE)));
 			return 0;
 		};
 		AL_HIP_CHECK(hipMemcpyAsync(&n_early, n_early_d, 4, hipMemcpyDeviceToHost, s));
@@ -3368,9 +3368,9 @@ int al_run_align_stage(al_ctx_t *c)
 			static const int fin_env = getenv("AL_FIN_HEAVY") ? atoi(getenv("AL_FIN_HEAVY")) : -1;                    // (0: every fragment on a lane)
 			const int fin_heavy = !frag_ord ? 0 : fin_env >= 0 ? fin_env : nf <= 400000 ? AL_FIN_HEAVY : 0;
 			if (fin_heavy > 0) {
-				AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->aux[0], c->ev_fj[0], 0));   // (not the side stream: the monolithic kernel may still be running there)
-				hipLaunchKernelGGL(k_ext_finish_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->aux[0], c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, E, lt, A->sc_ws.p, A->sc_off.p, nf, c->P, A->slow_list.p, n_slow_d, 1, frag_ord, fin_heavy);
-				AL_HIP_CHECK(hipEventRecord(c->ev_aux[0], c->aux[0]));
+				AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0), c->ev_fj[0], 0));   // (not the side stream: the monolithic kernel may still be running there)
+				hipLaunchKernelGGL(k_ext_finish_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->on(AL_ROLE_AUX0), c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, E, lt, A->sc_ws.p, A->sc_off.p, nf, c->P, A->slow_list.p, n_slow_d, 1, frag_ord, fin_heavy);
+				AL_HIP_CHECK(hipEventRecord(c->ev_aux[0], c->on(AL_ROLE_AUX0)));
 			}
 			hipLaunchKernelGGL(k_ext_finish, dim3((nf + 255) / 256), dim3(256), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, E, lt, A->sc_ws.p, A->sc_off.p, nf, c->P, A->slow_list.p, n_slow_d, 1, frag_ord, fin_heavy);
 			if (fin_heavy > 0) AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[0], 0));

@@ -7,6 +7,7 @@
 #include <thread>
 #include <chrono>
 #include "al_internal.h"
+#include "al_stream_plan.h"
 
 // Set when a device allocation fails; al_batch_run reports AL_ERR_NOMEM then (the context stays usable: every DevBuf is
 // either at its old size or empty, and the caller may upload a smaller batch).
@@ -66,16 +67,26 @@ struct al_ctx_s {
 	AlParams P;
 	int device = 0;
 	int n_threads = 1;                    // host worker threads for packing (al_ctx_set_threads)
-	hipStream_t stream = nullptr, side = nullptr;   // side: exact (serial) handling of the few fragments with equal-x anchors, next to the main pipeline
+	// The pipeline names ten stream ROLES (AlRole, al_stream_plan.h); the context creates n_phys <= 10 streams -- as many as the process has hardware
+	// queues -- and al_stream_plan() says which of them a role runs on.  Roles that share a stream run in submission order; a fork / join between two of
+	// them is then plain stream order.  With ten streams (ten or more queues) every role has its own.
+	//   main: the pipeline itself (`stream` below is that stream, physical 0)
+	//   side: exact (serial) handling of the few fragments with equal-x anchors, next to the main pipeline; k_align in the extension stage
+	//   aux0-2: more streams for stages made of independent latency-bound launches over disjoint fragments (heap merge classes, k_regs_heavy tiles)
+	//   ovl0-2: stages of the seed pass that run beside the main stream's: the device-wide anchor sort next to the block sorts, the lane chaining kernels next to the tile kernel
+	//   spec, spec2: the equal-x merge of giant fragments started ahead of the re-chain pass
+	hipStream_t phys[AL_ROLE_N] = {};     // the streams that exist: phys[0 .. n_phys)
+	uint8_t role_map[AL_ROLE_N] = {};     // role -> index into phys[]
+	int n_phys = 0;
+	hipStream_t stream = nullptr;         // == phys[0], the main role
+	hipStream_t on(int role) const { return phys[role_map[role]]; }   // the stream a role runs on
 	hipEvent_t ev_fj[2] = {};             // fork / join of the side stream inside a stage (chain_post classes, DP job classes)
-	hipStream_t aux[3] = {};              // more streams for stages made of independent latency-bound launches over disjoint fragments (heap merge classes, k_regs_heavy tiles)
-	hipEvent_t ev_aux[3] = {};            // ... their join events
-	hipStream_t ovl[3] = {};              // stages of the seed pass that run beside the main stream's: the device-wide anchor sort next to the block sorts, the lane chaining kernels next to the tile kernel
-	hipEvent_t ev_ovl[5] = {};            // ... fork and join events of the two
-	bool ovl_pending = false;             // chaining kernels in flight on ovl[1]: chain_tiles joins them before it reuses their scratch
+	hipEvent_t ev_aux[3] = {};            // join events of aux0-2
+	hipEvent_t ev_ovl[5] = {};            // fork and join events of ovl0-2
+	bool ovl_pending = false;             // chaining kernels in flight on ovl1: chain_tiles joins them before it reuses their scratch
 	hipEvent_t ev_side[4] = {};           // [0],[1]: start / end of the side stream's work in the first pass, [2],[3]: in the re-chain pass
 	// the equal-x merge of giant fragments started ahead of the re-chain pass (al_kernels_seed.hip: k_spec_build): its stream, events, slots
-	hipStream_t spec = nullptr, spec2 = nullptr; hipEvent_t ev_spec[3] = {}; uint32_t n_spec = 0, spec_idle = 0, spec_batch = 0; bool spec_pending = false, spec_busy = false;   // spec_idle: batches in a row whose re-chain pass took none of the merges made ahead
+	hipEvent_t ev_spec[3] = {}; uint32_t n_spec = 0, spec_idle = 0, spec_batch = 0; bool spec_pending = false, spec_busy = false;   // spec_idle: batches in a row whose re-chain pass took none of the merges made ahead
 	DevBuf<AlMatch> spec_match; DevBuf<uint32_t> spec_meta, spec_cnt, spec_use, spec_v32, spec_na2; DevBuf<uint64_t> spec_v64; DevBuf<AlAnchor> spec_anchors;
 	float ms_side = 0;
 	AlDevIndex di;
@@ -103,7 +114,7 @@ struct al_ctx_s {
 	DevBuf<AlMatch> match;
 	DevBuf<unsigned long long> counters;   // [0] heap fallbacks, [1] sort-tie flags, [2] alser total, [3] n_rechain, [4..] stage specific
 	DevBuf<uint8_t> scan_tmp;
-	DevBuf<uint8_t> big_tmp;               // rocprim scratch of the device-wide anchor sort (it runs on ovl[0], beside users of scan_tmp)
+	DevBuf<uint8_t> big_tmp;               // rocprim scratch of the device-wide anchor sort (it runs on ovl0, beside users of scan_tmp)
 	DevBuf<uint32_t> chain_key, chain_idx, chain_idx2, tie_list, lb_buf;
 	// segment-wise chaining of large fragments (al_runtime.hip: chain_by_segments) and the device-wide sort of their anchors
 	DevBuf<AlAnchor> chain_tmp; DevBuf<uint64_t> u_tmp, okey_tmp, seg_first, seg_first0, vs_off, big_off, big_toff;

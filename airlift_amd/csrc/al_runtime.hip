@@ -433,19 +433,31 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 	if (mi->w > 32 || mi->k > AL_MAX_K) { fprintf(stderr, "[airlift] FATAL: device sketch supports w <= 32, k <= %d\n", AL_MAX_K); return nullptr; }
 	al_ctx_t *c = new al_ctx_t();
 	c->mi = mi; c->opt = *opt; c->device = device;
-	if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
+	if (hipSetDevice(device) != hipSuccess) { delete c; return nullptr; }
 	for (int i = 0; i <= ST_N; ++i) if (hipEventCreate(&c->ev[i]) != hipSuccess) { delete c; return nullptr; }
+	// As many streams as the process has hardware queues (al_stream_plan.h): AL_STREAMS (1 ... 10: tests, experiments), else GPU_MAX_HW_QUEUES as the
+	// environment has it (HIP's default of 4 when it is unset), at most one per role.  The library only reads the variable.
+	static const char *const src_names[4] = {"AL_STREAMS", "GPU_MAX_HW_QUEUES in the environment", "default", "AL_STREAM_MAP"};
+	static int src = 0; static const int n_phys_proc = al_stream_count(getenv("AL_STREAMS"), getenv("GPU_MAX_HW_QUEUES"), &src);
+	c->n_phys = n_phys_proc; al_stream_plan(c->n_phys, c->role_map);
+	{ static uint8_t map_env[AL_ROLE_N]; static const int n_env = al_stream_map_parse(getenv("AL_STREAM_MAP"), map_env);   // (experiments: an explicit map)
+	  if (n_env > 0) { c->n_phys = n_env; memcpy(c->role_map, map_env, sizeof(map_env)); src = 3; } }
+	{ static std::once_flag once; static const bool timing = getenv("AL_TIMING") && atoi(getenv("AL_TIMING")) != 0;
+	  if (timing) std::call_once(once, [&] { fprintf(stderr, "[airlift] streams: %d physical for %d roles (%s)\n", c->n_phys, (int)AL_ROLE_N, src_names[src]); }); }
 	// AL_SIDE_PRIO=1 (experiment): the side streams at the highest stream priority.  Their thin classes then get CU slots ahead of the small
 	// blocks of the kernels beside them, but the main stream's kernel does not start before they are all placed and the hardware queues are
 	// shared out differently: measured 3 ms slower per C4 step than equal priorities.
 	int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
 	static const bool side_hi = getenv("AL_SIDE_PRIO") && atoi(getenv("AL_SIDE_PRIO")) == 1;
-	const int sp = side_hi ? prio_hi : 0;
-	if (hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, sp) != hipSuccess || hipEventCreate(&c->ev_side[0]) != hipSuccess || hipEventCreate(&c->ev_side[1]) != hipSuccess || hipEventCreate(&c->ev_side[2]) != hipSuccess || hipEventCreate(&c->ev_side[3]) != hipSuccess ||
-	    hipEventCreateWithFlags(&c->ev_fj[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_fj[1], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
-	for (int i = 0; i < 3; ++i) if (hipStreamCreateWithPriority(&c->aux[i], hipStreamNonBlocking, sp) != hipSuccess || hipEventCreateWithFlags(&c->ev_aux[i], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
-	for (int i = 0; i < 3; ++i) if (hipStreamCreateWithFlags(&c->ovl[i], hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
-	if (hipStreamCreateWithFlags(&c->spec, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->spec2, hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
+	if (hipStreamCreateWithFlags(&c->phys[0], hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
+	c->stream = c->phys[0];
+	for (int p = 1; p < c->n_phys; ++p) {   // a stream that carries side or aux0-2 has their priority
+		bool side_like = false; for (int r = AL_ROLE_SIDE; r <= AL_ROLE_AUX2; ++r) side_like |= c->role_map[r] == p;
+		if (hipStreamCreateWithPriority(&c->phys[p], hipStreamNonBlocking, side_like && side_hi ? prio_hi : 0) != hipSuccess) { delete c; return nullptr; }
+	}
+	for (int i = 0; i < 4; ++i) if (hipEventCreate(&c->ev_side[i]) != hipSuccess) { delete c; return nullptr; }
+	for (int i = 0; i < 2; ++i) if (hipEventCreateWithFlags(&c->ev_fj[i], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
+	for (int i = 0; i < 3; ++i) if (hipEventCreateWithFlags(&c->ev_aux[i], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
 	for (int i = 0; i < 3; ++i) if (hipEventCreateWithFlags(&c->ev_spec[i], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
 	for (int i = 0; i < 5; ++i) if (hipEventCreateWithFlags(&c->ev_ovl[i], hipEventDisableTiming) != hipSuccess) { delete c; return nullptr; }
 	if (al_upload_index(mi, device, &c->di) != 0) { delete c; return nullptr; }
@@ -470,19 +482,10 @@ static void ctx_release_buffers(al_ctx_t *c)
 	// A range given back to the reserve is handed out again at once, to any context's thread, with no device synchronisation in between (hipFree had one):
 	// every stream of this context is drained BEFORE the first range goes back -- this is reached from al_batch_run's out-of-memory exit with the
 	// alignment stage's kernels possibly still in flight.  (al_dev_free: the caller guarantees that nothing on the device still uses the range.)
-	if (c->stream) (void)hipStreamSynchronize(c->stream);
-	if (c->side) (void)hipStreamSynchronize(c->side);
-	for (int i = 0; i < 3; ++i) if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
-	for (int i = 0; i < 3; ++i) if (c->ovl[i]) (void)hipStreamSynchronize(c->ovl[i]);
-	if (c->spec) (void)hipStreamSynchronize(c->spec);
-	if (c->spec2) (void)hipStreamSynchronize(c->spec2);
+	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) (void)hipStreamSynchronize(c->phys[p]);
 	(void)hipGetLastError();
 	al_align_state_free(c);
-	if (c->side) (void)hipStreamSynchronize(c->side);
-	for (int i = 0; i < 3; ++i) if (c->aux[i]) (void)hipStreamSynchronize(c->aux[i]);
-	for (int i = 0; i < 3; ++i) if (c->ovl[i]) (void)hipStreamSynchronize(c->ovl[i]);
-	if (c->spec) (void)hipStreamSynchronize(c->spec);
-	if (c->spec2) (void)hipStreamSynchronize(c->spec2);
+	for (int p = 1; p < c->n_phys; ++p) if (c->phys[p]) (void)hipStreamSynchronize(c->phys[p]);
 	c->spec_busy = false; c->spec_pending = false; c->n_spec = 0;
 	c->spec_match.release(); c->spec_meta.release(); c->spec_cnt.release(); c->spec_use.release(); c->spec_v32.release(); c->spec_v64.release(); c->spec_anchors.release(); c->spec_na2.release();
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
@@ -504,14 +507,10 @@ extern "C" void al_ctx_destroy(al_ctx_t *c)
 	for (int i = 0; i <= ST_N; ++i) if (c->ev[i]) (void)hipEventDestroy(c->ev[i]);
 	for (int i = 0; i < 4; ++i) if (c->ev_side[i]) (void)hipEventDestroy(c->ev_side[i]);
 	for (int i = 0; i < 2; ++i) if (c->ev_fj[i]) (void)hipEventDestroy(c->ev_fj[i]);
-	if (c->side) (void)hipStreamDestroy(c->side);
-	for (int i = 0; i < 3; ++i) { if (c->aux[i]) (void)hipStreamDestroy(c->aux[i]); if (c->ev_aux[i]) (void)hipEventDestroy(c->ev_aux[i]); }
-	for (int i = 0; i < 3; ++i) if (c->ovl[i]) (void)hipStreamDestroy(c->ovl[i]);
+	for (int i = 0; i < 3; ++i) if (c->ev_aux[i]) (void)hipEventDestroy(c->ev_aux[i]);
 	for (int i = 0; i < 5; ++i) if (c->ev_ovl[i]) (void)hipEventDestroy(c->ev_ovl[i]);
-	if (c->spec) (void)hipStreamDestroy(c->spec);
-	if (c->spec2) (void)hipStreamDestroy(c->spec2);
 	for (int i = 0; i < 3; ++i) if (c->ev_spec[i]) (void)hipEventDestroy(c->ev_spec[i]);
-	if (c->stream) (void)hipStreamDestroy(c->stream);
+	for (int p = c->n_phys - 1; p >= 0; --p) if (c->phys[p]) (void)hipStreamDestroy(c->phys[p]);
 	delete c;
 }
 
@@ -869,7 +868,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 		hipLaunchKernelGGL(k_chain_tile6, dim3(S.n_items), dim3(256), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_meta.p, list, S, skip_flag,
 		                   c->chained.p, c->u.p, c->uo.p, c->frag_nu.p, c->fb_list.p, cnts, c->P, lmin, c->counters.p, force_fb, D);
 		if (ev(ST_SEG_FIND)) return -1;
-		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }   // the lane kernels of the small fragments (ovl[1]): done before their scratch is used again
+		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }   // the lane kernels of the small fragments (ovl1): done before their scratch is used again
 		{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: tile kernel (%u items, first pass %d) -> %s\n", S.n_items, (int)first, hipGetErrorName(e)); } }
 		uint32_t h[3] = {0, 0, 0};
 		AL_HIP_CHECK(hipMemcpyAsync(h, cnts, 12, hipMemcpyDeviceToHost, s));
@@ -906,17 +905,17 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 			                          cb[1] - cb[0], cb[2] - cb[1], cb[3] - cb[2], cb[4] - cb[3], cb[5] - cb[4], cb[6] - cb[5], cb[7] - cb[6], cb[8] - cb[7], cb[9] - cb[8], n_cmp); }
 			ChainSeg sg{c->vs_meta.p, nullptr, nullptr, 0, nullptr, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p};
 #define LDEF(C, L, K) do { if (!thin[K]) LCH(C, L, -1, c->vs_off.p, c->vs_na.p, c->chained.p, c->u.p, (uint32_t *)nullptr, c->seg_ord.p + cb[K], (int)(cb[K + 1] - cb[K]), sg, c->uo.p, c->ws_u64.p + wsb[K], C); } while (0)
-			// (round 5) the classes on two streams in turn, like the lane kernels of the small fragments (ovl[2] is idle here: they were joined above); AL_CHAIN_OVL2=0: all on this one
+			// (round 5) the classes on two streams in turn, like the lane kernels of the small fragments (ovl2 is idle here: they were joined above); AL_CHAIN_OVL2=0: all on this one
 			static const bool two_env = !(getenv("AL_CHAIN_OVL2") && atoi(getenv("AL_CHAIN_OVL2")) == 0);
 			const bool two = two_env && c->n_frag < 400000;                          // (a 1 M-pair batch's classes fill the chip: no gain there, C5 slightly slower)
-			hipStream_t const s_cls[2] = {s, two ? c->ovl[2] : s};
-			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->ovl[2], c->ev_ovl[4], 0)); }
+			hipStream_t const s_cls[2] = {s, two ? c->on(AL_ROLE_OVL2) : s};
+			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[4], 0)); }
 			{ int turn = 0;
 #define LDEF2(C, L, K) do { if (!thin[K] && cb[K + 1] > cb[K]) { hipStream_t const s = s_cls[turn++ & 1]; LDEF(C, L, K); } } while (0)
 			LDEF2(16, 64, 0); LDEF2(24, 64, 1); LDEF2(32, 64, 2); LDEF2(40, 64, 3); LDEF2(48, 64, 4); LDEF2(64, 64, 5); LDEF2(80, 64, 6); LDEF2(96, 64, 7); LDEF2(128, 32, 8);
 #undef LDEF2
 			}
-			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->ovl[2])); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[4], 0)); }
+			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->on(AL_ROLE_OVL2))); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[4], 0)); }
 			for (int k = 1; k < 9; ) {   // runs of neighbouring thin classes: one launch each
 				if (!thin[k]) { ++k; continue; }
 				int k1 = k; while (k1 + 1 < 9 && thin[k1 + 1]) ++k1;
@@ -975,7 +974,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 	static const uint32_t spec_min = getenv("AL_SPEC_MIN") ? (uint32_t)atoi(getenv("AL_SPEC_MIN")) : 49152u;
 	uint32_t h_spec[2 + 4 * AL_SPEC_CAP] = {0, 0};
 	if (first) {
-		if (c->spec_busy) { AL_HIP_CHECK(hipStreamSynchronize(c->spec)); AL_HIP_CHECK(hipStreamSynchronize(c->spec2)); c->spec_busy = false; }   // (the previous batch's slots: free again)
+		if (c->spec_busy) { AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SPEC))); AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SPEC2))); c->spec_busy = false; }   // (the previous batch's slots: free again)
 		c->n_spec = 0; c->spec_pending = false;
 		if (spec_now) {
 			const uint32_t SPEC_CAND = 16384;
@@ -999,9 +998,9 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 			if (c->spec_anchors.ensure(na + 1) == 0) {
 				uint32_t *v = c->spec_v32.p; const uint32_t st = SPEC_CAP + 2;
 				const SpecView V{v, v + st, v + 2 * st, v + 3 * st, v + 4 * st, v + 5 * st, v + 6 * st, c->spec_v64.p, c->spec_v64.p + st};
-				hipLaunchKernelGGL(k_spec_layout, dim3(1), dim3(64), 0, c->spec, (const uint32_t *)c->spec_meta.p, ns, SPEC_PER, V);
-				AL_HIP_CHECK(hipEventRecord(c->ev_spec[2], c->spec)); AL_HIP_CHECK(hipStreamWaitEvent(c->spec2, c->ev_spec[2], 0));   // (the two list-count classes side by side)
-#define LSPEC(NS, LO) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_lanes<NS, 16>), dim3(ns), dim3(64), 0, NS == 2 ? c->spec : c->spec2, c->di.pos, (const uint32_t *)V.first, (const uint32_t *)V.rdlen, (const uint64_t *)V.moff, (const AlMatch *)c->spec_match.p, \
+				hipLaunchKernelGGL(k_spec_layout, dim3(1), dim3(64), 0, c->on(AL_ROLE_SPEC), (const uint32_t *)c->spec_meta.p, ns, SPEC_PER, V);
+				AL_HIP_CHECK(hipEventRecord(c->ev_spec[2], c->on(AL_ROLE_SPEC))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SPEC2), c->ev_spec[2], 0));   // (the two list-count classes side by side)
+#define LSPEC(NS, LO) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_lanes<NS, 16>), dim3(ns), dim3(64), 0, NS == 2 ? c->on(AL_ROLE_SPEC) : c->on(AL_ROLE_SPEC2), c->di.pos, (const uint32_t *)V.first, (const uint32_t *)V.rdlen, (const uint64_t *)V.moff, (const AlMatch *)c->spec_match.p, \
 				                                     (const uint32_t *)V.nm, (const uint32_t *)V.na, (const uint64_t *)V.aoff, c->spec_anchors.p, (const uint32_t *)V.tie, (const uint32_t *)V.list, (const uint32_t *)V.n_list, LO, c->counters.p + 23, c->mi->k)
 				LSPEC(2, 63); LSPEC(1, -1);
 #undef LSPEC
@@ -1082,9 +1081,9 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		static const bool use_ovl = !(getenv("AL_CHAIN_OVL") && atoi(getenv("AL_CHAIN_OVL")) == 0);   // (AL_CHAIN_OVL=0: on the main stream, after the sorts)
 		// (round 5) ... on TWO streams, the classes in turn (AL_CHAIN_OVL2=0: one): a class ends in the tail of its slowest wavefronts, and the next one's start fills it
 		static const bool two = !(getenv("AL_CHAIN_OVL2") && atoi(getenv("AL_CHAIN_OVL2")) == 0);
-		if (use_ovl) { AL_HIP_CHECK(hipStreamWaitEvent(c->ovl[1], c->ev_ovl[2], 0)); if (two) AL_HIP_CHECK(hipStreamWaitEvent(c->ovl[2], c->ev_ovl[2], 0)); }
-		{ hipStream_t s = use_ovl ? c->ovl[1] : s_main; int turn = 0;
-#define NEXT_S() do { if (use_ovl && two) s = c->ovl[1 + (++turn & 1)]; } while (0)
+		if (use_ovl) { AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[2], 0)); if (two) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[2], 0)); }
+		{ hipStream_t s = use_ovl ? c->on(AL_ROLE_OVL1) : s_main; int turn = 0;
+#define NEXT_S() do { if (use_ovl && two) s = c->on(AL_ROLE_OVL1 + (++turn & 1)); } while (0)
 #define LFR(C, L, A, B) LCH(C, L, -1, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order + (A), (int)((B) - (A)), nosg, c->uo.p, c->ws_u64.p + (size_t)n_lo * 64 + (size_t)((A) - lb65) * 128, 128)
 #define LFRLO(C, L, LO) LCH(C, L, LO, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order, (int)n_lo, nosg, c->uo.p, c->ws_u64.p, 64)
 		if (lds_ok) { LFRLO(16, 64, -1); NEXT_S(); LFRLO(24, 64, 16); NEXT_S(); LFRLO(32, 64, 24); NEXT_S(); }
@@ -1105,7 +1104,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 				LFR(128, 32, from, lb129);
 			}
 		}
-		if (use_ovl && two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->ovl[2])); AL_HIP_CHECK(hipStreamWaitEvent(c->ovl[1], c->ev_ovl[4], 0)); s = c->ovl[1]; }   // (joined on ovl[1]: one event for the main stream)
+		if (use_ovl && two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->on(AL_ROLE_OVL2))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[4], 0)); s = c->on(AL_ROLE_OVL1); }   // (joined on ovl1: one event for the main stream)
 		if (use_ovl) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[3], s)); c->ovl_pending = true; } }
 #undef NEXT_S
 #undef LFR
@@ -1119,7 +1118,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		int rid_bits = 1; while ((1ULL << rid_bits) < c->mi->seq.size()) ++rid_bits;
 		// above the register tiles: composite-key device radix sort, a chunk of fragments at a time so that rank + x + list fit 64 bits.
 		// Bandwidth-bound passes over a few hundred fragments' keys: on a stream of its own, beside the tile sorts (instruction-bound) of everything else.
-		hipStream_t sb = c->ovl[0];
+		hipStream_t sb = c->on(AL_ROLE_OVL0);
 		AL_HIP_CHECK(hipEventRecord(c->ev_ovl[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(sb, c->ev_ovl[0], 0));
 		int pos_bits = 1; { uint32_t mx = 1; for (const AlSeq &sq : c->mi->seq) mx = std::max(mx, sq.len); while (pos_bits < 31 && (1ULL << pos_bits) < mx) ++pos_bits; }
 		const int rank_bits = 64 - 16 - 1 - rid_bits - pos_bits;
@@ -1200,17 +1199,17 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		else if (lb1025 > lb65) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_sort<1024>), dim3(lb1025 - lb65), dim3(64), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
 		                                           c->a_off.p, c->anchors.p, c->tie_list.p, tie_cnt, order + lb65, (int)(lb1025 - lb65), c->counters.p, c->mi->k);
 		if (ev(ST_ANCHOR_SORT)) return -1;
-		// fragments of up to 128 anchors are in order: their chaining (ovl[1], below) may start -- unless a test lowered the block sorts' bound
+		// fragments of up to 128 anchors are in order: their chaining (ovl1, below) may start -- unless a test lowered the block sorts' bound
 		// below 129 anchors (AL_TEST_SORT_BLK): then some of them are sorted by the block kernels below, and the event follows those
 		const bool small_by_blk = lb1025 < lb129;
 		if (!small_by_blk) AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));
 		LREG(8, 4, 1024, lb1025, lb2049); LREG(16, 4, 1024, lb2049, lb4097); LREG(16, 8, 1024, lb4097, lb_big);   // (non-compact keys: t_big == t_blk, empty ranges)
 		if (small_by_blk) AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));
 #undef LREG
-		// (enqueued before the merge kernels of the side streams below: whichever hardware queue ovl[1] shares, these do not wait behind one of those)
+		// (enqueued before the merge kernels of the side streams below: whichever hardware queue ovl1 shares, these do not wait behind one of those)
 		if (chain_small()) return -1;
 		if (ev(ST_ANCHOR_SORT_BLK)) return -1;
-		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[1], 0));                 // the device-wide sort (ovl[0], started before the tile sorts)
+		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[1], 0));                 // the device-wide sort (ovl0, started before the tile sorts)
 		if (ev(ST_ANCHOR_SORT_BIG)) return -1;
 		// Fragments the sort kernels flagged (equal x: overlapping mates, tandem repeats): the reference's order among equal heads is
 		// that of its binary heap, which only a serial emulation reproduces (one lane per fragment) -- a latency-bound tail on a few
@@ -1218,27 +1217,31 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		// (by segments, like the others) in a second, small round once the side stream is done.
 		hipEvent_t *const evs = c->ev_side + (first ? 0 : 2);
 		AL_HIP_CHECK(hipEventRecord(evs[0], s));
-		AL_HIP_CHECK(hipStreamWaitEvent(c->side, evs[0], 0));
+		AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), evs[0], 0));
 		// the flagged fragments are compacted first (on the side stream, count on the device): a wavefront of the merge kernels then holds 32 / 64
 		// of them instead of the few that happen to sit among 64 neighbours of the size-ordered list
 		if (c->tie_frags.ensure((size_t)nl + 2) || c->heap_cnt.ensure(4)) return -1;
 		uint32_t *const n_heap_d = c->heap_cnt.p + (first ? 0 : 1);
-		AL_HIP_CHECK(hipMemsetAsync(n_heap_d, 0, 4, c->side));
+		AL_HIP_CHECK(hipMemsetAsync(n_heap_d, 0, 4, c->on(AL_ROLE_SIDE)));
 		if (!first && c->n_spec > 0) {   // slots of the merge that was started after the first seeding: taken (flag 2) before the merge kernels' list is made, copied in on their own stream
 			const uint32_t st = AL_SPEC_CAP + 2;
-			AL_HIP_CHECK(hipEventRecord(c->ev_spec[2], c->spec2)); AL_HIP_CHECK(hipStreamWaitEvent(c->spec, c->ev_spec[2], 0));   // (both merge kernels done before the copy)
-			hipLaunchKernelGGL(k_spec_mark, dim3((AL_SPEC_CAP + 255) / 256), dim3(256), 0, c->side, (const uint32_t *)c->spec_meta.p, c->n_spec, (const uint32_t *)c->frag_nm.p, (const uint32_t *)c->frag_na.p, c->tie_list.p, c->spec_use.p, c->spec_cnt.p + 2);
-			AL_HIP_CHECK(hipEventRecord(c->ev_spec[0], c->side)); AL_HIP_CHECK(hipStreamWaitEvent(c->spec, c->ev_spec[0], 0));
-			hipLaunchKernelGGL(k_spec_apply, dim3(64, c->n_spec), dim3(256), 0, c->spec, (const uint32_t *)c->spec_meta.p, (const uint32_t *)c->spec_use.p, (const uint64_t *)(c->spec_v64.p + st), (const AlAnchor *)c->spec_anchors.p, (const uint64_t *)c->a_off.p, c->anchors.p);
-			AL_HIP_CHECK(hipEventRecord(c->ev_spec[1], c->spec));
+			AL_HIP_CHECK(hipEventRecord(c->ev_spec[2], c->on(AL_ROLE_SPEC2))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SPEC), c->ev_spec[2], 0));   // (both merge kernels done before the copy)
+			hipLaunchKernelGGL(k_spec_mark, dim3((AL_SPEC_CAP + 255) / 256), dim3(256), 0, c->on(AL_ROLE_SIDE), (const uint32_t *)c->spec_meta.p, c->n_spec, (const uint32_t *)c->frag_nm.p, (const uint32_t *)c->frag_na.p, c->tie_list.p, c->spec_use.p, c->spec_cnt.p + 2);
+			AL_HIP_CHECK(hipEventRecord(c->ev_spec[0], c->on(AL_ROLE_SIDE))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SPEC), c->ev_spec[0], 0));
+			hipLaunchKernelGGL(k_spec_apply, dim3(64, c->n_spec), dim3(256), 0, c->on(AL_ROLE_SPEC), (const uint32_t *)c->spec_meta.p, (const uint32_t *)c->spec_use.p, (const uint64_t *)(c->spec_v64.p + st), (const AlAnchor *)c->spec_anchors.p, (const uint64_t *)c->a_off.p, c->anchors.p);
+			AL_HIP_CHECK(hipEventRecord(c->ev_spec[1], c->on(AL_ROLE_SPEC)));
 			c->spec_pending = true;
-			{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { std::vector<uint32_t> u(c->n_spec); AL_HIP_CHECK(hipStreamSynchronize(c->side)); AL_HIP_CHECK(hipMemcpy(u.data(), c->spec_use.p, (size_t)c->n_spec * 4, hipMemcpyDeviceToHost));
+			{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { std::vector<uint32_t> u(c->n_spec); AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SIDE))); AL_HIP_CHECK(hipMemcpy(u.data(), c->spec_use.p, (size_t)c->n_spec * 4, hipMemcpyDeviceToHost));
 			  uint32_t k = 0; for (uint32_t x : u) k += x; fprintf(stderr, "[airlift] trace: re-chain pass takes %u of the %u merges made ahead\n", k, c->n_spec); } }
 		}
-		hipLaunchKernelGGL(k_collect_flagged_blk, dim3((nl + 255) / 256), dim3(256), 0, c->side, order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, n_heap_d);
+		hipLaunchKernelGGL(k_collect_flagged_blk, dim3((nl + 255) / 256), dim3(256), 0, c->on(AL_ROLE_SIDE), order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, n_heap_d);
 		// the four merge kernels take disjoint fragments and each waits for its slowest one: side by side, on a stream each
-		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], c->side));
-		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->aux[i], c->ev_fj[0], 0));
+		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], c->on(AL_ROLE_SIDE)));
+		// (only the streams that get a kernel below: aux1 has none unless AL_HEAP_OLD=1, and where it shares a stream with the merges made ahead its
+		//  join would make the main stream wait for those)
+		static const bool heap_old = getenv("AL_HEAP_OLD") && atoi(getenv("AL_HEAP_OLD")) == 1;
+		const bool aux_used[3] = {true, heap_old, true};
+		for (int i = 0; i < 3; ++i) if (aux_used[i]) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
 #define LHEAP(H, LN, LO, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap<H, LN>), dim3((nl + LN - 1) / LN), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
 		                                  c->a_off.p, c->anchors.p, c->heap_ws.p, c->tie_list.p, (const uint32_t *)c->tie_frags.p, nl, LO, c->counters.p, c->mi->k, (const uint32_t *)n_heap_d, wave_na_min)
 		// A lane of the lane kernels pops ~1 us per anchor with its 63 neighbours busy, the wavefront kernel 0.8 us with a wavefront to itself: in a
@@ -1248,25 +1251,24 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		const uint32_t wave_na_min = wave_env >= 0 ? (uint32_t)wave_env : c->n_frag >= 400000 ? 16384u : 8192u;
 		// Round 5: the heap in the lanes of a wavefront (k_anchor_heap_lanes: a fixed number of wave-wide instructions per pop instead of an LDS round trip
 		// per sift level) for every flagged fragment of up to 126 lists; the serial forms remain for more lists and behind AL_HEAP_OLD=1 (tests, A/B).
-		static const bool heap_old = getenv("AL_HEAP_OLD") && atoi(getenv("AL_HEAP_OLD")) == 1;
 		if (!heap_old) {
 #define LHL(NS, LO, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_lanes<NS, 16>), dim3(std::min(nl, 65536)), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
 		                                    c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, LO, c->counters.p, c->mi->k)
-			LHL(2, 63, c->side); LHL(1, -1, c->aux[0]);
+			LHL(2, 63, c->on(AL_ROLE_SIDE)); LHL(1, -1, c->on(AL_ROLE_AUX0));
 #undef LHL
-			{ const uint32_t wave_na_min = 0xffffffffu; LHEAP(0, 64, 126, c->aux[2]); }
+			{ const uint32_t wave_na_min = 0xffffffffu; LHEAP(0, 64, 126, c->on(AL_ROLE_AUX2)); }
 		} else {
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_wave<128, 32>), dim3(std::min(nl, 65536)), dim3(64), 0, c->side, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_wave<128, 32>), dim3(std::min(nl, 65536)), dim3(64), 0, c->on(AL_ROLE_SIDE), c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
 		                   c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, wave_na_min, c->counters.p, c->mi->k);
-		LHEAP(48, 64, -1, c->aux[0]); LHEAP(96, 32, 48, c->aux[1]); LHEAP(0, 64, 96, c->aux[2]);
+		LHEAP(48, 64, -1, c->on(AL_ROLE_AUX0)); LHEAP(96, 32, 48, c->on(AL_ROLE_AUX1)); LHEAP(0, 64, 96, c->on(AL_ROLE_AUX2));
 		}
 #undef LHEAP
-		for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->aux[i])); AL_HIP_CHECK(hipStreamWaitEvent(c->side, c->ev_aux[i], 0)); }
-		AL_HIP_CHECK(hipEventRecord(evs[1], c->side));
+		for (int i = 0; i < 3; ++i) if (aux_used[i]) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_aux[i], 0)); }
+		AL_HIP_CHECK(hipEventRecord(evs[1], c->on(AL_ROLE_SIDE)));
 		if (ev(ST_ANCHOR_HEAP)) return -1;
 	}
 	{
-		// (the four chain_lds intervals are empty since the lane-per-fragment kernels of the <= 128-anchor fragments moved to ovl[1], beside the block
+		// (the four chain_lds intervals are empty since the lane-per-fragment kernels of the <= 128-anchor fragments moved to ovl1, beside the block
 		//  sorts and the tile kernel: their time is inside anchor_sort_blk / chain_tile; the names stay so that the stage table keeps its columns)
 		if (ev(ST_CHAIN_LDS32) || ev(ST_CHAIN_LDS48) || ev(ST_CHAIN_LDS64) || ev(ST_CHAIN_LDS128)) return -1;
 		if (tiles_ok) {
