@@ -140,6 +140,12 @@ def load():
         L.al_dbg_bgzf_stream_dev.argtypes = [ci, vp, C.c_size_t, C.c_size_t, ci, C.c_size_t, ci, vp, C.c_size_t, szp]; L.al_dbg_bgzf_stream_dev.restype = ci
         L.al_dbg_deflate_hist.argtypes = [vp, C.c_size_t, ci, C.POINTER(C.c_uint32)]; L.al_dbg_deflate_hist.restype = ci
         L.al_dbg_deflate_selftest.argtypes = [C.c_uint64]; L.al_dbg_deflate_selftest.restype = ci
+    if hasattr(L, "al_dbg_bgzf_inflate"):   # (--gpu-inflate: the extraction with a choice of reader, and the test taps of the BGZF inflater)
+        szp = C.POINTER(C.c_size_t); u32p = C.POINTER(C.c_uint32)
+        L.al_extract_reads_ex.argtypes = [cs, cs, ci, ci, vp, C.c_uint, ci, ci]; L.al_extract_reads_ex.restype = C.c_int64
+        L.al_dbg_bgzf_inflate_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, szp, u32p, C.c_size_t, szp]; L.al_dbg_bgzf_inflate_host.restype = ci
+        L.al_dbg_bgzf_inflate.argtypes = [ci, vp, C.c_size_t, vp, C.c_size_t, szp, u32p, C.c_size_t, szp]; L.al_dbg_bgzf_inflate.restype = ci
+        L.al_dbg_bgzf_inflate_guard.argtypes = [ci, vp, C.c_size_t, vp, C.c_size_t, szp, u32p, C.c_size_t, szp]; L.al_dbg_bgzf_inflate_guard.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

@@ -40,6 +40,24 @@ int al_deflate_dev_run_resident(AlDeflateDev *d, hipStream_t st, const char *car
                                 FILE *out, std::vector<char> &tail, size_t *n_stored, double *kernel_s, double *xfer_s);
 int al_deflate_host_run(const char *src, size_t n, int level, int n_threads, std::vector<unsigned char> &dst, size_t *n_stored);
 
+
+// BGZF input (--gpu-inflate; al_inflate.hip): the file's members inflated by k_inflate, a piece of the file at a time, and handed out as one byte stream.
+// open(): true when the reader took the file; false with plain set when it is no BGZF file (gzip without the BC subfield, or "-"): the caller reads it as
+// one gzip stream.  read(): n bytes, false at the end of the file or at an error -- failed() tells which, message() names the member's file offset and status.
+struct AlBgzfInImpl;
+struct AlBgzfIn {
+	AlBgzfInImpl *p = nullptr; int device, n_threads; bool plain = false, host_backend = false, fell_back = false;
+	AlBgzfIn(int device, int n_threads);
+	~AlBgzfIn();
+	AlBgzfIn(const AlBgzfIn &) = delete; AlBgzfIn &operator=(const AlBgzfIn &) = delete;
+	bool open(const char *fn);
+	bool read(void *dst, size_t n);
+	bool failed() const;
+	const char *message() const;
+	void close();                 // stops the reader thread and releases the device and page-locked buffers
+	void timing_line(FILE *f, double scan_s) const;   // the AL_TIMING line; scan_s: seconds the caller spent in its record loop, read() included
+};
+
 // n bytes of BAM records as a sequence of whole BGZF blocks (a record may span blocks), deflated on n_threads workers, appended to dst: a lane's
 // share of a batch becomes a byte range that can be written at any offset of the output ("BGZF blocks are rank-local")
 int al_bgzf_blocks(const char *src, size_t n, int level, int n_threads, std::vector<char> &dst);

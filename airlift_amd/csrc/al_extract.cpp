@@ -1,5 +1,6 @@
 // al_extract.cpp -- SURVEY.md N1: the read-extraction stage that feeds the re-alignment path, as two host routines that
-// replace AirLift's per-region process spawning (product code, C++; no GPU work: this stage is I/O and set logic).
+// replace AirLift's per-region process spawning (product code, C++; I/O and set logic on the host -- with --gpu-inflate the BAM's BGZF members
+// are inflated on the device, AlBgzfIn in al_inflate.hip, and the record loop below reads from that).
 //
 //   al_extract_reads      src/4-extract_reads/extract_reads.sh:8 / extract_reads_noprune.sh:7.  The scripts start
 //                         `samtools view BAM chrom:B-E | convert2bed | awk` once per BED line (run_pipeline.sh:58 spreads them
@@ -23,6 +24,8 @@
 #include <vector>
 #include "al_internal.h"
 #include "al_seqio.h"
+#include "al_bam.h"
+#include <chrono>
 
 namespace {
 
@@ -40,6 +43,8 @@ struct GzIn {                      // BGZF is a sequence of gzip members: zlib's
 		}
 		return true;
 	}
+	bool failed() const { return false; }          // (a read error at a record boundary ends the file, as it always did)
+	const char *message() const { return ""; }
 };
 
 struct BedLine { int64_t b, e; uint32_t idx; };
@@ -47,12 +52,11 @@ struct ChromIdx { std::vector<BedLine> v; std::vector<int64_t> pmax; };      // 
 
 } // namespace
 
-// extract_reads.sh:8 (prune != 0) / extract_reads_noprune.sh:7 (prune == 0) for every line of bed_fn against bam_fn.
-// Rows: chrom, start, end, name[.1|.2], MAPQ, CIGAR.  Returns the number of rows, negative on error.
-extern "C" int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int read_size, int prune, FILE *out)
+namespace {
+typedef std::unordered_map<std::string, ChromIdx> BedIdx;
+int load_bed(const char *bed_fn, BedIdx &idx)
 {
 	// BED lines: (chrom B E); a record belongs to the line if its BED row lies in [B-1, E-1]
-	std::unordered_map<std::string, ChromIdx> idx;
 	{
 		FILE *fb = strcmp(bed_fn, "-") == 0 ? stdin : fopen(bed_fn, "r");
 		if (!fb) { fprintf(stderr, "ERROR: failed to open file '%s'\n", bed_fn); return -1; }
@@ -70,10 +74,13 @@ extern "C" int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int 
 			for (size_t i = 0; i < v.size(); ++i) { m = std::max(m, v[i].e); kv.second.pmax[i] = m; }
 		}
 	}
-	GzIn in;
-	if (!in.open(bam_fn)) { fprintf(stderr, "ERROR: failed to open file '%s'\n", bam_fn); return -1; }
+	return 0;
+}
+// the record loop, written once over either reader (GzIn, AlBgzfIn)
+template <class In> int64_t scan_records(In &in, const char *bam_fn, const BedIdx &idx, int read_size, int prune, FILE *out)
+{
 	char magic[4]; int32_t l_text, n_ref;
-	if (!in.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0 || !in.read(&l_text, 4)) { fprintf(stderr, "ERROR: '%s' is not a BAM file\n", bam_fn); return -2; }
+	if (!in.read(magic, 4) || memcmp(magic, "BAM\1", 4) != 0 || !in.read(&l_text, 4)) { fprintf(stderr, "ERROR: '%s' is not a BAM file%s%s\n", bam_fn, in.failed() ? ": " : "", in.failed() ? in.message() : ""); return -2; }
 	// every length field of the file is checked before it sizes anything: a truncated or corrupt BAM is error -2, not a crash
 	if (l_text < 0) return -2;
 	{ std::vector<char> t((size_t)l_text); if (l_text && !in.read(t.data(), t.size())) return -2; }
@@ -92,10 +99,10 @@ extern "C" int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int 
 	std::vector<unsigned char> rec; std::vector<uint32_t> cg; uint64_t ord = 0;
 	for (;;) {
 		int32_t bs;
-		if (!in.read(&bs, 4)) break;
+		if (!in.read(&bs, 4)) { if (in.failed()) { fprintf(stderr, "ERROR: '%s': %s\n", bam_fn, in.message()); return -2; } break; }
 		if (bs < 32 || bs > (1 << 28)) return -2;
 		rec.resize((size_t)bs);
-		if (!in.read(rec.data(), rec.size())) return -2;
+		if (!in.read(rec.data(), rec.size())) { if (in.failed()) fprintf(stderr, "ERROR: '%s': %s\n", bam_fn, in.message()); return -2; }
 		++ord;
 		int32_t rid, pos; memcpy(&rid, rec.data(), 4); memcpy(&pos, rec.data() + 4, 4);
 		const uint32_t l_rn = rec[8], mapq = rec[9]; uint16_t n_cig, flag; memcpy(&n_cig, rec.data() + 12, 2); memcpy(&flag, rec.data() + 14, 2);
@@ -128,6 +135,40 @@ extern "C" int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int 
 	std::sort(order.begin(), order.end(), [](const std::pair<const std::string, Row> *a, const std::pair<const std::string, Row> *b) { return a->first < b->first; });   // sort -k4,4, C locale
 	for (const auto *p : order) if (fwrite(p->second.text.data(), 1, p->second.text.size(), out) != p->second.text.size()) return -3;
 	return (int64_t)order.size();
+}
+int64_t extract_gz(const char *bam_fn, const BedIdx &idx, int read_size, int prune, FILE *out)
+{
+	GzIn in;
+	if (!in.open(bam_fn)) { fprintf(stderr, "ERROR: failed to open file '%s'\n", bam_fn); return -1; }
+	return scan_records(in, bam_fn, idx, read_size, prune, out);
+}
+} // namespace
+
+// extract_reads.sh:8 (prune != 0) / extract_reads_noprune.sh:7 (prune == 0) for every line of bed_fn against bam_fn.
+// Rows: chrom, start, end, name[.1|.2], MAPQ, CIGAR.  Returns the number of rows, negative on error.
+extern "C" int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int read_size, int prune, FILE *out)
+{
+	BedIdx idx;
+	if (const int r = load_bed(bed_fn, idx)) return r;
+	return extract_gz(bam_fn, idx, read_size, prune, out);
+}
+// The same rows with the BAM read through AlBgzfIn when flags has AL_EXTRACT_GPU_INFLATE: its BGZF members are inflated on `device` (-1: the default
+// device), or by zlib on n_threads workers where the device has no memory for it.  A file that is no BGZF file, and "-", take the one-stream reader.
+extern "C" int64_t al_extract_reads_ex(const char *bam_fn, const char *bed_fn, int read_size, int prune, FILE *out, unsigned flags, int device, int n_threads)
+{
+	if (!(flags & AL_EXTRACT_GPU_INFLATE)) return al_extract_reads(bam_fn, bed_fn, read_size, prune, out);
+	BedIdx idx;
+	if (const int r = load_bed(bed_fn, idx)) return r;
+	AlBgzfIn in(device, n_threads);
+	if (!in.open(bam_fn)) {
+		if (!in.plain) { fprintf(stderr, "ERROR: failed to open file '%s'\n", bam_fn); return -1; }
+		fprintf(stderr, "[airlift] --gpu-inflate: '%s' is not a BGZF file; it is read as one gzip stream on the host\n", bam_fn);
+		return extract_gz(bam_fn, idx, read_size, prune, out);
+	}
+	const auto t0 = std::chrono::steady_clock::now();
+	const int64_t n = scan_records(in, bam_fn, idx, read_size, prune, out);
+	if (getenv("AL_TIMING")) in.timing_line(stderr, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+	return n;
 }
 
 namespace {
@@ -229,11 +270,16 @@ extern "C" int al_extract_sequence(const char *fq1, const char *fq2, const char 
 // The caller closes the descriptors.  Returns 0, negative on error.
 extern "C" int al_extract_to_memory(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single)
 {
+	return al_extract_to_memory_ex(bam_fn, bed_fn, read_size, prune, fq1, fq2, fds, n_pairs, n_single, 0, -1, 1);
+}
+// flags, device, n_threads: as al_extract_reads_ex (the reader's buffers are released before this returns)
+extern "C" int al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single, unsigned flags, int device, int n_threads)
+{
 	fds[0] = fds[1] = fds[2] = -1;
 	char *rows = nullptr; size_t rows_len = 0;
 	FILE *rf = open_memstream(&rows, &rows_len);
 	if (!rf) return -1;
-	const int64_t n = al_extract_reads(bam_fn, bed_fn, read_size, prune, rf);
+	const int64_t n = al_extract_reads_ex(bam_fn, bed_fn, read_size, prune, rf, flags, device, n_threads);
 	if (fflush(rf) == EOF || n < 0) { fclose(rf); free(rows); return n < 0 ? (int)n : -3; }
 	fclose(rf);
 	std::unordered_set<std::string> l1, l2;

@@ -99,10 +99,16 @@ int main(int argc, char **argv)
 	al_set_opt("sr", &io, &mo);
 	mo.flag |= AL_F_OUT_SAM | AL_F_CIGAR;
 	if (!strcmp(argv[1], "extract-reads")) {       // N1: airlift-align extract-reads [--noprune] READS.bam REGIONS.bed READSIZE > rows   (extract_reads.sh BINDIR BAM BED READSIZE)
-		int prune = 1; std::vector<const char *> p;
-		for (int j = 2; j < argc; ++j) { if (!strcmp(argv[j], "--noprune")) prune = 0; else p.push_back(argv[j]); }
-		if (p.size() < 2 || (prune && p.size() < 3)) { fprintf(stderr, "Usage: airlift-align extract-reads [--noprune] reads.bam regions.bed [readsize]\n"); return 1; }
-		const int64_t n = al_extract_reads(p[0], p[1], p.size() > 2 ? atoi(p[2]) : 0, prune, stdout);
+		int prune = 1, nt = 3, dev = -1; unsigned xf = 0; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "--noprune")) prune = 0;
+			else if (!strcmp(argv[j], "--gpu-inflate")) xf |= AL_EXTRACT_GPU_INFLATE;      // the BAM's BGZF members are inflated on the GPU (-t: host threads of the fallback)
+			else if (xf && !strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
+			else if (xf && !strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else p.push_back(argv[j]);
+		}
+		if (p.size() < 2 || (prune && p.size() < 3)) { fprintf(stderr, "Usage: airlift-align extract-reads [--noprune] [--gpu-inflate [-t N] [--device D]] reads.bam regions.bed [readsize]\n"); return 1; }
+		const int64_t n = xf ? al_extract_reads_ex(p[0], p[1], p.size() > 2 ? atoi(p[2]) : 0, prune, stdout, xf, dev, nt) : al_extract_reads(p[0], p[1], p.size() > 2 ? atoi(p[2]) : 0, prune, stdout);
 		return n < 0 || fflush(stdout) == EOF ? 1 : 0;
 	}
 	if (!strcmp(argv[1], "extract-sequence")) {    // N1: airlift-align extract-sequence FQ1 FQ2 ROWS OUTDIR   (extract_sequence.sh BINDIR FQ1 FQ2 BED THREAD OUTPUT)
@@ -116,9 +122,10 @@ int main(int argc, char **argv)
 		// N1 fused with the re-alignment: airlift-align remap [-t N] [-R RG] [--noprune] [--readsize R] -o PAIRS.sam [--singletons SINGLE.sam] REF.fa READS.bam REGIONS.bed FQ1 FQ2
 		// = extract_reads.sh + extract_sequence.sh + 0-align_reads.sh + 0-align_singletons.sh (run_pipeline.sh:58,103-113) without the rows file, the
 		// three FASTQ files and the tool processes in between: the selected reads stay in memory files that the stream driver hands to the GPU.
-		int prune = 1, read_size = 0, n_threads = 3; const char *rg = nullptr, *out_p = nullptr, *out_s = nullptr; std::vector<const char *> p;
+		int prune = 1, read_size = 0, n_threads = 3; const char *rg = nullptr, *out_p = nullptr, *out_s = nullptr; std::vector<const char *> p; unsigned xf = 0;
 		for (int j = 2; j < argc; ++j) {
 			if (!strcmp(argv[j], "--noprune")) prune = 0;
+			else if (!strcmp(argv[j], "--gpu-inflate")) xf |= AL_EXTRACT_GPU_INFLATE;      // READS.bam is inflated on the run's device; the reader's buffers are gone before the mapper sizes its own
 			else if (!strcmp(argv[j], "--readsize") && j + 1 < argc) read_size = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-t") && j + 1 < argc) n_threads = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-R") && j + 1 < argc) rg = argv[++j];
@@ -128,11 +135,11 @@ int main(int argc, char **argv)
 			else p.push_back(argv[j]);
 		}
 		apply_out_sel(mo, sel);
-		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
+		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] [--gpu-inflate] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
 		if (!getenv("AL_PG_PLAIN")) al_set_program_line(AL_MM_VERSION, argc, argv);
 		if (!k_given) setenv("AL_AUTO_BATCH", "1", 0);
 		int fds[3]; int64_t np = 0, ns = 0;
-		if (al_extract_to_memory(p[1], p[2], read_size, prune, p[3], p[4], fds, &np, &ns) != 0) return 1;
+		if (al_extract_to_memory_ex(p[1], p[2], read_size, prune, p[3], p[4], fds, &np, &ns, xf, -1, n_threads) != 0) return 1;
 		fprintf(stderr, "[airlift] remap: %lld pairs, %lld singletons selected\n", (long long)np, (long long)ns);
 		if (al_check_opt(&io, &mo) < 0) return 1;
 		al_idx_t *mi = al_idx_build_device(p[0], &io, -1);

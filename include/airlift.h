@@ -211,6 +211,13 @@ int  al_dbg_ranked_selftest(const char *fn1, const char *fn2, int world, const c
  * (start >= B-1, end <= E-1) and, when pruning, have MAPQ <= 10 or a CIGAR other than "<read_size>M"; one row per name,
  * sorted by name (`sort -uk4,4`).  Returns the number of rows, negative on error. */
 int64_t al_extract_reads(const char *bam_fn, const char *bed_fn, int read_size, int prune, FILE *out);
+/* The same rows with a choice of reader.  flags & AL_EXTRACT_GPU_INFLATE (the CLI's --gpu-inflate): the BGZF members of the BAM are inflated on
+ * `device` (-1: the default device) by k_inflate, a piece of the file at a time, CRC32 checked there; where the device has no memory for the
+ * reader's buffers they are inflated by zlib on n_threads host threads instead (one notice on stderr).  A member that does not inflate, a wrong
+ * CRC32 and a truncated last member are error -2, with the member's file offset on stderr.  A gzip file that is not BGZF, and "-", are read as one
+ * gzip stream, as al_extract_reads does.  flags == 0 is al_extract_reads.  (Test switches: DESIGN.md section 8.) */
+#define AL_EXTRACT_GPU_INFLATE 1u
+int64_t al_extract_reads_ex(const char *bam_fn, const char *bed_fn, int read_size, int prune, FILE *out, unsigned flags, int device, int n_threads);
 /* src/4-extract_reads/extract_sequence.sh:17-19: FASTQ subsets by the names in column 4 of `rows_fn` (seqtk subseq), pairing
  * (BBMap repair.sh) and renaming (rename.sh: realigned_<n>, realigned_singleton_<n>) into out_dir/reads_1.fastq,
  * reads_2.fastq, singletons.fastq.  Returns 0, negative on error. */
@@ -219,6 +226,18 @@ int  al_extract_sequence(const char *fq1, const char *fq2, const char *rows_fn, 
  * (pairs file 1, pairs file 2, singletons) are left in anonymous memory files whose descriptors go to fds[0..2]; map them by path
  * ("/proc/self/fd/<n>") with al_map_file_frag -- `airlift-align remap` does exactly that -- and close() them.  0, negative on error. */
 int  al_extract_to_memory(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single);
+/* ... with flags, device, n_threads as al_extract_reads_ex; the reader's device and page-locked buffers are released before it returns. */
+int  al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single,
+                             unsigned flags, int device, int n_threads);
+/* Taps of the BGZF inflater (al_dev_inflate.h, al_inflate.hip; tests).  src[0, n) is a sequence of whole BGZF members: they are listed along the BSIZE
+ * chain and inflated to dst (cap bytes), member m at the sum of ISIZE of the members before it; *out_n = that sum over all, status[m] = 0 or the
+ * member's error (AL_INF_E_*: 1 header, 2 block type, 3 stored lengths, 4 code lengths, 5 symbol, 6 distance, 7 input exhausted, 8 over ISIZE,
+ * 9 short of ISIZE, 10 CRC), *n_members = members listed.  0; -2 when the chain breaks (no BC subfield, BSIZE past the end: the members before are
+ * done); -3 when cap or n_status is too small; -1 when a HIP call fails.  _host: the host twin, serially.  The device tap: k_inflate over the whole
+ * list in one launch.  _guard: the same with the output between two poisoned ranges of 64 KB, -7 when the kernel wrote into one. */
+int  al_dbg_bgzf_inflate_host(const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
+int  al_dbg_bgzf_inflate(int device, const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
+int  al_dbg_bgzf_inflate_guard(int device, const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
 
 /* Tap (parity tests): the extension DP alone -- ksw_extd2_sse's result for n caller-supplied pairs, as the reference's --print-aln-seq
  * shows them (align.c:313-339).  seqs: nt4 codes (0..4); jobs6: {target offset, query offset, tlen, qlen, ksw flag, 0} per pair (the
