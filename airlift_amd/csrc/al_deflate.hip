@@ -252,7 +252,7 @@ AlDeflateDev *al_deflate_dev_open(int device)
 {
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return nullptr; }
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) % n_dev : 0; }
+	device = al_env_pick_device(device, n_dev);
 	AlDeflateDev *d = new AlDeflateDev(); d->device = device;
 	hipDeviceProp_t pr;
 	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&pr, device) != hipSuccess || hipStreamCreateWithFlags(&d->st, hipStreamNonBlocking) != hipSuccess ||
@@ -280,7 +280,7 @@ void al_deflate_dev_close(AlDeflateDev *d)
 static int dfl_ensure(AlDeflateDev *d, size_t nb, bool need_in)
 {
 	if (nb <= d->cap_nb && (!need_in || nb <= d->cap_in)) return 0;
-	static const bool refuse = getenv("AL_TEST_DEFLATE_NOMEM") != nullptr;      // (test switch, DESIGN.md section 8: every request is refused)
+	const bool refuse = al_env().test_deflate_nomem;      // (test switch, DESIGN.md section 8: every request is refused)
 	const size_t cap = std::max(nb + nb / 4 + 1, d->cap_nb);
 	const bool in = need_in || d->cap_in > 0;
 	dfl_release(d);

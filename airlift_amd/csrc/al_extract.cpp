@@ -23,6 +23,7 @@
 #include <unordered_set>
 #include <vector>
 #include "al_internal.h"
+#include "al_env.h"
 #include "al_seqio.h"
 #include "al_bam.h"
 #include <chrono>
@@ -167,7 +168,7 @@ extern "C" int64_t al_extract_reads_ex(const char *bam_fn, const char *bed_fn, i
 	}
 	const auto t0 = std::chrono::steady_clock::now();
 	const int64_t n = scan_records(in, bam_fn, idx, read_size, prune, out);
-	if (getenv("AL_TIMING")) in.timing_line(stderr, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
+	if (al_env().timing) in.timing_line(stderr, std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 	return n;
 }
 

@@ -16,6 +16,7 @@
 #include <thread>
 #include <vector>
 #include "al_internal.h"
+#include "al_env.h"
 
 namespace {
 struct Piece { size_t beg, end; uint32_t rec; uint64_t n; uint64_t out; };
@@ -33,7 +34,7 @@ template <class F> void par_for(size_t n, int n_threads, F f)
 // names / lengths / offsets into seq (AlSeq) and the concatenated sequence bytes (ASCII as in the file, terminators removed).
 bool al_fasta_load_parallel(const char *fn, int n_threads, std::vector<AlSeq> &seqs, AlText &ascii)
 {
-	if (!fn || !strcmp(fn, "-") || getenv("AL_SERIAL_PARSE")) return false;
+	if (!fn || !strcmp(fn, "-") || al_env().serial_parse) return false;
 	const int fd = open(fn, O_RDONLY);
 	if (fd < 0) return false;
 	struct stat sb;

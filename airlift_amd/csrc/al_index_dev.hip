@@ -185,7 +185,7 @@ extern "C" al_idx_t *al_idx_build_device(const char *fn, const al_idxopt_t *io, 
 {
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) { fprintf(stderr, "[airlift] FATAL: al_idx_build_device: no HIP device available\n"); return nullptr; }
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) % n_dev : 0; }
+	device = al_env_pick_device(device, n_dev);
 	if (device >= n_dev) { fprintf(stderr, "[airlift] FATAL: device %d out of range (%d devices)\n", device, n_dev); return nullptr; }
 	const int w = io->w, k = io->k;
 	if (k < 1 || k > AL_MAX_K || w > 32 || w < 1) { fprintf(stderr, "[airlift] al_idx_build_device: needs k <= %d and w <= 32 (got k=%d w=%d)\n", AL_MAX_K, k, w); return nullptr; }
@@ -194,10 +194,10 @@ extern "C" al_idx_t *al_idx_build_device(const char *fn, const al_idxopt_t *io, 
 	al_idx_t *mi = new al_idx_t();
 	mi->k = k; mi->w = w;
 	AlText ascii; uint64_t sum = 0;
-	const bool timing = getenv("AL_TIMING") != nullptr;
+	const bool timing = al_env().timing;
 	struct timespec tq0, tq1, tq2; clock_gettime(CLOCK_MONOTONIC, &tq0);
 	auto secs = [](const struct timespec &a, const struct timespec &b) { return (double)(b.tv_sec - a.tv_sec) + 1e-9 * (double)(b.tv_nsec - a.tv_nsec); };
-	int n_host = getenv("AL_IDX_THREADS") ? atoi(getenv("AL_IDX_THREADS")) : (int)std::min(32u, std::max(1u, std::thread::hardware_concurrency()));
+	int n_host = al_env().idx_threads.value_or((int)std::min(32u, std::max(1u, std::thread::hardware_concurrency())));
 	if (al_fasta_load_parallel(fn, n_host, mi->seq, ascii)) sum = ascii.size();
 	else {
 		AlChunk c;

@@ -145,12 +145,12 @@ int inf_dev_open(InfDev &d, int device, size_t cap_in, size_t cap_out, size_t ca
 {
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return -1; }
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) % n_dev : 0; }
+	device = al_env_pick_device(device, n_dev);
 	hipDeviceProp_t pr;
 	if (hipSetDevice(device) != hipSuccess || hipGetDeviceProperties(&pr, device) != hipSuccess) { (void)hipGetLastError(); return -1; }
 	d.device = device; d.open = true;
 	d.grid = (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 64) * 4;
-	const bool refuse = getenv("AL_TEST_INFLATE_NOMEM") != nullptr;          // (test switch, DESIGN.md section 8: every request is refused)
+	const bool refuse = al_env().test_inflate_nomem;          // (test switch, DESIGN.md section 8: every request is refused)
 	for (int i = 0; i < n_q; ++i) {
 		InfQueue &q = d.q[i];
 		if (hipStreamCreateWithFlags(&q.st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); inf_dev_close(d); return -1; }
@@ -359,17 +359,16 @@ bool AlBgzfIn::open(const char *fn)
 	p = new AlBgzfInImpl();
 	AlBgzfInImpl &I = *p;
 	I.fd = fd; I.n_threads = n_threads;
-	const char *pk = getenv("AL_INFLATE_PIECE_KB");
-	I.piece = (size_t)(pk && atoi(pk) > 0 ? atoi(pk) : 16384) << 10;      // 16 MB hold some 1 000 members of a BAM: the kernel's rate is members in flight
+	I.piece = (size_t)al_env().inflate_piece_kb << 10;      // 16 MB hold some 1 000 members of a BAM: the kernel's rate is members in flight
 	I.cap_in = 2 * I.piece + 65536; I.cap_out = 4 * I.piece + 2 * 65536; I.cap_mem = I.cap_in / 64 + 1024;
-	const char *hs = getenv("AL_TEST_INFLATE_HOST");
+	const bool host_only = al_env().test_inflate_host;
 	int r = -1;
-	if (!(hs && atoi(hs) != 0)) {
+	if (!host_only) {
 		r = inf_dev_open(I.dev, device, I.cap_in, I.cap_out, I.cap_mem, 2);
 		if (r == 0) I.use_dev = true;
 		else fprintf(stderr, "[airlift] --gpu-inflate: %s; the BGZF members are inflated by zlib on %d host thread(s) (the pieces are counted in the AL_TIMING line)\n", r > 0 ? "no device memory for the inflater's buffers" : "no usable device", n_threads);
 	}
-	host_backend = !I.use_dev; fell_back = !I.use_dev && !(hs && atoi(hs) != 0);
+	host_backend = !I.use_dev; fell_back = !I.use_dev && !host_only;
 	bool ok = true;
 	for (AlBgzfInImpl::Slot &s : I.slot) {
 		if (I.use_dev) {

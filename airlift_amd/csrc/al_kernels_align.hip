@@ -2947,9 +2947,14 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 	// (round 5) A small batch's classes do not fill the chip (C2: 32 000 jobs of 9 ... 22 blocks over three kernels, 8 blocks per CU) and every class ends in the
 	// tail of its longest job (the 22-block kernel: 0.85 ms whatever the batch): below AL_DP_CONC jobs (default 700 000; 0: never) the class kernels run side by
 	// side on four streams, each on a workspace range of its own; the per-class intervals of the stage table then hold launch order only.
-	static const long long conc_thr = getenv("AL_DP_CONC") ? atoll(getenv("AL_DP_CONC")) : 700000;
+	const long long conc_thr = al_env().dp_conc;
 	long long n_real = 0; for (int cls = 0; cls < AL_NCLS; ++cls) n_real += (long long)hist[cls];                   // (nj counts two slots per hit, most of them empty)
 	const bool dp_conc = n_real < conc_thr;
+	// most blocks a launch of NB-block jobs gets (AL_CAP4 / 8 / 22: experiments), for the workspace ranges and for the launches alike
+	const auto block_cap = [&](int NB) -> int {
+		const int cap = NB <= 4 ? al_env().cap4 : NB <= 8 ? al_env().cap8 : NB <= 22 ? al_env().cap22 : 2048;
+		return dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap;   // (side by side the ranges add up: slightly fewer blocks each keep the sum near what the largest range was)
+	};
 	size_t ws_off[AL_NCLS + 1]; ws_off[0] = 0;
 	{   // one workspace range for every class of this batch: sized for the largest now, not grown class by class (a regrow frees -- and waits for -- what the running class uses)
 		size_t need = 0;
@@ -2961,9 +2966,7 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 			else if (cls < 9) {
 				const int NB = NBs[cls - 3];
 				const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
-				const int cap = NB <= 4 ? (getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096) : NB <= 8 ? (getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096) : NB <= 22 ? (getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072) : 2048;
-				const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap;   // (side by side the ranges add up: slightly fewer blocks each keep the sum near what the largest range was)
-				int nbj = (int)((cnt + 3) / 4); if (nbj > cap_eff) nbj = cap_eff;
+				const int nbj = std::min((int)((cnt + 3) / 4), block_cap(NB));
 				b = (size_t)nbj * 4 * st2;
 				if (cls == 7) { const unsigned long long c12 = std::min<unsigned long long>(sub7[0], cnt), c16 = std::min<unsigned long long>(sub7[1], cnt - c12), c22 = cnt - c12 - c16;
 				                if (c22 > 0 && c22 <= 8192) b += (size_t)std::min<unsigned long long>((c22 + 3) / 4, (unsigned long long)nbj) * 4 * st2; }   // (a thin 22-block kernel beside the other two of its class: its own range behind theirs)
@@ -2979,8 +2982,7 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 	hipStream_t const s_main = s;
 	bool g12_done = false, thin22_join = false; hipStream_t thin22_stream = nullptr;
 	// two cells per lane (al_dev_ksw2.h) where its arithmetic holds (d_pk_ok); AL_DP_PK=0: the one-cell form everywhere (tests, A/B)
-	static const int pk_env = getenv("AL_DP_PK") ? atoi(getenv("AL_DP_PK")) : 1;
-	const bool dp_pk = pk_env != 0 && d_pk_ok(c->P);
+	const bool dp_pk = al_env().dp_pk && d_pk_ok(c->P);
 	for (int cls = 0; cls < AL_NCLS; ++cls) {
 		const uint32_t cnt = (uint32_t)hist[cls];
 		if (cls == 3) AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_DP_LANE + 1], s));
@@ -3000,15 +3002,14 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 		} else if (cls < 9) {
 			const int NB = NBs[cls - 3];
 			const size_t pb = (((size_t)(Lmax + 16 * NB) * (size_t)(NB + 1) * 16) + 63) / 64 * 64, cw = ((size_t)(Lmax + 16 * NB) + 31) / 16 * 16, st2 = pb + cw * 8;
-			int nbj = (int)((cnt + 3) / 4); { static const int caps[3] = { getenv("AL_CAP4") ? atoi(getenv("AL_CAP4")) : 4096, getenv("AL_CAP8") ? atoi(getenv("AL_CAP8")) : 4096, getenv("AL_CAP22") ? atoi(getenv("AL_CAP22")) : 3072 };
-			  const int cap = NB <= 4 ? caps[0] : NB <= 8 ? caps[1] : NB <= 22 ? caps[2] : 2048; const int cap_eff = dp_conc ? (NB <= 4 ? cap / 2 : NB <= 8 ? cap * 5 / 8 : NB <= 22 ? cap * 5 / 6 : cap) : cap; if (nbj > cap_eff) nbj = cap_eff; }
+			const int nbj = std::min((int)((cnt + 3) / 4), block_cap(NB));
 #define LAUNCH_DP(NBV) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P)
 // (queries of up to 256 bases -- every short-read set -- get the instance with the smaller query arrays: 12 instead of 14 KB of LDS per block at 16 blocks, a third wavefront per SIMD)
 #define LAUNCH_DPK(NBV) do { if (Lmax <= 256) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 256, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); \
 	                         else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp<NBV, 512, NBV * 16, true>), dim3(nbj), dim3(64), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, st2, pb, cw, c->P); } while (0)
-			if (NB == 1) LAUNCH_DP(1); else if (NB == 2) LAUNCH_DP(2); else if (NB == 4) LAUNCH_DP(4); else if (NB == 8) { if (dp_pk) LAUNCH_DPK(8); else LAUNCH_DP(8); } else if (NB == 32) { static const bool pk32 = !(getenv("AL_DP_PK32") && atoi(getenv("AL_DP_PK32")) == 0); if (dp_pk && pk32) LAUNCH_DPK(32); else LAUNCH_DP(32); }
+			if (NB == 1) LAUNCH_DP(1); else if (NB == 2) LAUNCH_DP(2); else if (NB == 4) LAUNCH_DP(4); else if (NB == 8) { if (dp_pk) LAUNCH_DPK(8); else LAUNCH_DP(8); } else if (NB == 32) { if (dp_pk && al_env().dp_pk32) LAUNCH_DPK(32); else LAUNCH_DP(32); }
 			else {   // 9 ... 22 blocks: the sorted slice holds the jobs of <= 12 blocks first, then 13 ... 16, then the rest
-				static const bool split = !getenv("AL_DP_NO_SPLIT");
+				const bool split = !al_env().dp_no_split;
 				const uint32_t c12 = split ? (uint32_t)std::min<unsigned long long>(sub7[0], cnt) : 0u, c16 = split ? (uint32_t)std::min<unsigned long long>(sub7[1], cnt - c12) : 0u, c22 = cnt - c12 - c16;
 				const uint32_t first0 = first, cnt0 = cnt;
 #define LAUNCH_DPS(NBV, F, N) do { if ((N) > 0) { int nb2 = (int)(((N) + 3) / 4); if (nb2 > nbj) nb2 = nbj; \
@@ -3038,7 +3039,7 @@ static int ext_dp_launch_classes(al_ctx_t *c, AlignState *A, const AlignShared &
 			if (tmax <= 512) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<512, 256>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
 			else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ext_dp_lds<1024, 512>), dim3(nbj), dim3(GW), 0, s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, G, E, A->job_idx2.p, first, cnt, gbase, stride, p_bytes, cig_words, c->P);
 		}
-		if (getenv("AL_TRACE")) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: DP class %d (%u jobs) -> %s\n", cls, cnt, hipGetErrorName(e)); }
+		if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: DP class %d (%u jobs) -> %s\n", cls, cnt, hipGetErrorName(e)); }
 		first += cnt;
 	}
 	if (dp_conc) for (int i = 0; i < 3; ++i) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_aux[i], 0)); }
@@ -3099,7 +3100,7 @@ int al_run_align_stage(al_ctx_t *c)
 	    A->seg_u.ensure(2 * nu_total + 2) || A->reg_cnt.ensure(nr + 1) || A->seg_na.ensure(nr + 1) || A->out_off.ensure(nr + 2) || A->seg_fast.ensure(nr + 1) || A->cap2.ensure(nf + 2) || A->b2_off.ensure(nf + 2)) return -1;
 	{   // AL_TEST_SCRUB=<byte> (tests): the stage's work areas -- and the chaining scratch it reuses -- filled with that byte first: a result
 		// that depends on what an earlier stage or batch left there shows up as a difference between two byte values
-		static const char *scrub = getenv("AL_TEST_SCRUB");
+		const char *const scrub = al_env().test_scrub;
 		if (scrub) {
 			const int v = atoi(scrub);
 			AL_HIP_CHECK(hipMemsetAsync(A->regs0.p, v, A->regs0.cap * sizeof(AlReg), s)); AL_HIP_CHECK(hipMemsetAsync(A->aux128.p, v, A->aux128.cap * sizeof(AlAnchor), s));
@@ -3135,7 +3136,7 @@ int al_run_align_stage(al_ctx_t *c)
 		// The classes are disjoint sets of fragments.  Two fill the chip (65 ... 256 and 257 ... 1024 chains: hundreds of thousands of blocks); the
 		// others are a few hundred to a few thousand blocks that sort for a millisecond: on the side streams, beside the two.  4097 ... 8192 chains: the sort tile is 80 KB; its sort
 		// leaves keys and order in the work area for a one-wavefront pass (k_regs_select<-2>).
-		static const int split = getenv("AL_REGS_SPLIT") ? atoi(getenv("AL_REGS_SPLIT")) : 1;   // bit 0: 257 ... 1024 chains sorted and passed over by two kernels as well (4.6 + 2.2 ms against 7.7 in one: the pass alone fits twelve blocks a CU)
+		const int split = al_env().regs_split;   // bit 0: 257 ... 1024 chains sorted and passed over by two kernels as well (4.6 + 2.2 ms against 7.7 in one: the pass alone fits twelve blocks a CU)
 #define LSEL(CAPV, PH, NT, A, B, ST) do { if ((B) > (A)) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_regs_select<CAPV, PH>), dim3((B) - (A)), dim3(NT), 0, ST, c->chained.p, c->u.p, c->uo.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, ord + (A), (int)((B) - (A)), c->P, regs_n0); } while (0)
 		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s));
 		for (int i = 0; i < 3; ++i) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
@@ -3169,7 +3170,7 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipStreamSynchronize(s));
 		Btot2 = b2_total + 8;
 		if (A->mregs.ensure(2 * Btot2) || A->rtmp.ensure(Btot2) || (!map_only && A->rext.ensure(2 * Btot2 + 1))) return -1;
-		{ static const char *scrub = getenv("AL_TEST_SCRUB");
+		{ const char *const scrub = al_env().test_scrub;
 		  if (scrub) { const int v = atoi(scrub); AL_HIP_CHECK(hipMemsetAsync(A->mregs.p, v, A->mregs.cap * sizeof(AlReg), s)); AL_HIP_CHECK(hipMemsetAsync(A->rtmp.p, v, A->rtmp.cap * sizeof(AlReg), s)); if (!map_only) AL_HIP_CHECK(hipMemsetAsync(A->rext.p, v, A->rext.cap * sizeof(RegExt), s)); } }
 		W.mregs = A->mregs.p; W.rtmp = A->rtmp.p; W.rext = map_only ? nullptr : A->rext.p; W.cap2 = A->cap2.p; W.b2_off = A->b2_off.p;
 	}
@@ -3199,8 +3200,8 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0));
 	}
 	hipLaunchKernelGGL(k_regs, dim3((nf + 255) / 256), dim3(256), 0, s, c->chained.p, c->u.p, c->uo.p, c->frag_first.p, c->rd_len.p, c->frag_hash.p, W, nf, c->P, c->counters.p, (const uint32_t *)regs_n0, regs_part);
-	if (getenv("AL_DBG_FRAG")) {   // debugging aid: the chain_post result of one fragment (the kept hits at the front of its regs0 range)
-		const int f = atoi(getenv("AL_DBG_FRAG"));
+	if (al_env().dbg_frag) {   // debugging aid: the chain_post result of one fragment (the kept hits at the front of its regs0 range)
+		const int f = *al_env().dbg_frag;
 		if (f >= 0 && f < nf) {
 			uint64_t o[2]; uint32_t n0v = 0, nu = 0;
 			AL_HIP_CHECK(hipMemcpy(o, A->nu_off.p + f, 16, hipMemcpyDeviceToHost)); AL_HIP_CHECK(hipMemcpy(&nu, c->frag_nu.p + f, 4, hipMemcpyDeviceToHost));
@@ -3221,7 +3222,7 @@ int al_run_align_stage(al_ctx_t *c)
 			}
 		}
 	}
-	if (regs_n0 && getenv("AL_TRACE")) {   // which fragments were left to the one-lane code?
+	if (regs_n0 && al_env().trace) {   // which fragments were left to the one-lane code?
 		std::vector<uint32_t> h0(nf), hu(nf);
 		AL_HIP_CHECK(hipMemcpyAsync(h0.data(), regs_n0, (size_t)nf * 4, hipMemcpyDeviceToHost, s)); AL_HIP_CHECK(hipMemcpyAsync(hu.data(), c->frag_nu.p, (size_t)nf * 4, hipMemcpyDeviceToHost, s));
 		AL_HIP_CHECK(hipStreamSynchronize(s));
@@ -3314,7 +3315,7 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipMemsetAsync(A->hist.p, 0, AL_HIST_N * 8, s));
 		ExtShared E; E.jobs = A->jobs.p; E.outs = A->outs.p; E.rext = A->rext.p; E.job_off = A->job_off.p; E.frag_slow = A->frag_slow.p; E.job_key = A->job_key.p; E.hist = A->hist.p;
 		// fragments with a dozen hits or more (the head of the hits-descending order): a wavefront each, a lane per hit, on the side stream beside the rest
-		static const int heavy_env = getenv("AL_PREP_HEAVY") ? atoi(getenv("AL_PREP_HEAVY")) : AL_PREP_HEAVY;      // (0: every fragment on a lane)
+		const int heavy_env = al_env().prep_heavy.value_or(AL_PREP_HEAVY);      // (0: every fragment on a lane)
 		const int heavy_jobs = frag_ord ? heavy_env : 0;
 		if (heavy_jobs > 0) {
 			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_fj[0], 0));
@@ -3353,7 +3354,7 @@ int al_run_align_stage(al_ctx_t *c)
 			AL_HIP_CHECK(hipStreamSynchronize(s));
 			for (int i = 0; i < AL_NCLS; ++i) c->stat_dp_jobs[i] = hist[i];
 			if (early_mono()) return -1;
-			if (getenv("AL_TRACE")) fprintf(stderr, "[airlift] trace: prep + job sort done\n");
+			if (al_env().trace) fprintf(stderr, "[airlift] trace: prep + job sort done\n");
 			if ((c->P.dbg >> 30) & 1) { fprintf(stderr, "[airlift] DP jobs per class (lane16 lane32 lane64 g1 g2 g4 g8 g22 g32 lds | empty):"); for (int i = 0; i <= AL_NCLS; ++i) fprintf(stderr, " %llu", hist[i]); fprintf(stderr, "\n"); }
 			const DpGeom geom = {Lmax, tmax, stride, p_bytes, cig_words};
 			if (ext_dp_launch_classes(c, A, G, E, s, hist, sub7, geom)) return -1;
@@ -3365,7 +3366,7 @@ int al_run_align_stage(al_ctx_t *c)
 			// Such a fragment's bookkeeping between hits (order, parents, pairing of ~20 x 20 hits on global memory) is a millisecond of one lane
 			// whichever form runs it; sixty-four of them to a wavefront is how a large batch gets through its tens of thousands (1 M pairs: 5.1 ms
 			// against 6.5 ... 8.4 with the wavefront form), while a 262 144-pair batch has few enough for the per-hit part to matter (3.6 -> 2.2 ms).
-			static const int fin_env = getenv("AL_FIN_HEAVY") ? atoi(getenv("AL_FIN_HEAVY")) : -1;                    // (0: every fragment on a lane)
+			const int fin_env = al_env().fin_heavy;                    // (0: every fragment on a lane)
 			const int fin_heavy = !frag_ord ? 0 : fin_env >= 0 ? fin_env : nf <= 400000 ? AL_FIN_HEAVY : 0;
 			if (fin_heavy > 0) {
 				AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0), c->ev_fj[0], 0));   // (not the side stream: the monolithic kernel may still be running there)
@@ -3385,7 +3386,7 @@ int al_run_align_stage(al_ctx_t *c)
 		}
 		if (n_early > 0) AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0));
 		c->stat_n_slow = n_slow + n_early;
-		if (getenv("AL_TRACE")) fprintf(stderr, "[airlift] trace: ext: of %d fragments the monolithic kernel takes %u known after prep (oversize, z-drop in a closed-form flank; side stream) and %u after the DP (CIGAR above the fast path's buffer)\n", nf, n_early, n_slow);
+		if (al_env().trace) fprintf(stderr, "[airlift] trace: ext: of %d fragments the monolithic kernel takes %u known after prep (oversize, z-drop in a closed-form flank; side stream) and %u after the DP (CIGAR above the fast path's buffer)\n", nf, n_early, n_slow);
 		AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_FINISH + 1], s));
 	}
 	AL_HIP_CHECK(hipGetLastError());

@@ -22,6 +22,7 @@
 #include <string>
 #include <vector>
 #include "../../include/airlift.h"
+#include "al_env.h"
 
 // numbers with k/m/g suffixes, as the fork's command line reads -K, -r, -g, -F (mm_parse_num, main.c:87-96)
 static long long parse_num(const char *str, const char *opt)
@@ -136,7 +137,7 @@ int main(int argc, char **argv)
 		}
 		apply_out_sel(mo, sel);
 		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] [--gpu-inflate] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
-		if (!getenv("AL_PG_PLAIN")) al_set_program_line(AL_MM_VERSION, argc, argv);
+		if (!al_env().pg_plain) al_set_program_line(AL_MM_VERSION, argc, argv);
 		if (!k_given) setenv("AL_AUTO_BATCH", "1", 0);
 		int fds[3]; int64_t np = 0, ns = 0;
 		if (al_extract_to_memory_ex(p[1], p[2], read_size, prune, p[3], p[4], fds, &np, &ns, xf, -1, n_threads) != 0) return 1;
@@ -156,7 +157,7 @@ int main(int argc, char **argv)
 	}
 	// @PG as main.c:369 writes it (VN = the fork's MM_VERSION, main.c:16: the version whose records this path reproduces;
 	// CL = this process's argv).  AL_PG_PLAIN=1 leaves the bare line (the tests' goldens come from a driver without argv).
-	if (!getenv("AL_PG_PLAIN")) al_set_program_line(AL_MM_VERSION, argc, argv);
+	if (!al_env().pg_plain) al_set_program_line(AL_MM_VERSION, argc, argv);
 	if (!strcmp(argv[1], "mem")) mode = MODE_MEM, i = 2;
 	else if (!strcmp(argv[1], "aln")) mode = MODE_ALN, i = 2;
 	else if (!strcmp(argv[1], "samse")) mode = MODE_SAMSE, i = 2;
@@ -211,8 +212,8 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--rank") && i + 1 < argc) rank = atoi(argv[++i]);             // one process per GPU: --rank r --world R -o OUT (al_map_file_frag_ranked)
 		else if (!strcmp(a, "--world") && i + 1 < argc) world = atoi(argv[++i]);
 		else if (!strcmp(a, "--ranked")) {                                                 // ... with rank and world from the launcher's environment (torchrun: RANK, WORLD_SIZE; the GPU is LOCAL_RANK)
-			if (!getenv("RANK") || !getenv("WORLD_SIZE")) { fprintf(stderr, "[ERROR] --ranked needs RANK and WORLD_SIZE in the environment\n"); return 1; }
-			rank = atoi(getenv("RANK")); world = atoi(getenv("WORLD_SIZE"));
+			if (!al_env_rank() || !al_env_world_size()) { fprintf(stderr, "[ERROR] --ranked needs RANK and WORLD_SIZE in the environment\n"); return 1; }
+			rank = *al_env_rank(); world = *al_env_world_size();
 		}
 		else if (!strcmp(a, "--rendezvous") && i + 1 < argc) rendezvous = argv[++i];
 		else if (!strcmp(a, "--devices") && i + 1 < argc) {   // "0-7", "0,1,2", "0,0" (two lanes on one GPU): reads of every mini-batch sharded over the lanes
@@ -246,7 +247,7 @@ int main(int argc, char **argv)
 	}
 	// one process per GPU?  (--world, or --rank / --ranked with the launcher's WORLD_SIZE.)  Anything else -- also WORLD_SIZE = 1, or WORLD_SIZE set
 	// without --rank / --ranked -- is a single process and writes -o FILE itself (main.c:183-190).
-	if (world <= 0 && rank >= 0 && getenv("WORLD_SIZE")) world = atoi(getenv("WORLD_SIZE"));
+	if (world <= 0 && rank >= 0 && al_env_world_size()) world = *al_env_world_size();
 	if (world <= 1 && out_path && strcmp(out_path, "-") != 0 && !freopen(out_path, "wb", stdout)) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", out_path); return 1; }
 	// -K given: an upper bound of the bases per device batch.  Not given: the stream driver (plain FASTQ in, SAM out) sizes its batches
 	// from the free device memory (al_stream_pipe.cpp); the host driver keeps the preset's 50 Mbases, as the reference.
@@ -268,14 +269,14 @@ int main(int argc, char **argv)
 	if (!devices.empty()) device = devices[0];
 	// plain FASTQ files in, SAM out, one GPU: the run's device memory is obtained by a background thread while the reference is loaded and indexed
 	const bool ref_is_idx = al_idx_is_idx(ref) > 0;                              // index.c:585-600: a prebuilt index (the fork's -d file, or this program's) instead of a FASTA
-	if (devices.size() <= 1 && world <= 1 && !bam_mode && !count_only && mode != MODE_TOKENS && !getenv("AL_HOST_INDEX") && !getenv("AL_HOST_IO") && !ref_is_idx && !reads.empty()) {
+	if (devices.size() <= 1 && world <= 1 && !bam_mode && !count_only && mode != MODE_TOKENS && !al_env().host_index && !al_env().host_io && !ref_is_idx && !reads.empty()) {
 		const int64_t rb = al_device_reserve_for_run(device, ref, (int)reads.size(), reads.data());
-		if (rb > 0 && getenv("AL_TIMING")) fprintf(stderr, "[airlift] device memory reserve of %.1f GB started\n", rb / 1e9);
+		if (rb > 0 && al_env().timing) fprintf(stderr, "[airlift] device memory reserve of %.1f GB started\n", rb / 1e9);
 	}
-	al_idx_t *mi = ref_is_idx ? al_idx_load(ref) : getenv("AL_HOST_INDEX") ? al_idx_build(ref, &io, n_threads) : al_idx_build_device(ref, &io, device);
+	al_idx_t *mi = ref_is_idx ? al_idx_load(ref) : al_env().host_index ? al_idx_build(ref, &io, n_threads) : al_idx_build_device(ref, &io, device);
 	if (mi && ref_is_idx && (al_idx_k(mi) != io.k || al_idx_w(mi) != io.w)) fprintf(stderr, "[WARNING]\033[1;31m Indexing parameters (-k, -w or -H) overridden by parameters used in the prebuilt index.\033[0m\n");   // main.c:378-380
 	clock_gettime(CLOCK_MONOTONIC, &ts1);
-	if (getenv("AL_TIMING")) fprintf(stderr, "[airlift] index build %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
+	if (al_env().timing) fprintf(stderr, "[airlift] index build %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
 	if (!mi) { fprintf(stderr, "[ERROR] failed to open file '%s'\n", ref); return 1; }
 	if (dump_fn && !ref_is_idx && al_idx_dump(dump_fn, mi) != 0) { al_idx_destroy(mi); return 1; }
 	if (reads.empty()) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
@@ -299,7 +300,7 @@ int main(int argc, char **argv)
 		_exit(0);
 	}
 	if (world > 1) {   // one process per GPU
-		if (rank < 0 && getenv("RANK")) rank = atoi(getenv("RANK"));
+		if (rank < 0 && al_env_rank()) rank = *al_env_rank();
 		if (rank < 0 || rank >= world || !out_path || bam_mode == 2) { fprintf(stderr, "[ERROR] a multi-process run needs --rank r (or RANK) below --world, -o FILE after --world, and SAM or unsorted BAM output\n"); return 1; }
 		const int rc2 = bam_mode ? al_map_file_frag_ranked_bam(mi, (int)reads.size(), reads.data(), &mo, n_threads, out_path, rg, device, rank, world, rendezvous, 0.0, bam_level)
 		                         : al_map_file_frag_ranked(mi, (int)reads.size(), reads.data(), &mo, n_threads, out_path, rg, device, rank, world, rendezvous, 0.0);
@@ -313,12 +314,12 @@ int main(int argc, char **argv)
 	clock_gettime(CLOCK_MONOTONIC, &ts0);
 	al_idx_destroy(mi);
 	clock_gettime(CLOCK_MONOTONIC, &ts1);
-	if (getenv("AL_TIMING")) fprintf(stderr, "[airlift] index release %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
+	if (al_env().timing) fprintf(stderr, "[airlift] index release %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
 	if (fflush(stdout) == EOF) { perror("[ERROR] failed to write the results"); return 1; }
 	clock_gettime(CLOCK_MONOTONIC, &ts1);
-	if (getenv("AL_TIMING")) { fprintf(stderr, "[airlift] main() %.3f s\n", (ts1.tv_sec - tsm.tv_sec) + 1e-9 * (ts1.tv_nsec - tsm.tv_nsec)); al_device_reserve_report(stderr); }
+	if (al_env().timing) { fprintf(stderr, "[airlift] main() %.3f s\n", (ts1.tv_sec - tsm.tv_sec) + 1e-9 * (ts1.tv_nsec - tsm.tv_nsec)); al_device_reserve_report(stderr); }
 	// results are flushed and every device object is released: skip the HIP runtime's static teardown (0.3 s)
 	fflush(stderr);
-	if (getenv("AL_NO_FAST_EXIT")) return rc == 0 ? 0 : 1;          // (profilers flush their traces from exit handlers)
+	if (al_env().no_fast_exit) return rc == 0 ? 0 : 1;          // (profilers flush their traces from exit handlers)
 	_exit(rc == 0 ? 0 : 1);
 }

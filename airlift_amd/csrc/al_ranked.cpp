@@ -51,7 +51,7 @@ struct ProcExchange {
 static std::string g_nonce;                                // set once the launch's token has been agreed on (al_map_file_frag_ranked): part of every file name below
 static std::string run_id_base()
 {
-	for (const char *k : {"AL_RUN_ID", "TORCHELASTIC_RUN_ID", "MASTER_PORT"}) { const char *v = getenv(k); if (v && *v) { std::string s; for (const char *p = v; *p; ++p) s.push_back((*p >= '0' && *p <= '9') || (*p >= 'a' && *p <= 'z') || (*p >= 'A' && *p <= 'Z') ? *p : '_'); return s; } }
+	if (const char *v = al_env_run_id()) { std::string s; for (const char *p = v; *p; ++p) s.push_back((*p >= '0' && *p <= '9') || (*p >= 'a' && *p <= 'z') || (*p >= 'A' && *p <= 'Z') ? *p : '_'); return s; }
 	return "p" + std::to_string((long long)getppid());
 }
 static std::string run_id() { return g_nonce.empty() ? run_id_base() : run_id_base() + "_" + g_nonce; }
@@ -331,7 +331,7 @@ int find_grid(const char *const *fn, int n_fn, int rank, int world, int n_thread
 	// batch size: what a long input's batches hold in a single process (262144 pairs), less for a short input so that every rank has a few batches; AL_RANK_BATCH (records) overrides
 	uint64_t G = n_fn == 2 ? 262144u : 524288u;
 	{ const uint64_t per = (R + 4ULL * (uint64_t)world - 1) / (4ULL * (uint64_t)world); if (per < G) G = per ? per : 1; }
-	if (getenv("AL_RANK_BATCH") && atoll(getenv("AL_RANK_BATCH")) > 0) G = (uint64_t)atoll(getenv("AL_RANK_BATCH"));
+	if (al_env_rank_batch() > 0) G = (uint64_t)al_env_rank_batch();
 	if (n_fn == 1 && (G & 1)) ++G;                                   // (one interleaved file: a pair's two records stay in one batch)
 	gp->G = G; gp->records = R; gp->n_grid = (R + G - 1) / G;
 	const uint64_t ng = gp->n_grid;
@@ -434,17 +434,17 @@ static int map_ranked(const al_idx_t *mi, int n_fn, const char **fn, const al_ma
                       int device, int rank, int world, const char *rendezvous, double timeout_s, int bam, int bam_level)
 {
 	if (!mi || !fn || !out_path || n_fn < 1 || n_fn > 2 || world < 1 || rank < 0 || rank >= world) return -1;
-	if (timeout_s <= 0) timeout_s = getenv("AL_RANK_TIMEOUT") ? atof(getenv("AL_RANK_TIMEOUT")) : 600.0;
+	if (timeout_s <= 0) timeout_s = al_env().rank_timeout;
 	std::string dir = rendezvous && *rendezvous ? rendezvous : std::string(out_path);
 	if (!(rendezvous && *rendezvous)) { const size_t sl = dir.rfind('/'); dir = sl == std::string::npos ? "." : dir.substr(0, sl ? sl : 1); }
-	const bool timing = getenv("AL_TIMING") != nullptr;
+	const bool timing = al_env().timing;
 	int n_dev = 0; (void)hipGetDeviceCount(&n_dev);
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) : rank; if (n_dev > 0) device %= n_dev; }
+	device = al_env_pick_device(device, n_dev, rank);
 	// the launch's token (see agree_on_token), then the exchange: RCCL when the ranks sit on distinct GPUs, files otherwise
-	if (world > 1 && !getenv("AL_RUN_ID")) { const int e = agree_on_token(dir, rank, world, timeout_s); if (e) return e; }   // (AL_RUN_ID: the caller vouches for a fresh id)
+	if (world > 1 && !al_env_run_id_vouched()) { const int e = agree_on_token(dir, rank, world, timeout_s); if (e) return e; }   // (AL_RUN_ID: the caller vouches for a fresh id)
 	std::unique_ptr<FileExchange> fex(new FileExchange(dir, rank, world, timeout_s)); std::unique_ptr<RcclProcExchange> rx;
 	ProcExchange *ex = fex.get();
-	if (world > 1 && !getenv("AL_NO_RCCL") && n_dev >= world) {
+	if (world > 1 && !al_env().no_rccl && n_dev >= world) {
 		// every rank tells its device first (through the files): a communicator cannot hold one GPU twice
 		uint64_t d = (uint64_t)device; std::vector<uint64_t> all((size_t)world);
 		if (ex->allgather(&d, 1, all.data())) return -2;

@@ -8,6 +8,7 @@
 #include <chrono>
 #include "al_internal.h"
 #include "al_stream_plan.h"
+#include "al_env.h"
 
 // Set when a device allocation fails; al_batch_run reports AL_ERR_NOMEM then (the context stays usable: every DevBuf is
 // either at its old size or empty, and the caller may upload a smaller batch).
@@ -41,7 +42,7 @@ template <typename T> struct DevBuf {       // grow-only device array
 	{
 		if (n <= cap) return 0;
 		al_alloc_site() = AlAllocSite{file, line};
-		static const size_t big_div = getenv("AL_GROW_DIV") ? (size_t)std::max(1, atoi(getenv("AL_GROW_DIV"))) : 8;
+		const size_t big_div = (size_t)al_env().grow_div;
 		const size_t ncap = n + (n * sizeof(T) >= ((size_t)256 << 20) ? n / big_div : n / 4) + 64;   // headroom against regrowing: an eighth for the large arrays (batches of one run differ by a few per cent), a quarter for the small
 		T *np = nullptr;
 		if (!keep && p) { al_dev_free(p); p = nullptr; cap = 0; }         // contents not needed: release first, so the peak is one copy

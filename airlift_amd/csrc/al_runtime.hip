@@ -97,7 +97,7 @@ int al_dev_guard_check()
 }
 hipError_t al_dev_malloc(void **p, size_t bytes)
 {
-	static const char *poison = getenv("AL_TEST_POISON"), *only = getenv("AL_TEST_POISON_ONLY"), *plog = getenv("AL_TEST_POISON_LOG"), *guard = getenv("AL_TEST_GUARD");
+	const char *const poison = al_env().test_poison, *const only = al_env().test_poison_only; const bool plog = al_env().test_poison_log, guard = al_env().test_guard;
 	if (guard) {
 		void *raw = nullptr;
 		const hipError_t e = al_dev_malloc_raw(&raw, bytes + 2 * GUARD);
@@ -120,8 +120,7 @@ hipError_t al_dev_malloc(void **p, size_t bytes)
 void al_dev_free(void *p)
 {
 	if (!p) return;
-	static const char *guard = getenv("AL_TEST_GUARD");
-	if (guard) {
+	if (al_env().test_guard) {
 		GuardRec r{0, -1}; bool found = false;
 		{ std::lock_guard<std::mutex> l(g_guard_m); auto it = g_guard.find(p); if (it != g_guard.end()) { r = it->second; found = true; g_guard.erase(it); } }
 		if (found) { (void)guard_check_one(p, r); al_dev_free_raw((char *)p - GUARD); return; }
@@ -205,7 +204,7 @@ size_t pool_release_free(void)
 		}
 	}
 	for (char *q : rel) (void)hipFree(q);
-	if (bytes && getenv("AL_TIMING")) fprintf(stderr, "[airlift] device memory reserve: %.1f GB in %zu unused chunk(s) given back to the driver for a request the reserve could not serve\n", bytes / 1e9, rel.size());
+	if (bytes && al_env().timing) fprintf(stderr, "[airlift] device memory reserve: %.1f GB in %zu unused chunk(s) given back to the driver for a request the reserve could not serve\n", bytes / 1e9, rel.size());
 	return bytes;
 }
 }
@@ -215,7 +214,7 @@ extern "C" int al_device_reserve(int device, uint64_t bytes)
 	DevPool &P = pool();
 	int n_dev = 0;
 	if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev <= 0) return -1;
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) % n_dev : 0; }
+	device = al_env_pick_device(device, n_dev);
 	if (device >= n_dev || bytes == 0) return -1;
 	{
 		std::lock_guard<std::mutex> l(P.m);
@@ -223,7 +222,7 @@ extern "C" int al_device_reserve(int device, uint64_t bytes)
 		size_t free_b = 0, total_b = 0;
 		if (hipSetDevice(device) != hipSuccess || hipMemGetInfo(&free_b, &total_b) != hipSuccess) return -1;
 		P.device = device; P.target = (size_t)std::min<uint64_t>(bytes, (uint64_t)((double)free_b * 0.92));
-		static const double chunk_gb = getenv("AL_POOL_CHUNK_GB") ? atof(getenv("AL_POOL_CHUNK_GB")) : 0.0;
+		const double chunk_gb = al_env().pool_chunk_gb;
 		P.chunk = chunk_gb > 0 ? (size_t)(chunk_gb * 1e9) : std::min<size_t>(std::max<size_t>(P.target / 6, (size_t)2 << 30), (size_t)24 << 30);
 		P.chunk = P.chunk / POOL_ALIGN * POOL_ALIGN;
 		P.started = true; P.filling = true;
@@ -260,13 +259,12 @@ extern "C" int al_device_reserve(int device, uint64_t bytes)
 // (default 200 M: ~20 s of pipeline, 7 % of which is 1.4 s).
 double al_long_batch_cap(double reads)
 {
-	static const double fixed = getenv("AL_LONG_BATCH") ? atof(getenv("AL_LONG_BATCH")) : 0.0;
-	static const double big_from = getenv("AL_LONG_BATCH_BIG_FROM") ? atof(getenv("AL_LONG_BATCH_BIG_FROM")) : 2.0e8;
+	const double fixed = al_env().long_batch, big_from = al_env().long_batch_big_from;
 	return fixed > 0 ? fixed : reads >= big_from ? 1048576.0 : 524288.0;
 }
 extern "C" int64_t al_device_reserve_for_run(int device, const char *ref_fn, int n_fn, const char *const *fn)
 {
-	if (getenv("AL_NO_RESERVE")) return 0;
+	if (al_env().no_reserve) return 0;
 	struct stat sb;
 	if (!ref_fn || stat(ref_fn, &sb) != 0 || !S_ISREG(sb.st_mode)) return 0;
 	const double G = (double)sb.st_size;
@@ -277,7 +275,7 @@ extern "C" int64_t al_device_reserve_for_run(int device, const char *ref_fn, int
 	const double n_min = G / 5.7;
 	double tab = 32.0; while (tab < 2.0 * 0.9 * n_min + 2.0) tab *= 2.0; tab *= 16.0;
 	const double index = 0.5 * G + 8.0 * n_min + tab, build_tmp = G + 4.0 * 8.0 * n_min + 4.0 * n_min;
-	const double kb = getenv("AL_RESERVE_KB_PER_READ") ? atof(getenv("AL_RESERVE_KB_PER_READ")) : G >= 1.0e9 ? 85.0 : G >= 2.0e8 ? 40.0 : 12.0;
+	const double kb = al_env().reserve_kb_per_read.value_or(G >= 1.0e9 ? 85.0 : G >= 2.0e8 ? 40.0 : 12.0);
 	const bool long_input = reads >= 3.0e6;
 	// (a long input's batch by the stream driver's own rule: at least three batches per context)
 	const double batch = long_input ? std::min(al_long_batch_cap(reads), std::max(262144.0, reads / 6.0)) : std::min(131072.0, reads), n_ctx = long_input ? 2.0 : 3.0, n_slots = long_input ? 4.0 : 5.0;
@@ -329,7 +327,7 @@ extern "C" void al_device_reserve_reset_peak(void) { DevPool &P = pool(); if (!P
 static size_t pool_release_free_chunks();
 static hipError_t al_hip_malloc_margin(void **p, size_t bytes)
 {
-	static const size_t margin = (size_t)(getenv("AL_HBM_MARGIN_MB") ? std::max(0, atoi(getenv("AL_HBM_MARGIN_MB"))) : 2048) << 20;
+	const size_t margin = (size_t)al_env().hbm_margin_mb << 20;
 	for (int attempt = 0; attempt < 2; ++attempt) {
 		size_t fr = 0, tot = 0;
 		const bool known = hipMemGetInfo(&fr, &tot) == hipSuccess;
@@ -350,8 +348,7 @@ static hipError_t al_dev_malloc_raw(void **p, size_t bytes)
 	hipError_t e = hipSuccess;
 	if (void *q = pool_alloc(bytes)) *p = q; else e = al_hip_malloc_margin(p, bytes);
 	{ AlAllocStat &a = al_alloc_stat(); const long long ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); a.dev_ns += ns; a.dev_bytes += (long long)bytes; ++a.dev_calls;
-	  static const bool tr = getenv("AL_TRACE_ALLOC") != nullptr;
-	  if (tr && bytes >= (32u << 20)) { const AlAllocSite &w = al_alloc_site(); const char *b = strrchr(w.file, '/'); fprintf(stderr, "[airlift] alloc: %8.1f MB in %7.1f ms for %s:%d\n", bytes / 1e6, ns / 1e6, b ? b + 1 : w.file, w.line); } }
+	  if (al_env().trace_alloc && bytes >= (32u << 20)) { const AlAllocSite &w = al_alloc_site(); const char *b = strrchr(w.file, '/'); fprintf(stderr, "[airlift] alloc: %8.1f MB in %7.1f ms for %s:%d\n", bytes / 1e6, ns / 1e6, b ? b + 1 : w.file, w.line); } }
 	al_alloc_site() = AlAllocSite{"", 0};
 	std::atomic<size_t> *a = al_acct();
 	if (e == hipSuccess && a) { a->fetch_add(bytes); std::lock_guard<std::mutex> l(g_own_m); g_own[*p] = OwnRec{bytes, a}; }
@@ -428,7 +425,7 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 		fprintf(stderr, "[airlift] FATAL: no HIP device available -- this library has no CPU path\n");
 		return nullptr;
 	}
-	if (device < 0) { const char *lr = getenv("LOCAL_RANK"); device = lr ? atoi(lr) % n_dev : 0; }
+	device = al_env_pick_device(device, n_dev);
 	if (device >= n_dev) { fprintf(stderr, "[airlift] FATAL: device %d out of range (%d devices)\n", device, n_dev); return nullptr; }
 	if (mi->w > 32 || mi->k > AL_MAX_K) { fprintf(stderr, "[airlift] FATAL: device sketch supports w <= 32, k <= %d\n", AL_MAX_K); return nullptr; }
 	al_ctx_t *c = new al_ctx_t();
@@ -438,17 +435,17 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 	// As many streams as the process has hardware queues (al_stream_plan.h): AL_STREAMS (1 ... 10: tests, experiments), else GPU_MAX_HW_QUEUES as the
 	// environment has it (HIP's default of 4 when it is unset), at most one per role.  The library only reads the variable.
 	static const char *const src_names[4] = {"AL_STREAMS", "GPU_MAX_HW_QUEUES in the environment", "default", "AL_STREAM_MAP"};
-	static int src = 0; static const int n_phys_proc = al_stream_count(getenv("AL_STREAMS"), getenv("GPU_MAX_HW_QUEUES"), &src);
+	static int src = 0; static const int n_phys_proc = al_stream_count(al_env().streams, al_env().gpu_max_hw_queues, &src);
 	c->n_phys = n_phys_proc; al_stream_plan(c->n_phys, c->role_map);
-	{ static uint8_t map_env[AL_ROLE_N]; static const int n_env = al_stream_map_parse(getenv("AL_STREAM_MAP"), map_env);   // (experiments: an explicit map)
+	{ static uint8_t map_env[AL_ROLE_N]; static const int n_env = al_stream_map_parse(al_env().stream_map, map_env);   // (experiments: an explicit map)
 	  if (n_env > 0) { c->n_phys = n_env; memcpy(c->role_map, map_env, sizeof(map_env)); src = 3; } }
-	{ static std::once_flag once; static const bool timing = getenv("AL_TIMING") && atoi(getenv("AL_TIMING")) != 0;
-	  if (timing) std::call_once(once, [&] { fprintf(stderr, "[airlift] streams: %d physical for %d roles (%s)\n", c->n_phys, (int)AL_ROLE_N, src_names[src]); }); }
+	{ static std::once_flag once;
+	  if (al_env().timing_nonzero) std::call_once(once, [&] { fprintf(stderr, "[airlift] streams: %d physical for %d roles (%s)\n", c->n_phys, (int)AL_ROLE_N, src_names[src]); }); }
 	// AL_SIDE_PRIO=1 (experiment): the side streams at the highest stream priority.  Their thin classes then get CU slots ahead of the small
 	// blocks of the kernels beside them, but the main stream's kernel does not start before they are all placed and the hardware queues are
 	// shared out differently: measured 3 ms slower per C4 step than equal priorities.
 	int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-	static const bool side_hi = getenv("AL_SIDE_PRIO") && atoi(getenv("AL_SIDE_PRIO")) == 1;
+	const bool side_hi = al_env().side_prio;
 	if (hipStreamCreateWithFlags(&c->phys[0], hipStreamNonBlocking) != hipSuccess) { delete c; return nullptr; }
 	c->stream = c->phys[0];
 	for (int p = 1; p < c->n_phys; ++p) {   // a stream that carries side or aux0-2 has their priority
@@ -467,11 +464,11 @@ extern "C" al_ctx_t *al_ctx_init(const al_idx_t *mi, const al_mapopt_t *opt, int
 	P.mask_level = opt->mask_level; P.pri_ratio = opt->pri_ratio; P.max_clip_ratio = opt->max_clip_ratio; P.best_n = opt->best_n;
 	P.a = opt->a; P.b = opt->b; P.q = opt->q; P.e = opt->e; P.q2 = opt->q2; P.e2 = opt->e2; P.sc_ambi = opt->sc_ambi; P.zdrop = opt->zdrop; P.zdrop_inv = opt->zdrop_inv;
 	P.end_bonus = opt->end_bonus; P.min_dp_max = opt->min_dp_max; P.pe_ori = opt->pe_ori; P.pe_bonus = opt->pe_bonus; P.mid_occ = opt->mid_occ; P.max_occ = opt->max_occ;
-	{ const char *d = getenv("AL_DBG"); P.dbg = d ? atoi(d) : 0; if (P.dbg) fprintf(stderr, "[airlift] AL_DBG=%d: timing experiment, results are NOT valid\n", P.dbg); }
-	{ const char *d = getenv("AL_DBG2"); P.dbg2 = d ? atoi(d) : 0; if (P.dbg2 & ~32) fprintf(stderr, "[airlift] AL_DBG2=%d: timing experiment, results are NOT valid\n", P.dbg2); }
-	{ const char *d = getenv("AL_DP_EXIT"); P.dp_exit = d ? atoi(d) != 0 : 1; }
-	{ const char *d = getenv("AL_DP_EXIT_STRIDE"); const int v = d ? atoi(d) : 8; const bool ok = v == 1 || v == 2 || v == 4 || v == 8; P.dp_exit_stride = ok ? v : 8;
-	  if (!ok) fprintf(stderr, "[airlift] AL_DP_EXIT_STRIDE=%s is not 1, 2, 4 or 8: using 8\n", d); }
+	const AlEnvCtx ce = al_env_ctx();                                  // (read at every context's creation: al_env.h)
+	P.dbg = ce.dbg; P.dbg2 = ce.dbg2; P.dp_exit = ce.dp_exit; P.dp_exit_stride = ce.dp_exit_stride;
+	if (P.dbg) fprintf(stderr, "[airlift] AL_DBG=%d: timing experiment, results are NOT valid\n", P.dbg);
+	if (P.dbg2 & ~32) fprintf(stderr, "[airlift] AL_DBG2=%d: timing experiment, results are NOT valid\n", P.dbg2);
+	if (ce.dp_exit_stride_refused) fprintf(stderr, "[airlift] AL_DP_EXIT_STRIDE=%s is not 1, 2, 4 or 8: using 8\n", ce.dp_exit_stride_refused);
 	memset(&c->stat, 0, sizeof(c->stat));
 	return c;
 }
@@ -686,8 +683,9 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 	if (c->seg_cnt.ensure((size_t)n + 2) || c->seg_first.ensure((size_t)n + 2) || c->seg_cnt0.ensure((size_t)n + 2) || c->seg_first0.ensure((size_t)n + 2)) return -1;
 	// (fragments of more than AL_SEGS_BIG anchors: eight wavefronts each, launched first; big8_from: the entries before it have at most 8192 anchors)
 	// (tests lower the two sizes so that ordinary fragments take the eight-wavefront forms; the list positions are then no bound any more)
-	static const int segs_big = getenv("AL_TEST_SEG_BIG") ? atoi(getenv("AL_TEST_SEG_BIG")) : 8192, segm_big = getenv("AL_TEST_SEG_BIG") ? std::max(1, atoi(getenv("AL_TEST_SEG_BIG")) / 8) : 1024;
-	if (getenv("AL_TEST_SEG_BIG")) { big_from = 0; big8_from = 0; }
+	const std::optional<int> &seg_big = al_env().test_seg_big;
+	const int segs_big = seg_big.value_or(8192), segm_big = seg_big ? std::max(1, *seg_big / 8) : 1024;
+	if (seg_big) { big_from = 0; big8_from = 0; }
 	if (big8_from < 0 || big8_from > n) big8_from = 0;
 	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order + big8_from, n - big8_from, c->P, lmin, 0,
 	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, c->seg_cnt.p + big8_from, c->seg_cnt0.p + big8_from, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
@@ -723,15 +721,14 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 		static const uint32_t thr[8] = {2, 3, 4, 5, 6, 7, 8, 9};
 		if (lower_bounds(c, c->seg_key.p, (uint32_t)n1, thr, 8, lb)) return -1;
 	}
-	{ static const bool tr = getenv("AL_TRACE") != nullptr;
-	  if (tr && first) fprintf(stderr, "[airlift] trace: segments: %d in %d fragments; by size <=16:%d <=24:%u <=32:%u <=48:%u <=64:%u <=128:%u more:%u\n", ns, n,
-	                          ns0, lb[0], lb[1] - lb[0], lb[3] - lb[1], lb[4] - lb[3], lb[7] - lb[4], (uint32_t)n1 - lb[7]); }
+	if (al_env().trace && first) fprintf(stderr, "[airlift] trace: segments: %d in %d fragments; by size <=16:%d <=24:%u <=32:%u <=48:%u <=64:%u <=128:%u more:%u\n", ns, n,
+	                          ns0, lb[0], lb[1] - lb[0], lb[3] - lb[1], lb[4] - lb[3], lb[7] - lb[4], (uint32_t)n1 - lb[7]);
 	if (ev(ST_SEG_FIND)) return -1;
 	const bool keys_possible = c->opt.min_cnt >= 2;                           // a chain has >= 2 anchors: the keys of a segment fit half of its range
 	const bool keep_keys = with_keys && keys_possible;
 	const ChainSeg sg{c->vs_meta.p, (uint32_t *)c->vs_res.p, nullptr, 0, keep_keys ? c->okey_tmp.p : nullptr};
 	bool thin[4] = {false, false, false, false};
-	static const uint32_t wave_max = getenv("AL_CHAIN_WAVE_MAX") ? (uint32_t)atoi(getenv("AL_CHAIN_WAVE_MAX")) : 8192u;   // (tests: 0 = never, a large value = always)
+	const uint32_t wave_max = al_env().chain_wave_max;   // (tests: 0 = never, a large value = always)
 	if (ns > 0) {
 		const uint32_t *so0 = c->seg_idx.p, *so1 = c->seg_ord.p;
 		if (lds_ok) {
@@ -752,7 +749,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 #define LWAVE(LIST, N) do { const int nw__ = (N); if (nw__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(nw__), dim3(64), 0, s, c->anchors.p, c->vs_off.p, c->vs_na.p, c->frag_first.p, c->rd_len.p, c->chain_tmp.p, c->u_tmp.p, (uint32_t *)nullptr, \
 		                               c->ws_i32.p, c->ws_u64.p, (LIST), nw__, c->P, c->counters.p, sg); } while (0)
 		const int nw = lds_ok ? n1 - (int)lb[7] : ns;
-		{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr && nw > 0) fprintf(stderr, "[airlift] trace: %d segments to the wavefront kernel (of %d segments in %d fragments)\n", nw, ns, n); }
+		if (al_env().trace && nw > 0) fprintf(stderr, "[airlift] trace: %d segments to the wavefront kernel (of %d segments in %d fragments)\n", nw, ns, n);
 		if (lds_ok) { LWAVE(so1 + lb[7], n1 - (int)lb[7]); for (int k = 3; k < 7; ++k) if (thin[k - 3]) LWAVE(so1 + lb[k], (int)(lb[k + 1] - lb[k])); } else { LWAVE(so0, ns0); LWAVE(so1, n1); }
 #undef LWAVE
 		if (ev(ST_SEG_CHAIN_WAVE)) return -1;
@@ -779,7 +776,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 	const uint32_t *fb = c->fb_list.p;
 	if (n_fb > 0 && keep_keys) {   // order restated from the merged chains and their processing keys; only what does not fit its tile is chained again
 		const size_t lds = (size_t)AL_ORD_CAP * (8 + 4 + 2) + 64, lds16 = (size_t)AL_ORD_CAP2 * (8 + 2) + 64;   // (lds16 >= lds: the block form keeps the one-wavefront layout up to AL_ORD_CAP chains)
-		static const int nu_block = getenv("AL_ORDER_BLOCK") ? atoi(getenv("AL_ORDER_BLOCK")) : 128;             // chains from which a block of 16 wavefronts takes the fragment
+		const int nu_block = al_env().order_block;             // chains from which a block of 16 wavefronts takes the fragment
 		if (!c->attr_chain_order) {
 			AL_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_order_t<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
 			AL_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_order_t<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
@@ -794,7 +791,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 		fb = c->fb2_list.p;
 	}
 	const ChainSeg whole{nullptr, nullptr, nullptr, 0, nullptr};
-	{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) fprintf(stderr, "[airlift] trace: chain order: %llu fragments with tied chain starts among > 64 chains (%s keys), %u of them chained whole by the wavefront kernel\n", (unsigned long long)c->n_chain_fallback, keep_keys ? "with" : "without", n_fb); }
+	if (al_env().trace) fprintf(stderr, "[airlift] trace: chain order: %llu fragments with tied chain starts among > 64 chains (%s keys), %u of them chained whole by the wavefront kernel\n", (unsigned long long)c->n_chain_fallback, keep_keys ? "with" : "without", n_fb);
 	if (n_fb > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(n_fb), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
 	                                 c->ws_i32.p, c->ws_u64.p, fb, (int)n_fb, c->P, c->counters.p, whole);
 	if (ev(ST_SEG_MERGE)) return -1;
@@ -828,7 +825,7 @@ static int chain_fallback(al_ctx_t *c, const uint32_t *fb, int n_fb, bool lds_ok
 	uint64_t vt = 0;
 	AL_HIP_CHECK(hipMemcpyAsync(&vt, c->v_a_off.p + n_fb, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
-	{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) fprintf(stderr, "[airlift] trace: chain fallback: %d fragments, %llu anchors, through the segment-wise kernels\n", n_fb, (unsigned long long)vt); }
+	if (al_env().trace) fprintf(stderr, "[airlift] trace: chain fallback: %d fragments, %llu anchors, through the segment-wise kernels\n", n_fb, (unsigned long long)vt);
 	if (c->v_anchors.ensure(vt + 1, false, s) || c->v_chained.ensure(vt + 1, false, s) || c->v_u.ensure(vt + (uint64_t)n_fb + 2, false, s) ||
 	    c->ws_i32.ensure(vt * 4 + 4, false, s) || c->ws_u64.ensure(vt + 1, false, s) || c->chain_tmp.ensure(vt + 1, false, s) || c->u_tmp.ensure(vt + 1, false, s) || c->okey_tmp.ensure(vt + 2, false, s)) return -1;
 	hipLaunchKernelGGL(k_fb_reads, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_first.p, c->rd_len.p, c->v_first64.p, c->v_first.p, c->v_rd_len.p, c->v_order.p);
@@ -856,7 +853,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 	uint32_t n_fb = 0;
 	if (S.n_items > 0) {
 		uint32_t *cnts = (uint32_t *)(c->counters.p + 16);                          // (counters[16..17]) [0] handed back, [1] deferred segments, [2] fragments to compact
-		static const int force_fb = getenv("AL_TEST_TILE_FB") ? 1 : 0;
+		const int force_fb = al_env().test_tile_fb ? 1 : 0;
 		const size_t cap = (size_t)(c->n_anchor_total / 9) + 64;                    // a deferred segment has at least 9 anchors
 		if (cap >= (1ULL << 31)) { fprintf(stderr, "[airlift] too many anchors in one batch for the deferred-segment list: upload fewer fragments\n"); al_nomem_flag() = true; return -1; }
 		if (c->vs_off.ensure(cap) || c->d_uslot.ensure(cap) || c->vs_na.ensure(cap) || c->vs_meta.ensure(cap) || c->d_rel.ensure(cap) || c->d_fragid.ensure(cap) || c->vs_cls.ensure(cap) ||
@@ -869,7 +866,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 		                   c->chained.p, c->u.p, c->uo.p, c->frag_nu.p, c->fb_list.p, cnts, c->P, lmin, c->counters.p, force_fb, D);
 		if (ev(ST_SEG_FIND)) return -1;
 		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }   // the lane kernels of the small fragments (ovl1): done before their scratch is used again
-		{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: tile kernel (%u items, first pass %d) -> %s\n", S.n_items, (int)first, hipGetErrorName(e)); } }
+		if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: tile kernel (%u items, first pass %d) -> %s\n", S.n_items, (int)first, hipGetErrorName(e)); }
 		uint32_t h[3] = {0, 0, 0};
 		AL_HIP_CHECK(hipMemcpyAsync(h, cnts, 12, hipMemcpyDeviceToHost, s));
 		AL_HIP_CHECK(hipStreamSynchronize(s));
@@ -894,20 +891,18 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 			// segment for 0.1 - 0.5 ms whatever the launch holds, so a THIN class (a small batch, the tie rounds, the long classes) goes to k_chain_coop
 			// instead -- sixteen lanes per segment, over sooner, and neighbouring thin classes share a launch.  (Measured on the full classes of a
 			// 1 M-pair batch the sixteen-lane form is the slower one: 12.7 against 9.8 ms.)  AL_CHAIN_COOP = 0 / 1 (tests): never / always.
-			static const int coop_env = getenv("AL_CHAIN_COOP") ? atoi(getenv("AL_CHAIN_COOP")) : -1;
+			const int coop_env = al_env().chain_coop;
 			bool thin[9]; thin[0] = false;
 			for (int k = 1; k < 9; ++k) thin[k] = coop_env == 1 || (coop_env != 0 && cb[k + 1] - cb[k] < 4096u);
 			uint32_t capl[9]; for (int k = 0; k < 9; ++k) capl[k] = thin[k] ? 0u : capl0[k];
 			size_t wsb[10]; wsb[0] = 0; for (int k = 0; k < 9; ++k) wsb[k + 1] = wsb[k] + (size_t)(cb[k + 1] - cb[k]) * capl[k];   // chain-end scratch: CAPL words per entry, by list position
 			if (c->ws_u64.ensure(wsb[9] + 64, false, s)) return -1;
-			{ static const bool tr = getenv("AL_TRACE") != nullptr;
-			  if (tr && first) fprintf(stderr, "[airlift] trace: tile chaining: %u items, %u deferred segments (<=16:%u <=24:%u <=32:%u <=40:%u <=48:%u <=64:%u <=80:%u <=96:%u <=128:%u), %u fragments to compact\n", S.n_items, n_def,
-			                          cb[1] - cb[0], cb[2] - cb[1], cb[3] - cb[2], cb[4] - cb[3], cb[5] - cb[4], cb[6] - cb[5], cb[7] - cb[6], cb[8] - cb[7], cb[9] - cb[8], n_cmp); }
+			if (al_env().trace && first) fprintf(stderr, "[airlift] trace: tile chaining: %u items, %u deferred segments (<=16:%u <=24:%u <=32:%u <=40:%u <=48:%u <=64:%u <=80:%u <=96:%u <=128:%u), %u fragments to compact\n", S.n_items, n_def,
+			                          cb[1] - cb[0], cb[2] - cb[1], cb[3] - cb[2], cb[4] - cb[3], cb[5] - cb[4], cb[6] - cb[5], cb[7] - cb[6], cb[8] - cb[7], cb[9] - cb[8], n_cmp);
 			ChainSeg sg{c->vs_meta.p, nullptr, nullptr, 0, nullptr, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p};
 #define LDEF(C, L, K) do { if (!thin[K]) LCH(C, L, -1, c->vs_off.p, c->vs_na.p, c->chained.p, c->u.p, (uint32_t *)nullptr, c->seg_ord.p + cb[K], (int)(cb[K + 1] - cb[K]), sg, c->uo.p, c->ws_u64.p + wsb[K], C); } while (0)
 			// (round 5) the classes on two streams in turn, like the lane kernels of the small fragments (ovl2 is idle here: they were joined above); AL_CHAIN_OVL2=0: all on this one
-			static const bool two_env = !(getenv("AL_CHAIN_OVL2") && atoi(getenv("AL_CHAIN_OVL2")) == 0);
-			const bool two = two_env && c->n_frag < 400000;                          // (a 1 M-pair batch's classes fill the chip: no gain there, C5 slightly slower)
+			const bool two = al_env().chain_ovl2 && c->n_frag < 400000;                          // (a 1 M-pair batch's classes fill the chip: no gain there, C5 slightly slower)
 			hipStream_t const s_cls[2] = {s, two ? c->on(AL_ROLE_OVL2) : s};
 			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[4], 0)); }
 			{ int turn = 0;
@@ -928,12 +923,12 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 				}
 				k = k1 + 1;
 			}
-			{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: deferred segments (%u, first pass %d) -> %s\n", n_def, (int)first, hipGetErrorName(e)); } }
+			if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: deferred segments (%u, first pass %d) -> %s\n", n_def, (int)first, hipGetErrorName(e)); }
 #undef LDEF
 		}
 		if (n_cmp > 0) hipLaunchKernelGGL(k_u_compact, dim3(std::min<uint32_t>(n_cmp, 8192u)), dim3(64), 0, s, (const uint32_t *)c->cmp_list.p, (const uint32_t *)(cnts + 2), c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, (const uint32_t *)c->ctie.p, c->fb_list.p, cnts);
 		if (ev(ST_SEG_CHAIN_LDS)) return -1;
-		{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: compact (%u fragments) -> %s\n", n_cmp, hipGetErrorName(e)); } }
+		if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: compact (%u fragments) -> %s\n", n_cmp, hipGetErrorName(e)); }
 		if (n_cmp > 0) { AL_HIP_CHECK(hipMemcpyAsync(&n_fb, cnts, 4, hipMemcpyDeviceToHost, s)); AL_HIP_CHECK(hipStreamSynchronize(s)); } else n_fb = h[0];
 	} else if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
 	if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
@@ -957,11 +952,11 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 	const int nl = n_list;
 	if (nl == 0) return 0;
 	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
-	static const bool spec_on0 = !(getenv("AL_SPEC_MERGE") && atoi(getenv("AL_SPEC_MERGE")) == 0) && !(getenv("AL_HEAP_OLD") && atoi(getenv("AL_HEAP_OLD")) == 1);
+	const bool spec_on0 = al_env().spec_merge && !al_env().heap_old;
 	// (the merges made ahead cost a few milliseconds of the first pass even when the re-chain pass ends up taking none -- a genome whose re-seeded fragments are
 	//  small: after two such batches in a row a context makes them for every eighth batch only, until one is taken again)
 	if (first) ++c->spec_batch;
-	const bool spec_now = first && spec_on0 && c->opt.max_occ > c->opt.mid_occ && (c->spec_idle < 2 || c->spec_batch % 8 == 0 || getenv("AL_SPEC_MIN") != nullptr);
+	const bool spec_now = first && spec_on0 && c->opt.max_occ > c->opt.mid_occ && (c->spec_idle < 2 || c->spec_batch % 8 == 0 || al_env().spec_min.has_value());
 	if (spec_now && c->spec_na2.ensure((size_t)c->n_frag + 1)) return -1;
 	hipLaunchKernelGGL(k_seed, dim3((nl + 255) / 256), dim3(256), 0, s, c->di.tab, c->di.tab_bits, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->mini.p, c->mini_cnt.p,
 	                   c->match.p, c->frag_nm.p, c->frag_na.p, c->frag_rep.p, list, nl, max_occ, c->opt.max_occ, spec_now ? c->spec_na2.p : (uint32_t *)nullptr);
@@ -971,7 +966,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 	// The exact merge of GIANT fragments the re-chain pass may ask for, started now (k_spec_build, al_kernels_seed.hip): AL_SPEC_MERGE=0 turns it off,
 	// AL_SPEC_MIN sets the smallest max_occ anchor count that gets a slot (tests lower it so that ordinary fragments take this path).
 	constexpr uint32_t SPEC_CAP = AL_SPEC_CAP, SPEC_PER = 126;
-	static const uint32_t spec_min = getenv("AL_SPEC_MIN") ? (uint32_t)atoi(getenv("AL_SPEC_MIN")) : 49152u;
+	const uint32_t spec_min = al_env().spec_min ? (uint32_t)*al_env().spec_min : 49152u;
 	uint32_t h_spec[2 + 4 * AL_SPEC_CAP] = {0, 0};
 	if (first) {
 		if (c->spec_busy) { AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SPEC))); AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SPEC2))); c->spec_busy = false; }   // (the previous batch's slots: free again)
@@ -1005,8 +1000,8 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 				LSPEC(2, 63); LSPEC(1, -1);
 #undef LSPEC
 				c->n_spec = ns; c->spec_busy = true;
-				{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { uint32_t mx = 0, mn = 0xffffffffu; for (uint32_t i = 0; i < ns; ++i) { mx = std::max(mx, h_spec[2 + 4 * i + 2]); mn = std::min(mn, h_spec[2 + 4 * i + 2]); }
-				  fprintf(stderr, "[airlift] trace: %u giant fragment(s) of %u candidates (%llu anchors with max_occ, %u ... %u each) merged ahead of the re-chain pass\n", ns, h_spec[1], (unsigned long long)na, mn, mx); } }
+				if (al_env().trace) { uint32_t mx = 0, mn = 0xffffffffu; for (uint32_t i = 0; i < ns; ++i) { mx = std::max(mx, h_spec[2 + 4 * i + 2]); mn = std::min(mn, h_spec[2 + 4 * i + 2]); }
+				  fprintf(stderr, "[airlift] trace: %u giant fragment(s) of %u candidates (%llu anchors with max_occ, %u ... %u each) merged ahead of the re-chain pass\n", ns, h_spec[1], (unsigned long long)na, mn, mx); }
 			} else al_nomem_flag() = false;                                  // (no room: the re-chain pass merges them itself)
 		}
 		c->n_anchor_pass1 = total; c->n_anchor_total = total;
@@ -1035,7 +1030,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 	// kernels read neighbouring fragments.  One 5-bit radix pass instead of four 8-bit ones.
 	uint32_t lb[15];
 	{   // AL_TEST_SORT_BLK / AL_TEST_SORT_BIG (tests): smallest anchor count that goes to the block / device-wide sort
-		static const char *e1 = getenv("AL_TEST_SORT_BLK"), *e2 = getenv("AL_TEST_SORT_BIG");
+		const char *const e1 = al_env().test_sort_blk, *const e2 = al_env().test_sort_big;
 		uint32_t t_blk = e1 ? (uint32_t)atoi(e1) : 1025u, t_big = e2 ? (uint32_t)atoi(e2) : 8193u;   // above 8192 anchors: device-wide radix sort
 		if (t_blk < 65u) t_blk = 65u; if (t_blk > 1025u) t_blk = 1025u; if (t_big < t_blk) t_big = t_blk; if (t_big > 8193u) t_big = 8193u;
 		{ int rb = 1; while ((1ULL << rb) < c->mi->seq.size()) ++rb; if (33 + rb + 16 > 64) t_big = t_blk; }   // compact keys of the block sort: strand | contig | position | list in 64 bits
@@ -1065,7 +1060,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 	// other option values: the segment-wise kernels (chain_legacy).  AL_TEST_TILE_ALL (tests): every fragment through the tile kernel.
 	int lmin = c->opt.min_cnt > 1 ? c->opt.min_cnt : 1;
 	{ const int per = c->mi->k + 1, need = (c->opt.min_chain_score + per - 1) / per; if (need > lmin) lmin = need; }
-	static const bool tile_all = getenv("AL_TEST_TILE_ALL") != nullptr;
+	const bool tile_all = al_env().test_tile_all;
 	const bool tiles_ok = lds_ok && lmin >= 2 && c->opt.max_chain_skip >= 7 && !((c->P.dbg >> 28) & 1);   // (at most 7 predecessors in the segments the tile kernel chains itself: no skip rule)
 	const uint32_t tile_from = !tiles_ok ? (uint32_t)nl : tile_all ? lb1 : lb129;
 	if (c->fb_list.ensure((size_t)nl + 2)) return -1;
@@ -1078,9 +1073,9 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		// The lane-per-fragment kernels (fragments of up to 128 anchors, memory latency) run on a stream of their own: beside the tile sorts
 		// of the large fragments and beside the tile kernel, which takes the rest of the list.
 		hipStream_t const s_main = s;
-		static const bool use_ovl = !(getenv("AL_CHAIN_OVL") && atoi(getenv("AL_CHAIN_OVL")) == 0);   // (AL_CHAIN_OVL=0: on the main stream, after the sorts)
+		const bool use_ovl = al_env().chain_ovl;   // (AL_CHAIN_OVL=0: on the main stream, after the sorts)
 		// (round 5) ... on TWO streams, the classes in turn (AL_CHAIN_OVL2=0: one): a class ends in the tail of its slowest wavefronts, and the next one's start fills it
-		static const bool two = !(getenv("AL_CHAIN_OVL2") && atoi(getenv("AL_CHAIN_OVL2")) == 0);
+		const bool two = al_env().chain_ovl2;
 		if (use_ovl) { AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[2], 0)); if (two) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[2], 0)); }
 		{ hipStream_t s = use_ovl ? c->on(AL_ROLE_OVL1) : s_main; int turn = 0;
 #define NEXT_S() do { if (use_ovl && two) s = c->on(AL_ROLE_OVL1 + (++turn & 1)); } while (0)
@@ -1092,7 +1087,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		if (lds_ok && n_mid_end > lb65) {   // exact ranges of the size-ordered list (lane counts differ between these classes)
 			// 64-lane wavefronts hold more fragments per CU but need enough of them to cover the chip; a thin class runs on half waves
 			const uint32_t fill = 64u * 3u * 256u * 2u;
-			static const uint32_t wave_max = getenv("AL_CHAIN_WAVE_MAX") ? (uint32_t)atoi(getenv("AL_CHAIN_WAVE_MAX")) : 8192u;
+			const uint32_t wave_max = al_env().chain_wave_max;
 			uint32_t from = lb65;
 			if (lb129 - lb65 < wave_max) {   // few fragments of 65 ... 128 anchors (a small batch): a wavefront each is over sooner than a lane each
 				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(lb129 - lb65), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
@@ -1122,7 +1117,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		AL_HIP_CHECK(hipEventRecord(c->ev_ovl[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(sb, c->ev_ovl[0], 0));
 		int pos_bits = 1; { uint32_t mx = 1; for (const AlSeq &sq : c->mi->seq) mx = std::max(mx, sq.len); while (pos_bits < 31 && (1ULL << pos_bits) < mx) ++pos_bits; }
 		const int rank_bits = 64 - 16 - 1 - rid_bits - pos_bits;
-		static const char *e3 = getenv("AL_TEST_BIG_CHUNK");                // tests: fragments per device-wide sort
+		const char *const e3 = al_env().test_big_chunk;                // tests: fragments per device-wide sort
 		uint32_t chunk_max = rank_bits >= 31 ? 0x7fffffffu : rank_bits >= 1 ? (1u << rank_bits) : 1u;
 		if (e3 && atoi(e3) > 0) chunk_max = std::min<uint32_t>(chunk_max, (uint32_t)atoi(e3));
 		if (rank_bits < 0 && lb_big < (uint32_t)nl) {                       // (no such index in practice: > 2^46 contig-id x position range) exact merge for all of them
@@ -1130,11 +1125,11 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		}
 		// (round 5) runs of 8192 anchors sorted by the register network, then merged pairwise (k_anchor_run_sort / k_anchor_run_merge): one to six passes of 8 bytes
 		// per anchor by the fragment's size instead of expansion + seven radix passes + scatter.  AL_BIG_MERGE=0: the device-wide sort (tests run both).
-		static const int big_merge = getenv("AL_BIG_MERGE") ? atoi(getenv("AL_BIG_MERGE")) : 1;        // 0: radix everywhere, 1: run merge everywhere, 2: run merge in the re-chain pass only
+		const int big_merge = al_env().big_merge;        // 0: radix everywhere, 1: run merge everywhere, 2: run merge in the re-chain pass only
 		const bool use_merge = (big_merge == 1 || (big_merge == 2 && !first)) && 33 + rid_bits + 16 <= 64 && lb_big < (uint32_t)nl;
 		// AL_TEST_RUN=<run>,<tile> (tests): shorter runs and merge tiles (powers of two, tile <= run <= 8192, tile <= 2048) so that the golden sets' fragments take several passes
 		static uint32_t run_len = 8192, tile = 2048;
-		{ static bool once = false; if (!once) { once = true; const char *e = getenv("AL_TEST_RUN"); unsigned a = 0, b = 0;
+		{ static bool once = false; if (!once) { once = true; const char *e = al_env().test_run; unsigned a = 0, b = 0;
 		  if (e && sscanf(e, "%u,%u", &a, &b) == 2 && a && b && !(a & (a - 1)) && !(b & (b - 1)) && b <= a && a <= 8192 && b <= 2048) { run_len = a; tile = b; } } }
 		if (use_merge) {
 			const uint32_t nb = (uint32_t)nl - lb_big;
@@ -1231,15 +1226,15 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 			hipLaunchKernelGGL(k_spec_apply, dim3(64, c->n_spec), dim3(256), 0, c->on(AL_ROLE_SPEC), (const uint32_t *)c->spec_meta.p, (const uint32_t *)c->spec_use.p, (const uint64_t *)(c->spec_v64.p + st), (const AlAnchor *)c->spec_anchors.p, (const uint64_t *)c->a_off.p, c->anchors.p);
 			AL_HIP_CHECK(hipEventRecord(c->ev_spec[1], c->on(AL_ROLE_SPEC)));
 			c->spec_pending = true;
-			{ static const bool tr = getenv("AL_TRACE") != nullptr; if (tr) { std::vector<uint32_t> u(c->n_spec); AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SIDE))); AL_HIP_CHECK(hipMemcpy(u.data(), c->spec_use.p, (size_t)c->n_spec * 4, hipMemcpyDeviceToHost));
-			  uint32_t k = 0; for (uint32_t x : u) k += x; fprintf(stderr, "[airlift] trace: re-chain pass takes %u of the %u merges made ahead\n", k, c->n_spec); } }
+			if (al_env().trace) { std::vector<uint32_t> u(c->n_spec); AL_HIP_CHECK(hipStreamSynchronize(c->on(AL_ROLE_SIDE))); AL_HIP_CHECK(hipMemcpy(u.data(), c->spec_use.p, (size_t)c->n_spec * 4, hipMemcpyDeviceToHost));
+			  uint32_t k = 0; for (uint32_t x : u) k += x; fprintf(stderr, "[airlift] trace: re-chain pass takes %u of the %u merges made ahead\n", k, c->n_spec); }
 		}
 		hipLaunchKernelGGL(k_collect_flagged_blk, dim3((nl + 255) / 256), dim3(256), 0, c->on(AL_ROLE_SIDE), order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, n_heap_d);
 		// the four merge kernels take disjoint fragments and each waits for its slowest one: side by side, on a stream each
 		AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], c->on(AL_ROLE_SIDE)));
 		// (only the streams that get a kernel below: aux1 has none unless AL_HEAP_OLD=1, and where it shares a stream with the merges made ahead its
 		//  join would make the main stream wait for those)
-		static const bool heap_old = getenv("AL_HEAP_OLD") && atoi(getenv("AL_HEAP_OLD")) == 1;
+		const bool heap_old = al_env().heap_old;
 		const bool aux_used[3] = {true, heap_old, true};
 		for (int i = 0; i < 3; ++i) if (aux_used[i]) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
 #define LHEAP(H, LN, LO, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap<H, LN>), dim3((nl + LN - 1) / LN), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
@@ -1247,7 +1242,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		// A lane of the lane kernels pops ~1 us per anchor with its 63 neighbours busy, the wavefront kernel 0.8 us with a wavefront to itself: in a
 		// small batch the lane kernels' longest fragment is what the main stream ends up waiting for (131 k pairs of C4: 18 -> 11 ms with the bound
 		// at 8192 anchors), in a large one the wavefront kernel's share is (C5, 500 k pairs: 652 vs 672 ms): the bound follows the batch.
-		static const int wave_env = getenv("AL_TEST_HEAP_WAVE") ? atoi(getenv("AL_TEST_HEAP_WAVE")) : -1;                           // (tests lower it so that small fragments take the wavefront form)
+		const int wave_env = al_env().test_heap_wave;                           // (tests lower it so that small fragments take the wavefront form)
 		const uint32_t wave_na_min = wave_env >= 0 ? (uint32_t)wave_env : c->n_frag >= 400000 ? 16384u : 8192u;
 		// Round 5: the heap in the lanes of a wavefront (k_anchor_heap_lanes: a fixed number of wave-wide instructions per pop instead of an LDS round trip
 		// per sift level) for every flagged fragment of up to 126 lists; the serial forms remain for more lists and behind AL_HEAP_OLD=1 (tests, A/B).
@@ -1370,7 +1365,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 	// again, smaller) and report it as such
 	auto failed = [&]() -> int { if (!al_nomem_flag()) return -1; ctx_release_buffers(c); c->n_frag = c->n_reads = 0; c->ran = false; return AL_ERR_NOMEM; };
 	{   // test hook: behave as if batches above a size did not fit (tests/test_gpu_sam.py drives the halving of the file driver with it)
-		static const char *lim = getenv("AL_TEST_NOMEM_ABOVE");
+		const char *const lim = al_env().test_nomem_above;
 		if (lim && c->n_frag > atoi(lim)) { fprintf(stderr, "[airlift] AL_TEST_NOMEM_ABOVE: pretending %d fragments do not fit\n", c->n_frag); al_nomem_flag() = true; return failed(); }
 	}
 	if (al_run_seed_stages(c)) return failed();
@@ -1384,7 +1379,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 		if (ovf == 0 || attempt >= 8) break;
 		// long CIGARs (repeat-rich or indel-rich batches) did not fit the arena: the alignment stage only reads the chaining
 		// results, so it is simply run again with twice the arena
-		if (getenv("AL_TRACE")) fprintf(stderr, "[airlift] trace: CIGAR arena overflow (%llu), re-running the alignment stage with twice the arena\n", ovf);
+		if (al_env().trace) fprintf(stderr, "[airlift] trace: CIGAR arena overflow (%llu), re-running the alignment stage with twice the arena\n", ovf);
 		al_align_grow_arena(c);
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 4, 0, 8 * sizeof(unsigned long long), c->stream));     // [4..11]: stage statistics, error words, arena cursor
 		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 14, 0, sizeof(unsigned long long), c->stream));
@@ -1394,7 +1389,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 	float tot = 0; (void)hipEventElapsedTime(&tot, c->ev[0], c->ev[ST_N]); c->ms_total = tot;
 	{ float a = 0, b = 0; if (hipEventElapsedTime(&a, c->ev_side[0], c->ev_side[1]) != hipSuccess) a = 0; if (c->n_rechain == 0 || hipEventElapsedTime(&b, c->ev_side[2], c->ev_side[3]) != hipSuccess) b = 0; c->ms_side = a + b; (void)hipGetLastError(); }
 	c->ran = true;
-	{ static const bool guard = getenv("AL_TEST_GUARD") != nullptr; if (guard && al_dev_guard_check()) fprintf(stderr, "[airlift] GUARD: violations after al_batch_run\n"); }
+	if (al_env().test_guard && al_dev_guard_check()) fprintf(stderr, "[airlift] GUARD: violations after al_batch_run\n");
 	// counters + algorithmic bytes
 	unsigned long long h[16]; AL_HIP_CHECK(hipMemcpy(h, c->counters.p, sizeof(h), hipMemcpyDeviceToHost));
 	if ((c->P.dbg >> 24) & 1) { unsigned long long t[8]; AL_HIP_CHECK(hipMemcpy(t, c->counters.p + 24, sizeof(t), hipMemcpyDeviceToHost));
@@ -1406,7 +1401,7 @@ extern "C" int al_batch_run(al_ctx_t *c)
 	if ((c->P.dbg2 >> 5) & 1) { unsigned long long t[8]; AL_HIP_CHECK(hipMemcpy(t, c->counters.p + 24, sizeof(t), hipMemcpyDeviceToHost));
 		fprintf(stderr, "[airlift] DP exit shadow (two-cells-per-lane jobs): jobs %llu, differing %llu; rows needed %llu of %llu (%.1f %%); per wavefront %llu of %llu (%.1f %%); jobs saving < 10 %% %llu, 10-25 %% %llu, 25-40 %% %llu, >= 40 %% %llu\n",
 		        t[0], t[1], t[3], t[2], t[2] ? 100.0 * (double)t[3] / (double)t[2] : 0.0, t[5], t[4], t[4] ? 100.0 * (double)t[5] / (double)t[4] : 0.0, t[6] & 0xffffffffull, t[6] >> 32, t[7] & 0xffffffffull, t[7] >> 32); }
-	if (getenv("AL_TRACE")) { fprintf(stderr, "[airlift] trace: counters"); for (int i = 0; i < 16; ++i) fprintf(stderr, " [%d]=%llu", i, h[i]); fprintf(stderr, " rechain=%u\n", c->n_rechain); }
+	if (al_env().trace) { fprintf(stderr, "[airlift] trace: counters"); for (int i = 0; i < 16; ++i) fprintf(stderr, " [%d]=%llu", i, h[i]); fprintf(stderr, " rechain=%u\n", c->n_rechain); }
 	al_batch_stat_t &st = c->stat; memset(&st, 0, sizeof(st));
 	st.n_frag = c->n_frag; st.n_reads = c->n_reads; st.n_bases = c->n_bases;
 	st.n_mini = ~0ULL; st.n_chain = ~0ULL;   // filled lazily by al_batch_stat()

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 #include "al_bam.h"
+#include "al_env.h"
 
 struct SortedStore {            // --sorted-bam: mapped records are kept until the end of the input, in bounded runs
 	std::vector<std::vector<char>> bufs;                  // record bytes, one buffer per (batch, worker)
@@ -34,7 +35,7 @@ struct SortedStore {            // --sorted-bam: mapped records are kept until t
 	}
 	int spill()
 	{   // one sorted run to a temp file (like samtools sort's -m chunks); merged at the end
-		const char *td = getenv("TMPDIR"); std::string path = std::string(td && *td ? td : "/tmp") + "/airlift_sort_XXXXXX";
+		std::string path = std::string(al_env_tmpdir()) + "/airlift_sort_XXXXXX";
 		const int fd = mkstemp(&path[0]);
 		if (fd < 0) { perror("[airlift] --sorted-bam: cannot create a temporary run file"); return -3; }
 		unlink(path.c_str());

@@ -164,11 +164,12 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 {
 	static const AlStreamRange whole;
 	if (!range) range = &whole;
-	if (getenv("AL_HOST_IO") || n_fn < 1 || n_fn > 2 || n_dev < 1) return AL_STREAM_NA;
+	if (al_env().host_io || n_fn < 1 || n_fn > 2 || n_dev < 1) return AL_STREAM_NA;
 	const int bam = rs->bam_mode;                          // 0 text, 1 BAM, 2 coordinate-sorted BAM
 	if (bam && (n_dev != 1 || range != &whole || !rs->bgzf || (bam == 2 && !rs->store) || (opt->flag & AL_F_OUT_PAF))) return AL_STREAM_NA;
 	for (int i = 0; i < n_fn; ++i) if (!eligible_file(fn[i])) return AL_STREAM_NA;
-	const bool timing = getenv("AL_TIMING") != nullptr, trace = getenv("AL_TRACE") != nullptr;
+	const AlEnv &env = al_env();
+	const bool timing = env.timing, trace = env.trace;
 	const double T0 = now_s();
 	// A long input (by its file sizes, ~360 bytes per read) is mapped in batches of up to 2^20 reads on TWO contexts per GPU: since the chaining
 	// scratch went (44 instead of 96 workspace bytes per seed hit: ~70 KB per read on a repeat-rich genome) two such contexts fit next to the
@@ -180,10 +181,10 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	if (ranged) { for (int i = 0; i < n_fn; ++i) for (int j = 0; j < range->n_ranges; ++j) est_reads0 += (double)(range->rend[i][j] - range->rstart[i][j]) / 360.0; est_reads0 /= (double)n_dev; }
 	else { struct stat sb; for (int i = 0; i < n_fn; ++i) if (stat(fn[i], &sb) == 0) { const double hi = range->end[i] >= 0 ? (double)range->end[i] : (double)sb.st_size; est_reads0 += std::max(0.0, hi - (double)range->start[i]) / 360.0; } est_reads0 /= (double)n_dev; }
 	const bool long_input = est_reads0 >= 3.0e6;
-	const int n_slots_lane = std::max(2, std::min(8, getenv("AL_SLOTS") ? atoi(getenv("AL_SLOTS")) : long_input ? 4 : 5));      // text / SAM buffer sets per GPU
-	const int n_ctx_lane = std::max(1, std::min(n_slots_lane, getenv("AL_CTXS") ? atoi(getenv("AL_CTXS")) : long_input ? 2 : 3));  // mapping contexts per GPU
+	const int n_slots_lane = env.slots.value_or(long_input ? 4 : 5);      // text / SAM buffer sets per GPU
+	const int n_ctx_lane = std::max(1, std::min(n_slots_lane, env.ctxs.value_or(long_input ? 2 : 3)));  // mapping contexts per GPU
 	const int NL = n_dev, NS = NL * n_slots_lane, NM = NL * n_ctx_lane;
-	const size_t PIECE = (size_t)(getenv("AL_PIECE_MB") ? std::max(1, atoi(getenv("AL_PIECE_MB"))) : 8) << 20;
+	const size_t PIECE = (size_t)env.piece_mb << 20;
 
 	std::mutex m; std::condition_variable cv; int rc = 0;
 	auto fail = [&](int code) { { std::lock_guard<std::mutex> l(m); if (rc == 0) rc = code ? code : -1; } cv.notify_all(); };
@@ -228,20 +229,20 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	// small probes; what a probe held per read and how fast it ran decide the size: device memory costs per byte a process touches
 	// for the first time, so the workspaces of a batch are sized to cost a fraction of the job's estimated mapping time, inside the
 	// free memory.
-	const int64_t k_bases = getenv("AL_AUTO_BATCH") ? (int64_t)1 << 40 : opt->mini_batch_size > 0 ? (int64_t)opt->mini_batch_size : 50000000;
+	const int64_t k_bases = al_env_auto_batch() ? (int64_t)1 << 40 : opt->mini_batch_size > 0 ? (int64_t)opt->mini_batch_size : 50000000;
 	std::atomic<int> max_reads{0}; std::atomic<bool> sized{false};
-	const int probe_reads = getenv("AL_PROBE_READS") ? std::max(2, atoi(getenv("AL_PROBE_READS"))) : 32768;
+	const int probe_reads = env.probe_reads.value_or(32768);
 	std::atomic<int> reads_cap_k{1 << 30};                 // mini_batch_size in reads, once a read length is known
 	std::atomic<long long> est_total_reads{0};             // from the file sizes and the bytes per read of the first batch
 	max_reads = (int)std::max<int64_t>(2, std::min<int64_t>(probe_reads, k_bases / 64));   // batch 0 (-K is an upper bound: reads of >= 64 bases assumed until a batch has been seen); the following ones 4 x the probe until the size is decided
 	double probe_held0 = 0, probe_n0 = 0; int probe_mult = 0;
 	std::atomic<bool> single_probe{false};               // a long input (by its file sizes): no small first batch, the first batch already has the size the run keeps
-	if (getenv("AL_BATCH_READS")) { max_reads = std::max(2, atoi(getenv("AL_BATCH_READS"))); sized = true; }    // tests / tuning: fixed batches
+	if (env.batch_reads) { max_reads = *env.batch_reads; sized = true; }    // tests / tuning: fixed batches
 	if (ranged) { max_reads = 1 << 30; sized = true; }     // a range is a batch, whatever it holds (one that does not fit the device is halved by its mapper like any other)
 
 	// SAM text leaves the device through a small ring of page-locked buffers (page-locking memory costs ~0.2 s per GB: no buffer of a
 	// batch's size): the copy of piece n + 1 runs while piece n is written
-	const size_t CH = (size_t)(getenv("AL_OUT_PIECE_MB") ? std::max(1, atoi(getenv("AL_OUT_PIECE_MB"))) : 32) << 20;
+	const size_t CH = (size_t)env.out_piece_mb << 20;
 	// (page-locked buffers only: the 'piece copied' events belong to the slot that is drained -- AlStreamSlot::ev_out, created on the slot's device;
 	//  an event of another device cannot be recorded on the slot's stream, which is what a ring-owned pair amounted to with lanes on several GPUs)
 	struct OutRing { char *buf[2] = {nullptr, nullptr}; };
@@ -346,7 +347,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 							// With a reserve (al_device_reserve: the run's memory was obtained in the background during start-up) allocation costs nothing any more
 							// and the bound is what the reserve still has room for; without one, the fitted model of the driver's pace stays.
 							const long long room = al_dev_reserve_room();
-							static const double A = (getenv("AL_ALLOC_GBS") ? atof(getenv("AL_ALLOC_GBS")) : 30.0) * 1e9, t0b = (getenv("AL_BATCH_MS") ? atof(getenv("AL_BATCH_MS")) : 25.0) * 1e-3;
+							const double A = env.alloc_gbs * 1e9, t0b = env.batch_ms * 1e-3;
 							const double b_opt = sqrt(total_reads * t0b * A / (1.30 * v * (double)n_ctx_lane * (double)n_ctx_lane));
 							if (room >= 0) mr = std::min(mr, (((double)room + (double)held_ctx) * 0.95 / (double)n_ctx_lane - F) / (v * 1.30 + (double)n_slots_lane * 2048.0 / (double)n_ctx_lane));
 							else if (A > 0) mr = std::min(mr, b_opt);
@@ -372,7 +373,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	// a regular output file is written by a few threads at once (pwrite of the parts of a piece: one thread copies ~3 GB/s into the page cache)
 	long long woff = -1; int n_wr = 1;
 	{ struct stat sb; const int fl = fcntl(ofd, F_GETFL); const off_t at = lseek(ofd, 0, SEEK_CUR);
-	  if (fstat(ofd, &sb) == 0 && S_ISREG(sb.st_mode) && at >= 0 && fl >= 0 && !(fl & O_APPEND) && !getenv("AL_NO_PWRITE")) { woff = (long long)at; n_wr = std::max(1, std::min(16, n_threads / 2)); } }
+	  if (fstat(ofd, &sb) == 0 && S_ISREG(sb.st_mode) && at >= 0 && fl >= 0 && !(fl & O_APPEND) && !al_env_no_pwrite()) { woff = (long long)at; n_wr = std::max(1, std::min(16, n_threads / 2)); } }
 	if (bam) woff = -1;                                   // (BAM leaves through the BGZF stream's FILE)
 	uint64_t sink_rounds = 0;                             // rounds of the caller's sink this process has taken part in
 	const uint64_t pre_bytes = ranged && range->header && woff > 0 ? (uint64_t)woff : 0;   // (the header, already in the file)
@@ -520,15 +521,15 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			AlStreamSlot &S = sl->S;
 			// The second batch is the size the run keeps unless the input is long (growing later re-obtains every workspace): 4 x the first
 			// probe, 8 x when the input has at least 6 M reads and this process has been getting device memory fast so far (index, slots).
-			if (k == 0 && !sized.load() && !getenv("AL_PROBE_READS") && !getenv("AL_TWO_PROBES")) {
+			if (k == 0 && !sized.load() && !env.probe_reads && !env.two_probes) {
 				double fs = 0; for (int i = 0; i < n_fn; ++i) fs += (double)rd[i]->file_size();
 				const double est0 = fs / bytes_per_read / (double)NL;                 // (360 bytes per read until a batch has been seen)
 				if (est0 >= 1.0e6) {
 					const AlAllocStat &as = al_alloc_stat(); const double ns = (double)as.dev_ns.load(), by = (double)as.dev_bytes.load();
-					probe_mult = getenv("AL_PROBE_MULT") ? std::max(1, atoi(getenv("AL_PROBE_MULT"))) : est0 >= 6.0e6 && ns > 0 && by / (ns * 1e-9) >= 100e9 ? 8 : 4;
+					probe_mult = env.probe_mult.value_or(est0 >= 6.0e6 && ns > 0 && by / (ns * 1e-9) >= 100e9 ? 8 : 4);
 					single_probe = true;
 					int64_t first = (int64_t)probe_mult * probe_reads;
-					if (long_input && !getenv("AL_PROBE_MULT")) {   // at least three batches per context, at most 2^20 reads, within 60 % of the free memory at ~80 KB per read
+					if (long_input && !env.probe_mult) {   // at least three batches per context, at most 2^20 reads, within 60 % of the free memory at ~80 KB per read
 						size_t free_b = 0, total_b = 0;
 						double b = std::min(al_long_batch_cap(est0 * (double)NL), std::max(262144.0, est0 / (3.0 * n_ctx_lane)));   // (524 288 reads; 2^20 for very long inputs: al_runtime.hip)
 						if (hipSetDevice(mappers[0]->device) == hipSuccess && al_dev_mem_info(&free_b, &total_b) == hipSuccess) b = std::min(b, 0.6 * (double)free_b / ((double)n_ctx_lane * (al_map_only(opt->flag) ? 65536.0 : 81920.0)));   // (a map-only run has no extension stage: ~17 KB per read less, measured 13.2 against 30.9 KB on a small reference)
@@ -539,7 +540,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			}
 			if (k == 1 && probe_mult == 0) {
 				probe_mult = 4;
-				if (getenv("AL_PROBE_MULT")) probe_mult = std::max(1, atoi(getenv("AL_PROBE_MULT")));
+				if (env.probe_mult) probe_mult = *env.probe_mult;
 				else { const AlAllocStat &as = al_alloc_stat(); const double ns = (double)as.dev_ns.load(), by = (double)as.dev_bytes.load();
 				       if (est_total_reads.load() / NL >= 6000000 && ns > 0 && by / (ns * 1e-9) >= 100e9) probe_mult = 8; }
 			}

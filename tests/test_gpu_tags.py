@@ -46,7 +46,7 @@ HOST_CASES = [("g8_chimeric", "MD"), ("g8_chimeric", "Y_cs_long"), ("g8_chimeric
 
 @pytest.mark.parametrize("name,key", HOST_CASES, ids=["%s-%s" % c for c in HOST_CASES])
 def test_host_driver_matches_fork(golden_unpacked, name, key):
-    """AL_HIP_IO=1: reads parsed and SAM formatted on the host (the FASTA / gzip / token path); the tags come from the device all the same."""
+    """AL_HOST_IO=1: reads parsed and SAM formatted on the host (the FASTA / gzip / token path); the tags come from the device all the same."""
     d, e, args, exp = _case(golden_unpacked, name, key)
     r = subprocess.run([CLI, "-ax", "sr", "-K", "20000"] + args + [e["ref"]] + e["reads"], cwd=d, capture_output=True, timeout=300, env=dict(os.environ, AL_HOST_IO="1"))
     assert r.returncode == 0, r.stderr.decode()[-2000:]
