@@ -31,6 +31,7 @@ AL_F_EQX = 0x4000000
 AL_F_PAF_NO_HIT = 0x8000000
 AL_F_SAM_HIT_ONLY = 0x40000000
 AL_F_OUT_PAF = 0x100000000   # ours (above the fork's 32 bits): PAF output; only with it is AL_F_CIGAR looked at (clear = map-only)
+AL_F_IN_GPU_INFLATE = 0x200000000   # ours: BGZF FASTQ input of the file-mapping calls inflated on the GPU by the stream driver (--gpu-inflate)
 
 
 def lib_path():

@@ -117,6 +117,17 @@ __global__ __launch_bounds__(256) void k_inflate(const uint8_t *in, const AlInfM
 	}
 }
 
+} // namespace
+// the launch alone, for a caller with buffers of its own (the stream driver's slots, al_stream.hip): n_mem > 0 members of d_in to d_out, *d_next zero;
+// cu4 = 4 x the device's compute units.  0, or -1 when the launch failed
+int al_inflate_launch(hipStream_t st, int cu4, const uint8_t *d_in, const AlInfMember *d_mem, uint32_t n_mem, uint8_t *d_out, uint32_t *d_status, uint32_t *d_next)
+{
+	const uint32_t grid = (uint32_t)std::min<size_t>(((size_t)n_mem + INF_WAVES - 1) / INF_WAVES, (size_t)cu4);
+	hipLaunchKernelGGL(k_inflate, dim3(grid), dim3(INF_T), 0, st, d_in, d_mem, n_mem, d_out, d_status, d_next);
+	return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+namespace {
+
 inline double inf_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // one queue of the device backend: a stream, its device buffers and the events around its three steps
@@ -170,13 +181,12 @@ bool inf_dev_enqueue(InfDev &d, int qi, const uint8_t *h_in, size_t n_in, const 
 {
 	InfQueue &q = d.q[qi];
 	uint8_t *d_out = d_out_at ? d_out_at : q.d_out;
-	const uint32_t grid = (uint32_t)std::min<size_t>((n_mem + INF_WAVES - 1) / INF_WAVES, (size_t)d.grid);
 	bool ok = hipEventRecord(q.ev[0], q.st) == hipSuccess;
 	ok = ok && hipMemcpyAsync(q.d_in, h_in, n_in, hipMemcpyHostToDevice, q.st) == hipSuccess;
 	ok = ok && hipMemcpyAsync(q.d_mem, h_mem, n_mem * sizeof(AlInfMember), hipMemcpyHostToDevice, q.st) == hipSuccess;
 	ok = ok && hipMemsetAsync(q.d_next, 0, 4, q.st) == hipSuccess;
 	ok = ok && hipEventRecord(q.ev[1], q.st) == hipSuccess;
-	if (ok) { hipLaunchKernelGGL(k_inflate, dim3(grid), dim3(INF_T), 0, q.st, q.d_in, q.d_mem, (uint32_t)n_mem, d_out, q.d_status, q.d_next); ok = hipGetLastError() == hipSuccess; }
+	if (ok) { ok = al_inflate_launch(q.st, d.grid, q.d_in, q.d_mem, (uint32_t)n_mem, d_out, q.d_status, q.d_next) == 0; }
 	ok = ok && hipEventRecord(q.ev[2], q.st) == hipSuccess;
 	ok = ok && (n_out == 0 || hipMemcpyAsync(h_out, d_out, n_out, hipMemcpyDeviceToHost, q.st) == hipSuccess);
 	ok = ok && hipMemcpyAsync(h_status, q.d_status, n_mem * 4, hipMemcpyDeviceToHost, q.st) == hipSuccess;

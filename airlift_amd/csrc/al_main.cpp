@@ -81,7 +81,9 @@ static int usage()
 	                "PAF:   --paf (PAF instead of SAM: chaining and MAPQ only, no base-level alignment, unless -c or --cs is given), -c (cg:Z CIGAR),\n"
 	                "       --paf-no-hit (a line for reads without hits); not with mem / samse / aln / tokens, --bam, --sorted-bam, --count-candidates\n"
 	                "BAM:   --bam | --sorted-bam [-l LEVEL] [--sort-mem BYTES]; --gpu-deflate (BGZF blocks deflated on the GPU: one compressor for every -l above 0,\n"
-	                "       -l 0 stores; one device, one process: not with --devices of several lanes, --world, --rank, --ranked)\n");
+	                "       -l 0 stores; one device, one process: not with --devices of several lanes, --world, --rank, --ranked)\n"
+	                "input: --gpu-inflate (BGZF-compressed FASTQ files -- bgzip, bcl-convert, DRAGEN -- stay with the GPU's input parser: their members are\n"
+	                "       inflated on the GPU; decided per file; another gzip file, '-', or --world / --rank take the host reader as without the option)\n");
 	return 1;
 }
 
@@ -207,6 +209,7 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--sorted-bam")) bam_mode = 2;
 		else if (!strcmp(a, "-l") && i + 1 < argc) bam_level = atoi(argv[++i]);
 		else if (!strcmp(a, "--gpu-deflate")) gpu_deflate = true;
+		else if (!strcmp(a, "--gpu-inflate")) mo.flag |= AL_F_IN_GPU_INFLATE;              // BGZF-compressed FASTQ input stays with the stream driver, inflated on the GPU
 		else if (!strcmp(a, "--sort-mem") && i + 1 < argc) setenv("AL_SORT_MEM", std::to_string(parse_num(argv[++i], "--sort-mem")).c_str(), 1);   // --sorted-bam: bytes held before a sorted run is spilled (samtools sort -m)
 		else if (!strcmp(a, "--device") && i + 1 < argc) device = atoi(argv[++i]);
 		else if (!strcmp(a, "--rank") && i + 1 < argc) rank = atoi(argv[++i]);             // one process per GPU: --rank r --world R -o OUT (al_map_file_frag_ranked)

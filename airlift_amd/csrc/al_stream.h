@@ -33,6 +33,13 @@ struct AlIngestResult {
 	uint64_t consumed[2];            // bytes of each text the batch consumed (the rest is the next batch's carry)
 };
 
+// BGZF input (--gpu-inflate, al_stream_append_bgzf): a slot's staging of one launch of the inflater -- compressed bytes, member table, status words, counter
+struct AlInfMember;
+struct AlStreamBgzf {
+	uint8_t *d_in = nullptr; AlInfMember *d_mem = nullptr; uint32_t *d_status = nullptr, *d_next = nullptr, *h_status = nullptr;
+	size_t cap_in = 0, cap_mem = 0; hipEvent_t ev[2] = {nullptr, nullptr}; int cu4 = 0;
+	double kernel_s = 0; uint64_t members = 0, bytes_in = 0, bytes_out = 0, launches = 0;      // AL_TIMING: summed over the run by the driver
+};
 struct AlStreamSlot {
 	int device = 0; hipStream_t io = nullptr; hipEvent_t ev = nullptr;
 	hipEvent_t ev_out[2] = {nullptr, nullptr};   // 'piece copied' events of the SAM drain, created on THIS slot's device (an event must be recorded on a stream of its own device: the writer's shared ring must not own them when the lanes sit on different GPUs)
@@ -53,6 +60,7 @@ struct AlStreamSlot {
 	DevBuf<uint64_t> bam_key; DevBuf<uint32_t> bam_roff, bam_rlen;   // --sorted-bam: sort key, offset and length of every record of the batch
 	uint64_t sam_bytes = 0, sam_records = 0;
 	bool cfg_ready = false; int rg_len = 0;
+	AlStreamBgzf bz;
 	void release();
 };
 
@@ -61,6 +69,17 @@ void al_stream_slot_destroy(AlStreamSlot &S);
 // text of file i: begin (room for cap_bytes), then host pieces appended in file order (each call returns when its copy is done)
 int  al_stream_begin_text(AlStreamSlot &S, int i, size_t cap_bytes);
 int  al_stream_append_text(AlStreamSlot &S, int i, const char *p, size_t n);
+// BGZF input.  al_stream_bgzf_init: the slot's staging for launches of up to cap_in compressed bytes and cap_mem members, from al_dev_malloc under the
+// caller's al_acct(); 0, or 1 when the memory is refused (always under AL_TEST_INFLATE_NOMEM) or the device cannot be used: nothing is left allocated.
+// al_stream_append_bgzf: n_mem whole members (bytes[0, n_in); mem as al_bgzf_take lists them, out_off from 0, n_out inflated bytes in all) inflated by k_inflate on the
+// slot's io stream to the end of file i's text; only the status words come back.  0 with txt_n moved on
+// by n_out; 1 when a member's status is not zero (*bad: the first such member, *bad_status: its AL_INF_E_*; txt_n stays); -1 on a device error.
+// al_stream_end_text: file i has ended: a text whose last byte is no newline gets one (an unterminated last line still counts, kseq.h).
+int  al_stream_bgzf_init(AlStreamSlot &S, size_t cap_in, size_t cap_mem);
+int  al_stream_append_bgzf(AlStreamSlot &S, int i, const uint8_t *bytes, size_t n_in, const AlInfMember *mem, size_t n_mem, uint64_t n_out, size_t *bad, uint32_t *bad_status);
+int  al_stream_end_text(AlStreamSlot &S, int i);
+// al_inflate.hip: the launch alone (n_mem > 0 members of d_in to d_out, *d_next zero; cu4 = 4 x the device's compute units); 0, or -1 when it failed
+int  al_inflate_launch(hipStream_t st, int cu4, const uint8_t *d_in, const AlInfMember *d_mem, uint32_t n_mem, uint8_t *d_out, uint32_t *d_status, uint32_t *d_next);
 // line index + record parse of the loaded text; decides what the batch takes (at most max_reads reads).  eof[i]: no more bytes of file i
 // will follow (a trailing unpaired read is taken; an unterminated last line counts).  Blocks until the device has answered.
 int  al_stream_parse(AlStreamSlot &S, const bool *eof, int max_reads, AlIngestResult *res);

@@ -24,6 +24,7 @@
 #include "al_runtime.h"
 #include "al_io.h"
 #include "al_stream.h"
+#include "al_dev_inflate.h"
 #include "al_dev_sam.h"
 #include "al_dev_paf.h"
 #include "al_dev_bam.h"
@@ -506,12 +507,13 @@ int al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_f
 	AL_HIP_CHECK(hipMemcpy(S.name_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
 	return 0;
 }
+static void bgzf_release(AlStreamBgzf &z);
 void al_stream_slot_destroy(AlStreamSlot &S)
 {
 	if (!S.io) return;
 	(void)hipSetDevice(S.device);
 	(void)hipStreamSynchronize(S.io);
-	S.release();
+	S.release(); bgzf_release(S.bz);
 	(void)hipEventDestroy(S.ev); (void)hipStreamDestroy(S.io); S.io = nullptr; S.ev = nullptr;
 	for (int i = 0; i < 2; ++i) if (S.ev_out[i]) { (void)hipEventDestroy(S.ev_out[i]); S.ev_out[i] = nullptr; }
 }
@@ -531,6 +533,67 @@ int al_stream_append_text(AlStreamSlot &S, int i, const char *p, size_t n)
 	AL_HIP_CHECK(hipMemcpyAsync(S.txt[i].p + S.txt_n[i], p, n, hipMemcpyHostToDevice, S.io));
 	AL_HIP_CHECK(hipStreamSynchronize(S.io));
 	S.txt_n[i] += n;
+	return 0;
+}
+
+static void bgzf_release(AlStreamBgzf &z)
+{
+	if (z.d_in) al_dev_free(z.d_in); if (z.d_mem) al_dev_free(z.d_mem); if (z.d_status) al_dev_free(z.d_status); if (z.d_next) al_dev_free(z.d_next);
+	if (z.h_status) (void)hipHostFree(z.h_status);
+	for (hipEvent_t &e : z.ev) if (e) (void)hipEventDestroy(e);
+	z = AlStreamBgzf();
+}
+int al_stream_bgzf_init(AlStreamSlot &S, size_t cap_in, size_t cap_mem)
+{
+	AlStreamBgzf &z = S.bz;
+	hipDeviceProp_t pr;
+	if (hipSetDevice(S.device) != hipSuccess || hipGetDeviceProperties(&pr, S.device) != hipSuccess) { (void)hipGetLastError(); return 1; }
+	z.cu4 = (pr.multiProcessorCount > 0 ? pr.multiProcessorCount : 64) * 4;
+	bool ok = !al_env().test_inflate_nomem;                    // (test switch, DESIGN.md section 8: the request is refused)
+	ok = ok && al_dev_malloc((void **)&z.d_in, cap_in + 16) == hipSuccess;
+	ok = ok && al_dev_malloc((void **)&z.d_mem, cap_mem * sizeof(AlInfMember)) == hipSuccess;
+	ok = ok && al_dev_malloc((void **)&z.d_status, cap_mem * 4) == hipSuccess;
+	ok = ok && al_dev_malloc((void **)&z.d_next, 4) == hipSuccess;
+	ok = ok && hipHostMalloc((void **)&z.h_status, cap_mem * 4, hipHostMallocDefault) == hipSuccess;
+	for (hipEvent_t &e : z.ev) ok = ok && hipEventCreate(&e) == hipSuccess;
+	if (!ok) { (void)hipGetLastError(); bgzf_release(z); return 1; }
+	z.cap_in = cap_in; z.cap_mem = cap_mem;
+	return 0;
+}
+int al_stream_append_bgzf(AlStreamSlot &S, int i, const uint8_t *bytes, size_t n_in, const AlInfMember *mem, size_t n_mem, uint64_t n_out, size_t *bad, uint32_t *bad_status)
+{
+	AlStreamBgzf &z = S.bz;
+	if (n_mem == 0) return 0;
+	if (!z.d_in || n_in > z.cap_in || n_mem > z.cap_mem) { fprintf(stderr, "[airlift] al_stream_append_bgzf: staging too small\n"); return -1; }
+	if (S.txt_n[i] + n_out + NL_TILE + 16 > S.txt[i].cap) { fprintf(stderr, "[airlift] al_stream_append_bgzf: text buffer too small\n"); return -1; }
+	AL_HIP_CHECK(hipSetDevice(S.device));
+	AL_HIP_CHECK(hipMemcpyAsync(z.d_in, bytes, n_in, hipMemcpyHostToDevice, S.io));
+	AL_HIP_CHECK(hipMemcpyAsync(z.d_mem, mem, n_mem * sizeof(AlInfMember), hipMemcpyHostToDevice, S.io));
+	AL_HIP_CHECK(hipMemsetAsync(z.d_next, 0, 4, S.io));
+	AL_HIP_CHECK(hipEventRecord(z.ev[0], S.io));
+	if (al_inflate_launch(S.io, z.cu4, z.d_in, z.d_mem, (uint32_t)n_mem, S.txt[i].p + S.txt_n[i], z.d_status, z.d_next)) { fprintf(stderr, "[airlift] al_stream_append_bgzf: the launch failed\n"); return -1; }
+	AL_HIP_CHECK(hipEventRecord(z.ev[1], S.io));
+	AL_HIP_CHECK(hipMemcpyAsync(z.h_status, z.d_status, n_mem * 4, hipMemcpyDeviceToHost, S.io));
+	AL_HIP_CHECK(hipStreamSynchronize(S.io));
+	float ms = 0;
+	if (hipEventElapsedTime(&ms, z.ev[0], z.ev[1]) == hipSuccess) z.kernel_s += ms * 1e-3;
+	z.members += n_mem; z.bytes_in += n_in; z.bytes_out += n_out; ++z.launches;
+	for (size_t k = 0; k < n_mem; ++k) if (z.h_status[k]) { *bad = k; *bad_status = z.h_status[k]; return 1; }
+	S.txt_n[i] += n_out;
+	return 0;
+}
+int al_stream_end_text(AlStreamSlot &S, int i)
+{
+	if (S.txt_n[i] == 0) return 0;
+	if (S.txt_n[i] + 1 + NL_TILE + 16 > S.txt[i].cap) { fprintf(stderr, "[airlift] al_stream_end_text: text buffer too small\n"); return -1; }
+	AL_HIP_CHECK(hipSetDevice(S.device));
+	char last = 0;
+	AL_HIP_CHECK(hipMemcpyAsync(&last, S.txt[i].p + S.txt_n[i] - 1, 1, hipMemcpyDeviceToHost, S.io));
+	AL_HIP_CHECK(hipStreamSynchronize(S.io));
+	if (last == '\n') return 0;
+	AL_HIP_CHECK(hipMemsetAsync(S.txt[i].p + S.txt_n[i], '\n', 1, S.io));
+	AL_HIP_CHECK(hipStreamSynchronize(S.io));
+	S.txt_n[i] += 1;
 	return 0;
 }
 

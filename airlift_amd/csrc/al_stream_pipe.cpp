@@ -18,6 +18,9 @@
 // (mini_batch_size, -K, stays as the upper bound; results do not depend on the batching: map.c:229-400 is per read).
 // Input that is not plain four-line FASTQ (gzip, FASTA, multi-line records, a pipe) goes to the host driver (al_pipeline.cpp),
 // from the byte where the device parser stops.
+// BGZF files under AL_F_IN_GPU_INFLATE (--gpu-inflate) stay here: the ingest thread reads their compressed pieces itself, takes whole members
+// (al_bgzf_take.h) until the file's share of the batch is covered, and the slot inflates them straight into its text (al_stream_append_bgzf); from
+// there on a batch is what it is for a plain file, and every offset of such a file (carry, hand-over) is an offset in its inflated stream.
 #include <stdio.h>
 #include <stdlib.h>
 #include <math.h>
@@ -43,6 +46,7 @@
 #include "al_stream_pipe.h"
 #include "al_bam.h"
 #include "al_sorted_store.h"
+#include "al_bgzf_take.h"
 
 namespace {
 
@@ -157,6 +161,51 @@ bool eligible_file(const char *fn)
 	return ok;
 }
 
+// BGZF (its first bytes pass al_inf_parse_header): 1; another gzip file, or "-": 2; anything else: 0
+int bgzf_kind(const char *fn)
+{
+	if (!strcmp(fn, "-")) return 2;
+	const int fd = open(fn, O_RDONLY);
+	if (fd < 0) return 0;
+	struct stat sb; uint8_t h[4096]; int k = 0;
+	if (fstat(fd, &sb) == 0 && S_ISREG(sb.st_mode)) {
+		const ssize_t g = pread(fd, h, sizeof(h), 0);
+		uint32_t ms = 0, hd = 0;
+		if (g >= 2 && h[0] == 0x1f && h[1] == 0x8b) k = al_inf_parse_header(h, (uint64_t)g, &ms, &hd) == 0 ? 1 : 2;
+	}
+	close(fd);
+	return k;
+}
+// one BGZF input file of the run: the window over its compressed bytes (page-locked) and where the next piece is read
+struct BgzfFile {
+	int fd = -1; uint64_t fpos = 0; long long size = 0; bool eof_file = false; AlBgzfFeed feed; size_t piece = 0; double ratio = 1.0;
+	bool open(const char *fn, size_t piece_bytes)
+	{
+		struct stat sb;
+		fd = ::open(fn, O_RDONLY);
+		if (fd < 0 || fstat(fd, &sb) != 0) return false;
+		size = (long long)sb.st_size; piece = piece_bytes; feed.cap = 2 * piece + 65536;
+		if (hipHostMalloc((void **)&feed.buf, feed.cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); feed.buf = nullptr; return false; }
+		if (!read_piece()) return false;
+		ratio = al_bgzf_ratio(feed);
+		return true;
+	}
+	// the next piece behind the window; false on a read error
+	bool read_piece()
+	{
+		size_t room = 0; uint8_t *dst = al_bgzf_feed_room(feed, &room);
+		size_t want = std::min(piece, room);
+		while (want) {
+			const ssize_t g = pread(fd, dst, want, (off_t)fpos);
+			if (g < 0) return false;
+			if (g == 0) { eof_file = true; break; }
+			al_bgzf_feed_add(feed, (size_t)g); dst += g; fpos += (uint64_t)g; want -= (size_t)g;
+		}
+		return true;
+	}
+	~BgzfFile() { if (feed.buf) (void)hipHostFree(feed.buf); if (fd >= 0) close(fd); }
+};
+
 } // namespace
 
 int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_mapopt_t *opt, int n_threads, FILE *out, const char *rg,
@@ -167,8 +216,25 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	if (al_env().host_io || n_fn < 1 || n_fn > 2 || n_dev < 1) return AL_STREAM_NA;
 	const int bam = rs->bam_mode;                          // 0 text, 1 BAM, 2 coordinate-sorted BAM
 	if (bam && (n_dev != 1 || range != &whole || !rs->bgzf || (bam == 2 && !rs->store) || (opt->flag & AL_F_OUT_PAF))) return AL_STREAM_NA;
-	for (int i = 0; i < n_fn; ++i) if (!eligible_file(fn[i])) return AL_STREAM_NA;
 	const AlEnv &env = al_env();
+	// --gpu-inflate: a BGZF file is taken as well, decided per file; another gzip file (or "-") sends the whole run to the host driver, with one notice
+	bool is_bgzf[2] = {false, false}, any_bgzf = false;
+	for (int i = 0; i < n_fn; ++i) {
+		if (eligible_file(fn[i])) continue;
+		if (!(opt->flag & AL_F_IN_GPU_INFLATE)) return AL_STREAM_NA;
+		const int kd = bgzf_kind(fn[i]);
+		if (kd == 2) fprintf(stderr, "[airlift] --gpu-inflate: '%s' is not a BGZF file; it is read as one gzip stream on the host\n", fn[i]);
+		if (kd != 1) return AL_STREAM_NA;
+		is_bgzf[i] = any_bgzf = true;
+	}
+	if (any_bgzf && range != &whole) { fprintf(stderr, "[airlift] --gpu-inflate: BGZF input is not split over the processes of a multi-process run (their byte ranges are found in file bytes)\n"); return AL_STREAM_NA; }
+	std::unique_ptr<BgzfFile> bzf[2];
+	for (int i = 0; i < n_fn; ++i) if (is_bgzf[i]) {
+		bzf[i].reset(new BgzfFile());
+		if (!bzf[i]->open(fn[i], (size_t)env.inflate_piece_kb << 10)) { fprintf(stderr, "[airlift] --gpu-inflate: no page-locked buffer for '%s', or it cannot be read; the host driver reads the input\n", fn[i]); return AL_STREAM_NA; }
+	}
+	// the size of file i as text: a BGZF file's bytes scaled by inflated / compressed bytes of its first piece's members
+	auto text_scale = [&](int i) -> double { return bzf[i] ? bzf[i]->ratio : 1.0; };
 	const bool timing = env.timing, trace = env.trace;
 	const double T0 = now_s();
 	// A long input (by its file sizes, ~360 bytes per read) is mapped in batches of up to 2^20 reads on TWO contexts per GPU: since the chaining
@@ -179,7 +245,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 	if (ranged && (!range->sink || !range->sink->offset_of || (range->n_ranges > 0 && (!range->rstart[0] || !range->rend[0] || (n_fn == 2 && (!range->rstart[1] || !range->rend[1])))))) return -1;
 	double est_reads0 = 0;
 	if (ranged) { for (int i = 0; i < n_fn; ++i) for (int j = 0; j < range->n_ranges; ++j) est_reads0 += (double)(range->rend[i][j] - range->rstart[i][j]) / 360.0; est_reads0 /= (double)n_dev; }
-	else { struct stat sb; for (int i = 0; i < n_fn; ++i) if (stat(fn[i], &sb) == 0) { const double hi = range->end[i] >= 0 ? (double)range->end[i] : (double)sb.st_size; est_reads0 += std::max(0.0, hi - (double)range->start[i]) / 360.0; } est_reads0 /= (double)n_dev; }
+	else { struct stat sb; for (int i = 0; i < n_fn; ++i) if (stat(fn[i], &sb) == 0) { const double hi = range->end[i] >= 0 ? (double)range->end[i] : (double)sb.st_size; est_reads0 += std::max(0.0, hi - (double)range->start[i]) * text_scale(i) / 360.0; } est_reads0 /= (double)n_dev; }
 	const bool long_input = est_reads0 >= 3.0e6;
 	const int n_slots_lane = env.slots.value_or(long_input ? 4 : 5);      // text / SAM buffer sets per GPU
 	const int n_ctx_lane = std::max(1, std::min(n_slots_lane, env.ctxs.value_or(long_input ? 2 : 3)));  // mapping contexts per GPU
@@ -211,6 +277,13 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			al_acct() = nullptr;
 			slots.push_back(std::move(sl));
 			if (e) { destroy_all(); return -2; }
+			if (any_bgzf) {   // the slot's staging of the inflater; refused: nothing has been written yet, the host driver takes the run
+				al_acct() = &slots.back()->held;
+				size_t ci = 0; for (int f = 0; f < n_fn; ++f) if (bzf[f]) ci = std::max(ci, bzf[f]->feed.cap);
+				const int be = al_stream_bgzf_init(slots.back()->S, ci, ci / 64 + 1024);
+				al_acct() = nullptr;
+				if (be) { fprintf(stderr, "[airlift] --gpu-inflate: no device memory for the inflater's staging buffers; the input is read by the host driver\n"); destroy_all(); return AL_STREAM_NA; }
+			}
 		}
 	}
 	const double T1 = now_s();
@@ -449,6 +522,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 		std::unique_ptr<PieceReader> rd[2];
 		bool open_ok = true;
 		for (int i = 0; i < n_fn; ++i) {
+			if (bzf[i]) continue;
 			rd[i].reset(new PieceReader());
 			if (ranged ? !rd[i]->open_ranges(fn[i], range->rstart[i], range->rend[i], range->n_ranges, PIECE, 2 * rd_threads + 2, rd_threads)
 			           : !rd[i]->open(fn[i], range->start[i], range->end[i], PIECE, 2 * rd_threads + 2, rd_threads)) open_ok = false;
@@ -506,6 +580,43 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 		} else {
 		std::vector<char> carry[2]; long long base_off[2] = {range->start[0], range->start[1]}; bool eof[2] = {false, false};
 		for (int i = 0; i < n_fn; ++i) if (rd[i] && rd[i]->file_size() == 0) eof[i] = true;
+		auto file_text_size = [&](int i) -> double { return bzf[i] ? (double)bzf[i]->size * bzf[i]->ratio : (double)rd[i]->file_size(); };
+		std::vector<AlInfMember> bmem;
+		// BGZF file i: members until `want` more inflated bytes are in the slot's text, or the file has ended.  0, or -1 with the message printed
+		auto load_bgzf = [&](AlStreamSlot &S, int i, size_t want) -> int {
+			BgzfFile &B = *bzf[i];
+			uint64_t got = 0;
+			while (got < want && !eof[i]) {
+				// compressed bytes for what is still wanted, as far as the window has room: a launch takes one member's latency while all of its members are
+				// in flight, so the file's share of a batch is one launch where it fits, not one launch per piece
+				const uint64_t need_c = (uint64_t)((double)(want - got) / B.ratio * 1.1) + 65536;
+				while (!B.eof_file && al_bgzf_feed_left(B.feed) < need_c && B.feed.cap - al_bgzf_feed_left(B.feed) >= B.piece) {
+					const double tw = now_s();
+					if (!B.read_piece()) { fprintf(stderr, "[airlift] reading '%s' failed\n", fn[i]); return -1; }
+					t_wait_read += now_s() - tw;
+				}
+				const uint8_t *bytes = nullptr; uint64_t n_in = 0, n_out = 0, at = 0;
+				const int r = al_bgzf_take(B.feed, want - got, S.bz.cap_in, S.bz.cap_mem, bmem, &bytes, &n_in, &n_out, &at);
+				if (!bmem.empty()) {
+					size_t bad = 0; uint32_t bst = 0;
+					const int ar = al_stream_append_bgzf(S, i, bytes, (size_t)n_in, bmem.data(), bmem.size(), n_out, &bad, &bst);
+					if (ar > 0) fprintf(stderr, "[ERROR] airlift: --gpu-inflate: '%s': BGZF member at file offset %llu: status %u (%s)\n", fn[i], (unsigned long long)(at + bmem[bad].in_off), bst, al_inf_strerror((int)bst));
+					if (ar) return -1;
+					got += n_out;
+				}
+				if (r == AL_BGZF_BROKEN) { fprintf(stderr, "[ERROR] airlift: --gpu-inflate: '%s': no BGZF member at file offset %llu\n", fn[i], (unsigned long long)B.feed.file_off); return -1; }
+				if (r == AL_BGZF_MORE) {
+					if (B.eof_file) {
+						if (al_bgzf_feed_left(B.feed)) { fprintf(stderr, "[ERROR] airlift: --gpu-inflate: '%s': truncated BGZF member at file offset %llu\n", fn[i], (unsigned long long)B.feed.file_off); return -1; }
+						eof[i] = true; break;
+					}
+					const double tw = now_s();
+					if (!B.read_piece()) { fprintf(stderr, "[airlift] reading '%s' failed\n", fn[i]); return -1; }
+					t_wait_read += now_s() - tw;
+				}
+			}
+			return eof[i] ? al_stream_end_text(S, i) : 0;
+		};
 		double bytes_per_read = 360.0;                      // refined from every batch
 		uint64_t k = 0; bool stop = false;
 		while (!stop) {
@@ -522,7 +633,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			// The second batch is the size the run keeps unless the input is long (growing later re-obtains every workspace): 4 x the first
 			// probe, 8 x when the input has at least 6 M reads and this process has been getting device memory fast so far (index, slots).
 			if (k == 0 && !sized.load() && !env.probe_reads && !env.two_probes) {
-				double fs = 0; for (int i = 0; i < n_fn; ++i) fs += (double)rd[i]->file_size();
+				double fs = 0; for (int i = 0; i < n_fn; ++i) fs += file_text_size(i);
 				const double est0 = fs / bytes_per_read / (double)NL;                 // (360 bytes per read until a batch has been seen)
 				if (est0 >= 1.0e6) {
 					const AlAllocStat &as = al_alloc_stat(); const double ns = (double)as.dev_ns.load(), by = (double)as.dev_bytes.load();
@@ -557,9 +668,10 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 				// enough text for this file's share of the batch; at least one more piece unless the file is exhausted
 				const size_t share = (size_t)((double)(mr / n_fn) * bytes_per_read * 1.02) + 4096;
 				const size_t want = share > carry[i].size() ? share - carry[i].size() : 0;
-				const size_t n_pc = eof[i] ? 0 : (want + PIECE - 1) / PIECE;
-				if (al_stream_begin_text(S, i, carry[i].size() + n_pc * (PIECE + 16) + 64)) { err = -1; break; }
+				const size_t n_pc = eof[i] || bzf[i] ? 0 : (want + PIECE - 1) / PIECE;
+				if (al_stream_begin_text(S, i, carry[i].size() + (bzf[i] ? want + 2 * 65536 : n_pc * (PIECE + 16)) + 64)) { err = -1; break; }
 				if (!carry[i].empty() && al_stream_append_text(S, i, carry[i].data(), carry[i].size())) { err = -1; break; }
+				if (bzf[i] && load_bgzf(S, i, want)) { err = -1; break; }
 				for (size_t j = 0; j < n_pc && !eof[i]; ++j) {
 					Piece pc; const double tw = now_s();
 					if (!rd[i]->next(pc)) { if (rd[i]->has_failed()) { fprintf(stderr, "[airlift] reading '%s' failed\n", fn[i]); err = -1; } eof[i] = true; break; }
@@ -590,7 +702,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 			if (res.n_reads > 0) {
 				double used = 0; for (int i = 0; i < n_fn; ++i) used += (double)res.consumed[i];
 				bytes_per_read = used / (double)res.n_reads;
-				if (est_total_reads.load() == 0) { double fs = 0; for (int i = 0; i < n_fn; ++i) fs += (double)rd[i]->file_size(); est_total_reads = (long long)(fs / bytes_per_read); }
+				if (est_total_reads.load() == 0) { double fs = 0; for (int i = 0; i < n_fn; ++i) fs += file_text_size(i); est_total_reads = (long long)(fs / bytes_per_read); }
 				if (reads_cap_k.load() == (1 << 30)) {          // -K bases as reads: a record is about 2 L + name + 6 bytes
 					const double L = std::max(1.0, (bytes_per_read - 16.0) / 2.0);
 					reads_cap_k = (int)std::max(2.0, std::min(1.0e9, (double)k_bases / L));
@@ -646,6 +758,11 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 		fprintf(stderr, "[airlift] stream pipeline: %d lane(s) x (%d context(s), %d slots); init %.3f s; %llu fragments, %llu reads, %llu records, %.1f MB of %s in %.3f s (%.2f M reads/s); ingest: wait-slot %.3f load %.3f (wait-read %.3f) parse+carry %.3f; mappers (sum): setup %.3f run %.3f sam %.3f; writer %.3f; total %.3f s\n",
 		        NL, n_ctx_lane, n_slots_lane, T1 - T0, (unsigned long long)n_frag_total, (unsigned long long)n_reads_total, (unsigned long long)recs_out, bytes_out / 1e6, bam == 2 ? "BAM records (coordinate-sorted)" : bam ? "BAM records" : "SAM", T2 - T1, n_reads_total / std::max(1e-9, T2 - T1) / 1e6,
 		        t_wait_slot, t_load, t_wait_read, t_parse, ts, tr, tm, t_write, T2 - T0);
+		if (any_bgzf) {
+			AlStreamBgzf z; for (auto &sp : slots) { const AlStreamBgzf &b = sp->S.bz; z.kernel_s += b.kernel_s; z.members += b.members; z.bytes_in += b.bytes_in; z.bytes_out += b.bytes_out; z.launches += b.launches; }
+			fprintf(stderr, "[airlift] stream pipeline: BGZF input (k_inflate, into the slots' text): %llu members in %llu launches, %llu bytes in, %llu bytes out, kernels %.3f s (events; inside the ingest's load)\n",
+			        (unsigned long long)z.members, (unsigned long long)z.launches, (unsigned long long)z.bytes_in, (unsigned long long)z.bytes_out, z.kernel_s);
+		}
 		if (bam && rs->bgzf->dev_on) { rs->bgzf->timing_line(stderr, "stream pipeline"); fprintf(stderr, "[airlift] stream pipeline: BAM output: the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n", t_write, t_tail); }
 		else if (bam) fprintf(stderr, "[airlift] stream pipeline: BAM output: deflate (level %d, %d threads) %.3f s in all%s; the writer's %.3f s hold the part inside the batches; sort / merge / last blocks after the last batch %.3f s\n",
 		                 rs->bgzf->level, rs->bgzf->n_threads, rs->bgzf->t_deflate, rs->resume ? " so far (the host driver continues)" : "", t_write, t_tail);

@@ -44,6 +44,9 @@ extern "C" {
 #define AL_F_OUT_CG        0x020            /* -c: cg:Z: CIGAR in PAF */
 #define AL_F_PAF_NO_HIT    0x8000000        /* --paf-no-hit: a `name len 0 0 * * 0 0 0 0 0 0` line for a read without hits */
 #define AL_F_OUT_PAF       0x100000000LL    /* --paf (no analogue in the fork: its default) */
+/* Input: BGZF-compressed FASTQ files (bgzip, bcl-convert, DRAGEN) of the file-mapping calls stay with the stream driver, their members inflated on the
+ * GPU straight into the batch text.  Decided per file; without the flag, or for a gzip file that is not BGZF, the host reader inflates as before. */
+#define AL_F_IN_GPU_INFLATE 0x200000000LL   /* --gpu-inflate of the mapping commands (no analogue in the fork) */
 
 /* replaces mm_idxopt_t (minimap.h:101-105) */
 typedef struct {
