@@ -151,6 +151,8 @@ def load():
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci
+    if hasattr(L, "al_dbg_chain"):
+        L.al_dbg_chain.argtypes = [vp] * 9; L.al_dbg_chain.restype = ci
     L.al_version.restype = cs
     L.al_gen_cs.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs, ci]; L.al_gen_cs.restype = ci
     L.al_gen_MD.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs]; L.al_gen_MD.restype = ci
@@ -311,6 +313,24 @@ class Context:
         if n < 0:
             raise AirliftError("tap %s failed" % name)
         return arr[: n // arr.itemsize]
+
+    CHAIN_COUNTS = ("lane_lo", "lane_mid", "wave_mid", "tile_items", "tile_frags", "handed_back", "deferred", "deferred_coop", "compacted", "legacy_frags", "wave_segs", "order_frags",
+                    "whole_wave", "tie_round", "seg_big", "fallback_frags", "n_chain_fallback", "lds_ok", "tiles_ok", "tile_from", "lb1", "lb65", "lb129", "lmin")
+
+    def chain(self, anchors, a_off, tie_flag):
+        """al_dbg_chain: the chain stage on caller-supplied anchors ((n, 2) uint64; a_off uint64[n_frag + 1]; tie_flag uint32[n_frag]) for the
+        uploaded batch (not run).  Returns (frag_nu, u, uo, chained, counts by name); fragment f's chain list starts at a_off[f] + f."""
+        anchors = np.ascontiguousarray(anchors, dtype=np.uint64).reshape(-1, 2); a_off = np.ascontiguousarray(a_off, dtype=np.uint64); tie_flag = np.ascontiguousarray(tie_flag, dtype=np.uint32)
+        nf, tot = self.n_frag, int(a_off[-1])
+        if len(a_off) != nf + 1 or len(tie_flag) != nf or len(anchors) != tot:
+            raise AirliftError("al_dbg_chain: arrays do not fit the uploaded batch")
+        nu = np.zeros(nf, dtype=np.uint32); u = np.zeros(tot + nf + 1, dtype=np.uint64); uo = np.zeros(tot + nf + 1, dtype=np.uint32)
+        ch = np.zeros((max(tot, 1), 2), dtype=np.uint64); cnt = np.zeros(24, dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = load().al_dbg_chain(self.h, p(anchors), p(a_off), p(tie_flag), p(nu), p(u), p(uo), p(ch), p(cnt))
+        if rc != 0:
+            raise AirliftError("al_dbg_chain failed: %d" % rc)
+        return nu, u, uo, ch[:tot], dict(zip(self.CHAIN_COUNTS, (int(x) for x in cnt)))
 
     def alser_count(self):
         v = C.c_int64()

@@ -62,6 +62,7 @@ struct AlRegOut {            // per-read result header copied back to the host
 	uint32_t n_regs, reg_off;   // reg_off: index into the AlReg output array
 };
 
+#define AL_CHAIN_WHO_N 16                  // counters of al_ctx_s::chain_who (al_runtime.hip: CW_*)
 struct al_ctx_s {
 	const al_idx_t *mi = nullptr;
 	al_mapopt_t opt;
@@ -122,6 +123,7 @@ struct al_ctx_s {
 	DevBuf<uint64_t> vs_res;                 // two words per segment: ChainSeg::res
 	DevBuf<uint32_t> seg_cnt, seg_cnt0, seg_t1, vs_na, vs_meta, vs_cls, seg_key, seg_idx, seg_ord, fb_list, fb2_list, fb3_list, big_na, big_nt, big_tent, big_cuts, tie_frags, tie_sorted, heap_cnt;
 	uint64_t n_chain_fallback = 0;
+	uint64_t chain_who[AL_CHAIN_WHO_N] = {};          // which chaining kernels took how much of the last pass (al_runtime.hip: CW_*), for the al_dbg_chain tap
 	int max_qlen_sum = 0;                 // longest fragment of the resident batch
 	int max_rd_len = 0;                   // longest read of the resident batch
 	bool attr_chain_order = false, attr_regs_heavy = false;   // > 64 KB dynamic-LDS opt-in of two kernels: per device (hipFuncSetAttribute acts on the current device), kept per context

@@ -663,6 +663,11 @@ static int sort_u32_pairs(al_ctx_t *c, const uint32_t *k_in, uint32_t *k_out, co
 	return 0;
 }
 
+// Who did the work, counted on the host as the launches are made (al_dbg_chain reports them; the mapping path never reads them)
+enum { CW_LANE_LO, CW_LANE_MID, CW_WAVE_MID, CW_TILE_ITEMS, CW_TILE_FRAGS, CW_HANDED_BACK, CW_DEFERRED, CW_DEFERRED_COOP, CW_COMPACTED, CW_LEGACY_FRAGS, CW_WAVE_SEGS, CW_ORDER_FRAGS,
+       CW_WHOLE_WAVE, CW_TIE_ROUND, CW_SEG_BIG, CW_FALLBACK_FRAGS, CW_N };
+static_assert(CW_N <= AL_CHAIN_WHO_N, "al_ctx_t::chain_who holds a counter per CW_* name");
+
 #define LCH(C, L, LO, AOFF, NA, CH, UO, NU, LIST, N, SEG, UOFF, WS, STRIDE) do { const int n__ = (N); if (n__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_lds<C, L>), dim3((n__ + L - 1) / L), dim3(64), 0, s, c->anchors.p, AOFF, NA, c->frag_first.p, c->rd_len.p, CH, UO, NU, WS, LIST, n__, LO, c->P, c->counters.p, SEG, UOFF, STRIDE); } while (0)
 
 // Chaining of the fragments order[0 .. n) (more than 128 anchors each, or any size when the compact LDS rows cannot hold the
@@ -685,7 +690,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 	// (tests lower the two sizes so that ordinary fragments take the eight-wavefront forms; the list positions are then no bound any more)
 	const std::optional<int> &seg_big = al_env().test_seg_big;
 	const int segs_big = seg_big.value_or(8192), segm_big = seg_big ? std::max(1, *seg_big / 8) : 1024;
-	if (seg_big) { big_from = 0; big8_from = 0; }
+	if (seg_big) { big_from = 0; big8_from = 0; c->chain_who[CW_SEG_BIG] += (uint64_t)n; }
 	if (big8_from < 0 || big8_from > n) big8_from = 0;
 	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order + big8_from, n - big8_from, c->P, lmin, 0,
 	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, c->seg_cnt.p + big8_from, c->seg_cnt0.p + big8_from, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
@@ -749,6 +754,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 #define LWAVE(LIST, N) do { const int nw__ = (N); if (nw__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(nw__), dim3(64), 0, s, c->anchors.p, c->vs_off.p, c->vs_na.p, c->frag_first.p, c->rd_len.p, c->chain_tmp.p, c->u_tmp.p, (uint32_t *)nullptr, \
 		                               c->ws_i32.p, c->ws_u64.p, (LIST), nw__, c->P, c->counters.p, sg); } while (0)
 		const int nw = lds_ok ? n1 - (int)lb[7] : ns;
+		c->chain_who[CW_WAVE_SEGS] += (uint64_t)nw; if (lds_ok) for (int k = 3; k < 7; ++k) if (thin[k - 3]) c->chain_who[CW_WAVE_SEGS] += lb[k + 1] - lb[k];
 		if (al_env().trace && nw > 0) fprintf(stderr, "[airlift] trace: %d segments to the wavefront kernel (of %d segments in %d fragments)\n", nw, ns, n);
 		if (lds_ok) { LWAVE(so1 + lb[7], n1 - (int)lb[7]); for (int k = 3; k < 7; ++k) if (thin[k - 3]) LWAVE(so1 + lb[k], (int)(lb[k + 1] - lb[k])); } else { LWAVE(so0, ns0); LWAVE(so1, n1); }
 #undef LWAVE
@@ -783,6 +789,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 			c->attr_chain_order = true;
 		}
 		if (c->fb2_list.ensure((size_t)n_fb + 2)) return -1;
+		c->chain_who[CW_ORDER_FRAGS] += n_fb;
 		AL_HIP_CHECK(hipMemsetAsync(fb_cnt, 0, 8, s));
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<16>), dim3(n_fb), dim3(1024), lds16, s, c->fb_list.p, (int)n_fb, c->a_off.p, c->frag_nu.p, c->u.p, c->chained.p, (const uint64_t *)c->ws_u64.p, c->u_tmp.p, c->chain_tmp.p, c->fb2_list.p, fb_cnt, c->ws_i32.p, nu_block, 1 << 30);
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<1>), dim3(n_fb), dim3(64), lds, s, c->fb_list.p, (int)n_fb, c->a_off.p, c->frag_nu.p, c->u.p, c->chained.p, (const uint64_t *)c->ws_u64.p, c->u_tmp.p, c->chain_tmp.p, c->fb2_list.p, fb_cnt, c->ws_i32.p, 0, nu_block);
@@ -794,6 +801,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 	if (al_env().trace) fprintf(stderr, "[airlift] trace: chain order: %llu fragments with tied chain starts among > 64 chains (%s keys), %u of them chained whole by the wavefront kernel\n", (unsigned long long)c->n_chain_fallback, keep_keys ? "with" : "without", n_fb);
 	if (n_fb > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(n_fb), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
 	                                 c->ws_i32.p, c->ws_u64.p, fb, (int)n_fb, c->P, c->counters.p, whole);
+	c->chain_who[CW_WHOLE_WAVE] += n_fb;
 	if (ev(ST_SEG_MERGE)) return -1;
 	return 0;
 }
@@ -802,6 +810,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 static int chain_legacy(al_ctx_t *c, const uint32_t *list, int n, bool lds_ok, const uint32_t *skip_flag)
 {
 	if (n <= 0) return 0;
+	c->chain_who[CW_LEGACY_FRAGS] += (uint64_t)n;
 	const uint64_t total = c->n_anchor_total;
 	if (c->ws_i32.ensure(total * 4 + 4, false, c->stream) || c->ws_u64.ensure(total + 1, false, c->stream) ||
 	    c->chain_tmp.ensure(total + 1, false, c->stream) || c->u_tmp.ensure(total + 1, false, c->stream) || c->okey_tmp.ensure(total + 2, false, c->stream)) return -1;
@@ -818,6 +827,7 @@ static int chain_fallback(al_ctx_t *c, const uint32_t *fb, int n_fb, bool lds_ok
 {
 	hipStream_t s = c->stream;
 	if (n_fb <= 0) return 0;
+	c->chain_who[CW_FALLBACK_FRAGS] += (uint64_t)n_fb;
 	if (c->v_na.ensure((size_t)n_fb + 2) || c->v_nseg.ensure((size_t)n_fb + 2) || c->v_a_off.ensure((size_t)n_fb + 2) || c->v_first64.ensure((size_t)n_fb + 2) ||
 	    c->v_first.ensure((size_t)n_fb + 2) || c->v_rd_len.ensure(2 * (size_t)n_fb + 2) || c->v_order.ensure((size_t)n_fb + 2) || c->v_nu.ensure((size_t)n_fb + 2)) return -1;
 	hipLaunchKernelGGL(k_fb_meta, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_na.p, c->frag_first.p, c->v_na.p, c->v_nseg.p);
@@ -871,6 +881,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 		AL_HIP_CHECK(hipMemcpyAsync(h, cnts, 12, hipMemcpyDeviceToHost, s));
 		AL_HIP_CHECK(hipStreamSynchronize(s));
 		const uint32_t n_def = h[1], n_cmp = h[2];
+		c->chain_who[CW_TILE_ITEMS] += S.n_items; c->chain_who[CW_TILE_FRAGS] += S.ent[6] - S.ent[0]; c->chain_who[CW_DEFERRED] += n_def; c->chain_who[CW_COMPACTED] += n_cmp;
 		if (n_def > cap) { fprintf(stderr, "[airlift] deferred-segment list overflow (%u > %zu)\n", n_def, cap); return -1; }
 		if (n_def > 0) {
 			// the deferred segments by size class (stable: inside a class they keep the tiles' order, i.e. memory order inside a tile)
@@ -916,6 +927,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 				int k1 = k; while (k1 + 1 < 9 && thin[k1 + 1]) ++k1;
 				const int nn = (int)(cb[k1 + 1] - cb[k]);
 				if (nn > 0) {
+					c->chain_who[CW_DEFERRED_COOP] += (uint64_t)nn;
 					if (k1 <= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<48>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, c->vs_off.p, c->vs_na.p, c->vs_meta.p, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p,
 					                                (const uint32_t *)c->seg_ord.p + cb[k], nn, c->P, c->counters.p);
 					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<128>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, c->vs_off.p, c->vs_na.p, c->vs_meta.p, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p,
@@ -933,7 +945,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 	} else if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
 	if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
 	if (n_fb > 0) {
-		c->n_chain_fallback += n_fb;
+		c->n_chain_fallback += n_fb; c->chain_who[CW_HANDED_BACK] += n_fb;
 		// (the list the kernels appended to atomically, in ascending fragment order: the same virtual batch on every run)
 		size_t bytes = 0;
 		if (c->fbk_list.ensure((size_t)n_fb + 2)) return -1;
@@ -943,6 +955,179 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 		if (chain_fallback(c, c->fbk_list.p, (int)n_fb, lds_ok)) return -1;
 	}
 	if (ev(ST_SEG_CHAIN_WAVE)) return -1;
+	return 0;
+}
+
+// ---- the chaining half of a pass (run_seed_chain), in the pieces the al_dbg_chain tap runs too --------------------------------------------
+// The fragment list of a pass by size class, and which kernels the options in force allow: made by chain_plan
+struct ChainPlan {
+	int nl; bool first;
+	const uint32_t *order;                // the list, ordered by size class (stable)
+	uint32_t lb1, lb33, lb65, lb81, lb97, lb129, lb257, lb513, lb257x, lb513x, lb1025, lb2049, lb4097, lb8193, lb_big;   // first entry with at least that many anchors (lb257 / lb513: capped by the block sorts' bound)
+	bool lds_ok, tiles_ok; uint32_t tile_from; int lmin;
+};
+static int chain_plan(al_ctx_t *c, const uint32_t *list, int nl, bool first, ChainPlan &pl)
+{
+	hipStream_t s = c->stream;
+	// Fragments ordered by anchor count: the sort kernels and the chaining kernels are chosen per size class, and the lanes of one
+	// wavefront get equal trip counts.  Class boundaries = lower bounds in the sorted counts.
+	// The LDS chaining kernels keep 16-bit window-relative positions and 8-bit row indices: they need max_dist_x < 2^15 and
+	// max_chain_iter >= 128 (true for the short-read preset); other option values go through the wave-per-entry kernel.
+	const int mdx = std::max(std::max(c->opt.max_gap_ref, c->opt.max_frag_len), c->opt.max_gap);
+	const bool lds_ok = mdx <= 0x7fff && c->opt.max_chain_iter >= 128 && !((c->P.dbg >> 27) & 1) && c->max_qlen_sum <= 0xfff;   // 12-bit query positions in the compact rows
+	if (first) hipLaunchKernelGGL(k_iota_u32, dim3((nl + 255) / 256), dim3(256), 0, s, c->chain_idx.p, (uint32_t)nl);
+	// The list by SIZE CLASS, not by exact count: the class boundaries are all the kernels below ask for, and inside a class the fragments stay in
+	// memory order (the sort is stable) -- the blocks that run side by side then work on neighbouring ranges of the anchor arrays instead of
+	// ranges scattered over tens of gigabytes (a TLB miss per tile cost the tile kernel a third of its time), and the lanes of the lane-per-fragment
+	// kernels read neighbouring fragments.  One 5-bit radix pass instead of four 8-bit ones.
+	uint32_t lb[15];
+	{   // AL_TEST_SORT_BLK / AL_TEST_SORT_BIG (tests): smallest anchor count that goes to the block / device-wide sort
+		const char *const e1 = al_env().test_sort_blk, *const e2 = al_env().test_sort_big;
+		uint32_t t_blk = e1 ? (uint32_t)atoi(e1) : 1025u, t_big = e2 ? (uint32_t)atoi(e2) : 8193u;   // above 8192 anchors: device-wide radix sort
+		if (t_blk < 65u) t_blk = 65u; if (t_blk > 1025u) t_blk = 1025u; if (t_big < t_blk) t_big = t_blk; if (t_big > 8193u) t_big = 8193u;
+		{ int rb = 1; while ((1ULL << rb) < c->mi->seq.size()) ++rb; if (33 + rb + 16 > 64) t_big = t_blk; }   // compact keys of the block sort: strand | contig | position | list in 64 bits
+		const uint32_t thr[15] = {65, 81, 97, 129, t_blk, t_big, std::min(std::max(t_blk, 2049u), t_big), std::min(std::max(t_blk, 4097u), t_big), std::min(std::max(t_blk, 8193u), t_big),
+		                          std::min(257u, t_blk), std::min(513u, t_blk), 1, 33, 257, 513};
+		std::vector<uint32_t> T(thr, thr + 15);
+		for (uint32_t t : {17u, 25u, 41u, 49u, 1025u, 2049u, 4097u, 8193u}) T.push_back(t);   // the lane kernels' row sizes; the large classes, so that the heaviest items start first
+		std::sort(T.begin(), T.end()); T.erase(std::unique(T.begin(), T.end()), T.end());
+		SizeThr ST; ST.n = (int)T.size();
+		if (ST.n > 28) { fprintf(stderr, "[airlift] internal: too many size classes\n"); return -1; }
+		for (int i = 0; i < 28; ++i) ST.v[i] = i < ST.n ? T[i] : 0xffffffffu;
+		if (c->chain_cls.ensure((size_t)nl + 1)) return -1;
+		hipLaunchKernelGGL(k_size_class, dim3((nl + 255) / 256), dim3(256), 0, s, first ? (const uint32_t *)c->frag_na.p : (const uint32_t *)c->tmp_u32.p, nl, ST, c->chain_cls.p);
+		size_t bytes = 0;
+		AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
+		if (c->scan_tmp.ensure(bytes + 16)) return -1;
+		AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
+		uint32_t thr_cls[15];                                                 // count >= thr[k]  <=>  class >= (rank of thr[k] among the thresholds) + 1
+		for (int k = 0; k < 15; ++k) thr_cls[k] = (uint32_t)(std::lower_bound(T.begin(), T.end(), thr[k]) - T.begin()) + 1u;
+		if (lower_bounds(c, c->chain_key.p, (uint32_t)nl, thr_cls, 15, lb)) return -1;
+	}
+	const uint32_t *order = c->chain_idx2.p;
+	const uint32_t lb1 = lb[11], lb33 = lb[12], lb257x = lb[13], lb513x = lb[14];
+	const uint32_t lb65 = lb[0], lb81 = lb[1], lb97 = lb[2], lb129 = lb[3], lb1025 = lb[4], lb_big = lb[5], lb2049 = lb[6], lb4097 = lb[7], lb8193 = lb[8], lb257 = lb[9], lb513 = lb[10];
+	// Fragments of more than 128 anchors: the tile kernel (al_kernels_chain.hip).  Its compact rows need what the lane kernels need, and a
+	// segment that can hold a chain must have >= 2 anchors (min_cnt anchors, min_chain_score at <= k + 1 per anchor: chain.c:60-73,118-124);
+	// other option values: the segment-wise kernels (chain_legacy).  AL_TEST_TILE_ALL (tests): every fragment through the tile kernel.
+	int lmin = c->opt.min_cnt > 1 ? c->opt.min_cnt : 1;
+	{ const int per = c->mi->k + 1, need = (c->opt.min_chain_score + per - 1) / per; if (need > lmin) lmin = need; }
+	const bool tile_all = al_env().test_tile_all;
+	const bool tiles_ok = lds_ok && lmin >= 2 && c->opt.max_chain_skip >= 7 && !((c->P.dbg >> 28) & 1);   // (at most 7 predecessors in the segments the tile kernel chains itself: no skip rule)
+	const uint32_t tile_from = !tiles_ok ? (uint32_t)nl : tile_all ? lb1 : lb129;
+	if (c->fb_list.ensure((size_t)nl + 2)) return -1;
+	pl.nl = nl; pl.first = first; pl.order = order;
+	pl.lb1 = lb1; pl.lb33 = lb33; pl.lb65 = lb65; pl.lb81 = lb81; pl.lb97 = lb97; pl.lb129 = lb129; pl.lb257 = lb257; pl.lb513 = lb513; pl.lb257x = lb257x; pl.lb513x = lb513x;
+	pl.lb1025 = lb1025; pl.lb2049 = lb2049; pl.lb4097 = lb4097; pl.lb8193 = lb8193; pl.lb_big = lb_big;
+	pl.lds_ok = lds_ok; pl.tiles_ok = tiles_ok; pl.tile_from = tile_from; pl.lmin = lmin;
+	return 0;
+}
+
+// fragments of up to 128 anchors: the lane-per-fragment kernels
+static int chain_small(al_ctx_t *c, const ChainPlan &pl)
+{
+	hipStream_t s = c->stream;
+	const uint32_t *const order = pl.order; const bool lds_ok = pl.lds_ok;
+	const uint32_t lb65 = pl.lb65, lb81 = pl.lb81, lb97 = pl.lb97, lb129 = pl.lb129, tile_from = pl.tile_from;
+	const ChainSeg nosg{nullptr, nullptr, (const uint32_t *)c->tie_list.p, 1, nullptr};
+	// chain-end scratch of the whole-fragment lane kernels: 64 words per entry of the <= 64-anchor classes, 128 above, by list position
+	const uint32_t n_lo = std::min(lb65, tile_from), n_mid_end = std::min(lb129, tile_from);
+	if (lds_ok && c->ws_u64.ensure((size_t)n_lo * 64 + (size_t)(n_mid_end > lb65 ? n_mid_end - lb65 : 0u) * 128 + 64, false, s)) return -1;
+	// The lane-per-fragment kernels (fragments of up to 128 anchors, memory latency) run on a stream of their own: beside the tile sorts
+	// of the large fragments and beside the tile kernel, which takes the rest of the list.
+	hipStream_t const s_main = s;
+	const bool use_ovl = al_env().chain_ovl;   // (AL_CHAIN_OVL=0: on the main stream, after the sorts)
+	// (round 5) ... on TWO streams, the classes in turn (AL_CHAIN_OVL2=0: one): a class ends in the tail of its slowest wavefronts, and the next one's start fills it
+	const bool two = al_env().chain_ovl2;
+	if (use_ovl) { AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[2], 0)); if (two) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[2], 0)); }
+	{ hipStream_t s = use_ovl ? c->on(AL_ROLE_OVL1) : s_main; int turn = 0;
+#define NEXT_S() do { if (use_ovl && two) s = c->on(AL_ROLE_OVL1 + (++turn & 1)); } while (0)
+#define LFR(C, L, A, B) LCH(C, L, -1, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order + (A), (int)((B) - (A)), nosg, c->uo.p, c->ws_u64.p + (size_t)n_lo * 64 + (size_t)((A) - lb65) * 128, 128)
+#define LFRLO(C, L, LO) LCH(C, L, LO, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order, (int)n_lo, nosg, c->uo.p, c->ws_u64.p, 64)
+	if (lds_ok) { LFRLO(16, 64, -1); NEXT_S(); LFRLO(24, 64, 16); NEXT_S(); LFRLO(32, 64, 24); NEXT_S(); }
+	if (lds_ok) { LFRLO(40, 64, 32); NEXT_S(); LFRLO(48, 64, 40); NEXT_S(); }
+	if (lds_ok) { LFRLO(64, 64, 48); NEXT_S(); c->chain_who[CW_LANE_LO] += n_lo; }
+	if (lds_ok && n_mid_end > lb65) {   // exact ranges of the size-ordered list (lane counts differ between these classes)
+		// 64-lane wavefronts hold more fragments per CU but need enough of them to cover the chip; a thin class runs on half waves
+		const uint32_t fill = 64u * 3u * 256u * 2u;
+		const uint32_t wave_max = al_env().chain_wave_max;
+		uint32_t from = lb65;
+		if (lb129 - lb65 < wave_max) {   // few fragments of 65 ... 128 anchors (a small batch): a wavefront each is over sooner than a lane each
+			hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(lb129 - lb65), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
+			                   (int32_t *)nullptr, (uint64_t *)nullptr, order + lb65, (int)(lb129 - lb65), c->P, c->counters.p, nosg);   // (<= 128 anchors: its rows are in LDS, no scratch)
+			hipLaunchKernelGGL(k_uo_fill, dim3(lb129 - lb65), dim3(64), 0, s, order + lb65, (int)(lb129 - lb65), c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, (const uint32_t *)c->tie_list.p);
+			c->chain_who[CW_WAVE_MID] += lb129 - lb65;
+		} else {
+			if (lb81 - lb65 >= fill) { LFR(80, 64, lb65, lb81); from = lb81; NEXT_S(); }
+			if (from == lb81 && lb97 - lb81 >= fill) { LFR(96, 64, lb81, lb97); from = lb97; NEXT_S(); }
+			LFR(128, 32, from, lb129);
+			c->chain_who[CW_LANE_MID] += lb129 - lb65;
+		}
+	}
+	if (use_ovl && two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->on(AL_ROLE_OVL2))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[4], 0)); s = c->on(AL_ROLE_OVL1); }   // (joined on ovl1: one event for the main stream)
+	if (use_ovl) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[3], s)); c->ovl_pending = true; } }
+#undef NEXT_S
+#undef LFR
+#undef LFRLO
+	return 0;
+}
+
+// everything else: the tile kernel, or (option values outside its range) the segment-wise kernels
+static int chain_large(al_ctx_t *c, const ChainPlan &pl)
+{
+	hipStream_t s = c->stream;
+	const bool first = pl.first, lds_ok = pl.lds_ok, tiles_ok = pl.tiles_ok; const int nl = pl.nl, lmin = pl.lmin;
+	const uint32_t *const order = pl.order;
+	const uint32_t tile_from = pl.tile_from, lb33 = pl.lb33, lb65 = pl.lb65, lb129 = pl.lb129, lb257x = pl.lb257x, lb513x = pl.lb513x;
+	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
+	// (the four chain_lds intervals are empty since the lane-per-fragment kernels of the <= 128-anchor fragments moved to ovl1, beside the block
+	//  sorts and the tile kernel: their time is inside anchor_sort_blk / chain_tile; the names stay so that the stage table keeps its columns)
+	if (ev(ST_CHAIN_LDS32) || ev(ST_CHAIN_LDS48) || ev(ST_CHAIN_LDS64) || ev(ST_CHAIN_LDS128)) return -1;
+	if (tiles_ok) {
+		TileSched S; const uint32_t b[6] = {tile_from, std::max(tile_from, lb33), std::max(tile_from, lb65), std::max(tile_from, lb129), std::max(tile_from, lb257x), std::max(tile_from, lb513x)};
+		for (int k = 0; k < 6; ++k) S.ent[k] = b[k]; S.ent[6] = (uint32_t)nl;
+		S.item[0] = 0; for (int k = 0; k < 6; ++k) { const uint32_t per = 32u >> k; S.item[k + 1] = S.item[k] + (S.ent[k + 1] - S.ent[k] + per - 1) / per; }
+		S.n_items = S.item[6];
+		if (chain_tiles(c, order, S, (const uint32_t *)c->tie_list.p, lmin, first, lds_ok)) return -1;
+	} else {
+		if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
+		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
+		const uint32_t tail = lds_ok ? lb129 : 0u;
+		if (chain_legacy(c, order + tail, nl - (int)tail, lds_ok, (const uint32_t *)c->tie_list.p)) return -1;
+		if (ev(ST_SEG_CHAIN_WAVE)) return -1;
+	}
+	return 0;
+}
+
+// second round: the flagged fragments (their anchors merged on the side stream), a fragment per item, any size
+static int chain_ties(al_ctx_t *c, const ChainPlan &pl)
+{
+	hipStream_t s = c->stream;
+	const bool first = pl.first, lds_ok = pl.lds_ok, tiles_ok = pl.tiles_ok; const int nl = pl.nl, lmin = pl.lmin;
+	const uint32_t *const order = pl.order;
+	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
+	if (c->tie_frags.ensure((size_t)nl + 2)) return -1;
+	uint32_t *cnt = (uint32_t *)(c->counters.p + 15);
+	AL_HIP_CHECK(hipMemsetAsync(cnt, 0, 8, s));
+	hipLaunchKernelGGL(k_collect_flagged, dim3((nl + 255) / 256), dim3(256), 0, s, order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, cnt);
+	uint32_t n_tie = 0, n_spec_used = 0;
+	AL_HIP_CHECK(hipMemcpyAsync(&n_tie, cnt, 4, hipMemcpyDeviceToHost, s));
+	if (!first && c->n_spec > 0) AL_HIP_CHECK(hipMemcpyAsync(&n_spec_used, c->spec_cnt.p + 2, 4, hipMemcpyDeviceToHost, s));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	if (!first && c->n_spec > 0) c->spec_idle = n_spec_used ? 0u : c->spec_idle + 1u;
+	c->chain_who[CW_TIE_ROUND] += n_tie;
+	if (n_tie > 0) {
+		size_t bytes = 0;    // ascending fragment ids: a deterministic order (the collection above appends atomically)
+		if (c->tie_sorted.ensure((size_t)n_tie + 2)) return -1;
+		AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
+		if (c->scan_tmp.ensure(bytes + 16)) return -1;
+		AL_HIP_CHECK(rocprim::radix_sort_keys(c->scan_tmp.p, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
+		if (tiles_ok) {
+			TileSched S; for (int k = 0; k < 6; ++k) { S.ent[k] = 0; S.item[k] = 0; } S.ent[6] = n_tie; S.item[6] = n_tie; S.n_items = n_tie;   // a fragment per item, any size
+			if (chain_tiles(c, c->tie_sorted.p, S, nullptr, lmin, false, lds_ok)) return -1;
+		} else if (chain_legacy(c, c->tie_sorted.p, (int)n_tie, lds_ok, nullptr)) return -1;
+	}
+	if (ev(ST_SEG_MERGE)) return -1;
 	return 0;
 }
 
@@ -1017,95 +1202,12 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		c->n_anchor_total = base_off + total;
 	}
 	if (ev(ST_SCAN)) return -1;
-	// Fragments ordered by anchor count: the sort kernels and the chaining kernels are chosen per size class, and the lanes of one
-	// wavefront get equal trip counts.  Class boundaries = lower bounds in the sorted counts.
-	// The LDS chaining kernels keep 16-bit window-relative positions and 8-bit row indices: they need max_dist_x < 2^15 and
-	// max_chain_iter >= 128 (true for the short-read preset); other option values go through the wave-per-entry kernel.
-	const int mdx = std::max(std::max(c->opt.max_gap_ref, c->opt.max_frag_len), c->opt.max_gap);
-	const bool lds_ok = mdx <= 0x7fff && c->opt.max_chain_iter >= 128 && !((c->P.dbg >> 27) & 1) && c->max_qlen_sum <= 0xfff;   // 12-bit query positions in the compact rows
-	if (first) hipLaunchKernelGGL(k_iota_u32, dim3((nl + 255) / 256), dim3(256), 0, s, c->chain_idx.p, (uint32_t)nl);
-	// The list by SIZE CLASS, not by exact count: the class boundaries are all the kernels below ask for, and inside a class the fragments stay in
-	// memory order (the sort is stable) -- the blocks that run side by side then work on neighbouring ranges of the anchor arrays instead of
-	// ranges scattered over tens of gigabytes (a TLB miss per tile cost the tile kernel a third of its time), and the lanes of the lane-per-fragment
-	// kernels read neighbouring fragments.  One 5-bit radix pass instead of four 8-bit ones.
-	uint32_t lb[15];
-	{   // AL_TEST_SORT_BLK / AL_TEST_SORT_BIG (tests): smallest anchor count that goes to the block / device-wide sort
-		const char *const e1 = al_env().test_sort_blk, *const e2 = al_env().test_sort_big;
-		uint32_t t_blk = e1 ? (uint32_t)atoi(e1) : 1025u, t_big = e2 ? (uint32_t)atoi(e2) : 8193u;   // above 8192 anchors: device-wide radix sort
-		if (t_blk < 65u) t_blk = 65u; if (t_blk > 1025u) t_blk = 1025u; if (t_big < t_blk) t_big = t_blk; if (t_big > 8193u) t_big = 8193u;
-		{ int rb = 1; while ((1ULL << rb) < c->mi->seq.size()) ++rb; if (33 + rb + 16 > 64) t_big = t_blk; }   // compact keys of the block sort: strand | contig | position | list in 64 bits
-		const uint32_t thr[15] = {65, 81, 97, 129, t_blk, t_big, std::min(std::max(t_blk, 2049u), t_big), std::min(std::max(t_blk, 4097u), t_big), std::min(std::max(t_blk, 8193u), t_big),
-		                          std::min(257u, t_blk), std::min(513u, t_blk), 1, 33, 257, 513};
-		std::vector<uint32_t> T(thr, thr + 15);
-		for (uint32_t t : {17u, 25u, 41u, 49u, 1025u, 2049u, 4097u, 8193u}) T.push_back(t);   // the lane kernels' row sizes; the large classes, so that the heaviest items start first
-		std::sort(T.begin(), T.end()); T.erase(std::unique(T.begin(), T.end()), T.end());
-		SizeThr ST; ST.n = (int)T.size();
-		if (ST.n > 28) { fprintf(stderr, "[airlift] internal: too many size classes\n"); return -1; }
-		for (int i = 0; i < 28; ++i) ST.v[i] = i < ST.n ? T[i] : 0xffffffffu;
-		if (c->chain_cls.ensure((size_t)nl + 1)) return -1;
-		hipLaunchKernelGGL(k_size_class, dim3((nl + 255) / 256), dim3(256), 0, s, first ? (const uint32_t *)c->frag_na.p : (const uint32_t *)c->tmp_u32.p, nl, ST, c->chain_cls.p);
-		size_t bytes = 0;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
-		if (c->scan_tmp.ensure(bytes + 16)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
-		uint32_t thr_cls[15];                                                 // count >= thr[k]  <=>  class >= (rank of thr[k] among the thresholds) + 1
-		for (int k = 0; k < 15; ++k) thr_cls[k] = (uint32_t)(std::lower_bound(T.begin(), T.end(), thr[k]) - T.begin()) + 1u;
-		if (lower_bounds(c, c->chain_key.p, (uint32_t)nl, thr_cls, 15, lb)) return -1;
-	}
-	const uint32_t *order = c->chain_idx2.p;
-	const uint32_t lb1 = lb[11], lb33 = lb[12], lb257x = lb[13], lb513x = lb[14];
-	const uint32_t lb65 = lb[0], lb81 = lb[1], lb97 = lb[2], lb129 = lb[3], lb1025 = lb[4], lb_big = lb[5], lb2049 = lb[6], lb4097 = lb[7], lb8193 = lb[8], lb257 = lb[9], lb513 = lb[10];
-	// Fragments of more than 128 anchors: the tile kernel (al_kernels_chain.hip).  Its compact rows need what the lane kernels need, and a
-	// segment that can hold a chain must have >= 2 anchors (min_cnt anchors, min_chain_score at <= k + 1 per anchor: chain.c:60-73,118-124);
-	// other option values: the segment-wise kernels (chain_legacy).  AL_TEST_TILE_ALL (tests): every fragment through the tile kernel.
-	int lmin = c->opt.min_cnt > 1 ? c->opt.min_cnt : 1;
-	{ const int per = c->mi->k + 1, need = (c->opt.min_chain_score + per - 1) / per; if (need > lmin) lmin = need; }
-	const bool tile_all = al_env().test_tile_all;
-	const bool tiles_ok = lds_ok && lmin >= 2 && c->opt.max_chain_skip >= 7 && !((c->P.dbg >> 28) & 1);   // (at most 7 predecessors in the segments the tile kernel chains itself: no skip rule)
-	const uint32_t tile_from = !tiles_ok ? (uint32_t)nl : tile_all ? lb1 : lb129;
-	if (c->fb_list.ensure((size_t)nl + 2)) return -1;
+	// Fragments ordered by size class; which kernels chain them (chain_plan)
+	ChainPlan pl;
+	if (chain_plan(c, list, nl, first, pl)) return -1;
+	const uint32_t *const order = pl.order;
+	const uint32_t lb65 = pl.lb65, lb129 = pl.lb129, lb257 = pl.lb257, lb513 = pl.lb513, lb1025 = pl.lb1025, lb2049 = pl.lb2049, lb4097 = pl.lb4097, lb_big = pl.lb_big;
 	if (ev(ST_ORDER)) return -1;
-	auto chain_small = [&]() -> int {   // fragments of up to 128 anchors: the lane-per-fragment kernels
-		const ChainSeg nosg{nullptr, nullptr, (const uint32_t *)c->tie_list.p, 1, nullptr};
-		// chain-end scratch of the whole-fragment lane kernels: 64 words per entry of the <= 64-anchor classes, 128 above, by list position
-		const uint32_t n_lo = std::min(lb65, tile_from), n_mid_end = std::min(lb129, tile_from);
-		if (lds_ok && c->ws_u64.ensure((size_t)n_lo * 64 + (size_t)(n_mid_end > lb65 ? n_mid_end - lb65 : 0u) * 128 + 64, false, s)) return -1;
-		// The lane-per-fragment kernels (fragments of up to 128 anchors, memory latency) run on a stream of their own: beside the tile sorts
-		// of the large fragments and beside the tile kernel, which takes the rest of the list.
-		hipStream_t const s_main = s;
-		const bool use_ovl = al_env().chain_ovl;   // (AL_CHAIN_OVL=0: on the main stream, after the sorts)
-		// (round 5) ... on TWO streams, the classes in turn (AL_CHAIN_OVL2=0: one): a class ends in the tail of its slowest wavefronts, and the next one's start fills it
-		const bool two = al_env().chain_ovl2;
-		if (use_ovl) { AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[2], 0)); if (two) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[2], 0)); }
-		{ hipStream_t s = use_ovl ? c->on(AL_ROLE_OVL1) : s_main; int turn = 0;
-#define NEXT_S() do { if (use_ovl && two) s = c->on(AL_ROLE_OVL1 + (++turn & 1)); } while (0)
-#define LFR(C, L, A, B) LCH(C, L, -1, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order + (A), (int)((B) - (A)), nosg, c->uo.p, c->ws_u64.p + (size_t)n_lo * 64 + (size_t)((A) - lb65) * 128, 128)
-#define LFRLO(C, L, LO) LCH(C, L, LO, c->a_off.p, c->frag_na.p, c->chained.p, c->u.p, c->frag_nu.p, order, (int)n_lo, nosg, c->uo.p, c->ws_u64.p, 64)
-		if (lds_ok) { LFRLO(16, 64, -1); NEXT_S(); LFRLO(24, 64, 16); NEXT_S(); LFRLO(32, 64, 24); NEXT_S(); }
-		if (lds_ok) { LFRLO(40, 64, 32); NEXT_S(); LFRLO(48, 64, 40); NEXT_S(); }
-		if (lds_ok) { LFRLO(64, 64, 48); NEXT_S(); }
-		if (lds_ok && n_mid_end > lb65) {   // exact ranges of the size-ordered list (lane counts differ between these classes)
-			// 64-lane wavefronts hold more fragments per CU but need enough of them to cover the chip; a thin class runs on half waves
-			const uint32_t fill = 64u * 3u * 256u * 2u;
-			const uint32_t wave_max = al_env().chain_wave_max;
-			uint32_t from = lb65;
-			if (lb129 - lb65 < wave_max) {   // few fragments of 65 ... 128 anchors (a small batch): a wavefront each is over sooner than a lane each
-				hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(lb129 - lb65), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
-				                   (int32_t *)nullptr, (uint64_t *)nullptr, order + lb65, (int)(lb129 - lb65), c->P, c->counters.p, nosg);   // (<= 128 anchors: its rows are in LDS, no scratch)
-				hipLaunchKernelGGL(k_uo_fill, dim3(lb129 - lb65), dim3(64), 0, s, order + lb65, (int)(lb129 - lb65), c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, (const uint32_t *)c->tie_list.p);
-			} else {
-				if (lb81 - lb65 >= fill) { LFR(80, 64, lb65, lb81); from = lb81; NEXT_S(); }
-				if (from == lb81 && lb97 - lb81 >= fill) { LFR(96, 64, lb81, lb97); from = lb97; NEXT_S(); }
-				LFR(128, 32, from, lb129);
-			}
-		}
-		if (use_ovl && two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], c->on(AL_ROLE_OVL2))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL1), c->ev_ovl[4], 0)); s = c->on(AL_ROLE_OVL1); }   // (joined on ovl1: one event for the main stream)
-		if (use_ovl) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[3], s)); c->ovl_pending = true; } }
-#undef NEXT_S
-#undef LFR
-#undef LFRLO
-		return 0;
-	};
 	{
 		if (c->tie_list.ensure((size_t)c->n_frag + 2)) return -1;         // one flag per fragment id
 		unsigned int *tie_cnt = nullptr;
@@ -1202,7 +1304,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		if (small_by_blk) AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));
 #undef LREG
 		// (enqueued before the merge kernels of the side streams below: whichever hardware queue ovl1 shares, these do not wait behind one of those)
-		if (chain_small()) return -1;
+		if (chain_small(c, pl)) return -1;
 		if (ev(ST_ANCHOR_SORT_BLK)) return -1;
 		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[1], 0));                 // the device-wide sort (ovl0, started before the tile sorts)
 		if (ev(ST_ANCHOR_SORT_BIG)) return -1;
@@ -1262,49 +1364,11 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		AL_HIP_CHECK(hipEventRecord(evs[1], c->on(AL_ROLE_SIDE)));
 		if (ev(ST_ANCHOR_HEAP)) return -1;
 	}
-	{
-		// (the four chain_lds intervals are empty since the lane-per-fragment kernels of the <= 128-anchor fragments moved to ovl1, beside the block
-		//  sorts and the tile kernel: their time is inside anchor_sort_blk / chain_tile; the names stay so that the stage table keeps its columns)
-		if (ev(ST_CHAIN_LDS32) || ev(ST_CHAIN_LDS48) || ev(ST_CHAIN_LDS64) || ev(ST_CHAIN_LDS128)) return -1;
-		if (tiles_ok) {
-			TileSched S; const uint32_t b[6] = {tile_from, std::max(tile_from, lb33), std::max(tile_from, lb65), std::max(tile_from, lb129), std::max(tile_from, lb257x), std::max(tile_from, lb513x)};
-			for (int k = 0; k < 6; ++k) S.ent[k] = b[k]; S.ent[6] = (uint32_t)nl;
-			S.item[0] = 0; for (int k = 0; k < 6; ++k) { const uint32_t per = 32u >> k; S.item[k + 1] = S.item[k] + (S.ent[k + 1] - S.ent[k] + per - 1) / per; }
-			S.n_items = S.item[6];
-			if (chain_tiles(c, order, S, (const uint32_t *)c->tie_list.p, lmin, first, lds_ok)) return -1;
-		} else {
-			if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
-			if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
-			const uint32_t tail = lds_ok ? lb129 : 0u;
-			if (chain_legacy(c, order + tail, nl - (int)tail, lds_ok, (const uint32_t *)c->tie_list.p)) return -1;
-			if (ev(ST_SEG_CHAIN_WAVE)) return -1;
-		}
-	}
-	{   // second round: the fragments whose anchors the side stream merged, any size
-		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_side[first ? 1 : 3], 0));
-		if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
-		if (c->tie_frags.ensure((size_t)nl + 2)) return -1;
-		uint32_t *cnt = (uint32_t *)(c->counters.p + 15);
-		AL_HIP_CHECK(hipMemsetAsync(cnt, 0, 8, s));
-		hipLaunchKernelGGL(k_collect_flagged, dim3((nl + 255) / 256), dim3(256), 0, s, order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, cnt);
-		uint32_t n_tie = 0, n_spec_used = 0;
-		AL_HIP_CHECK(hipMemcpyAsync(&n_tie, cnt, 4, hipMemcpyDeviceToHost, s));
-		if (!first && c->n_spec > 0) AL_HIP_CHECK(hipMemcpyAsync(&n_spec_used, c->spec_cnt.p + 2, 4, hipMemcpyDeviceToHost, s));
-		AL_HIP_CHECK(hipStreamSynchronize(s));
-		if (!first && c->n_spec > 0) c->spec_idle = n_spec_used ? 0u : c->spec_idle + 1u;
-		if (n_tie > 0) {
-			size_t bytes = 0;    // ascending fragment ids: a deterministic order (the collection above appends atomically)
-			if (c->tie_sorted.ensure((size_t)n_tie + 2)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
-			if (c->scan_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_keys(c->scan_tmp.p, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
-			if (tiles_ok) {
-				TileSched S; for (int k = 0; k < 6; ++k) { S.ent[k] = 0; S.item[k] = 0; } S.ent[6] = n_tie; S.item[6] = n_tie; S.n_items = n_tie;   // a fragment per item, any size
-				if (chain_tiles(c, c->tie_sorted.p, S, nullptr, lmin, false, lds_ok)) return -1;
-			} else if (chain_legacy(c, c->tie_sorted.p, (int)n_tie, lds_ok, nullptr)) return -1;
-		}
-		if (ev(ST_SEG_MERGE)) return -1;
-	}
+	if (chain_large(c, pl)) return -1;
+	// second round: the fragments whose anchors the side stream merged, any size
+	AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_side[first ? 1 : 3], 0));
+	if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
+	if (chain_ties(c, pl)) return -1;
 	AL_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -1452,6 +1516,51 @@ extern "C" int al_dbg_minimizers(al_ctx_t *c, int r, uint64_t *xy, int cap)
 	if (c->dev_batch) AL_HIP_CHECK(hipMemcpy(&mo, c->mini_off.p + r, 8, hipMemcpyDeviceToHost)); else mo = c->h_mini_off[r];
 	if (m > 0) AL_HIP_CHECK(hipMemcpy(xy, c->mini.p + mo, (size_t)m * 16, hipMemcpyDeviceToHost));
 	return (int)n;
+}
+
+// Tap (parity tests): the chain stage on caller-supplied anchors -- see include/airlift.h.  The batch's fragments, read lengths and longest
+// fragment are the uploaded ones; the anchors take the place of what seeding and the sorts would have left, the flags that of the sorts' tie flags.
+extern "C" int al_dbg_chain(al_ctx_t *c, const uint64_t *anchors_xy, const uint64_t *a_off, const uint32_t *tie_flag, uint32_t *nu_out, uint64_t *u_out, uint32_t *uo_out, uint64_t *chained_xy, uint64_t *counts)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_chain: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	const int nf = c->n_frag;
+	if (a_off[0] != 0) return -2;
+	for (int f = 0; f < nf; ++f) if (a_off[f + 1] < a_off[f] || a_off[f + 1] - a_off[f] > 0x7fffffffu) return -2;
+	const uint64_t total = a_off[nf];
+	AL_HIP_CHECK(hipSetDevice(c->device));
+	al_nomem_flag() = false;
+	hipStream_t s = c->stream;
+	std::vector<uint32_t> na((size_t)nf + 1, 0u);
+	for (int f = 0; f < nf; ++f) na[f] = (uint32_t)(a_off[f + 1] - a_off[f]);
+	c->n_anchor_pass1 = total; c->n_anchor_total = total; c->n_rechain = 0; c->ran = false; c->n_chain_fallback = 0;
+	if (ensure_anchor_space(c, total + 1, false) || c->frag_meta.ensure((size_t)nf + 1) || c->chain_key.ensure(nf + 1) || c->chain_idx.ensure(nf + 1) || c->chain_idx2.ensure(nf + 1) || c->tie_list.ensure((size_t)nf + 2)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), s));
+	if (total) AL_HIP_CHECK(hipMemcpyAsync(c->anchors.p, anchors_xy, (size_t)total * 16, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->a_off.p, a_off, ((size_t)nf + 1) * 8, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->frag_na.p, na.data(), ((size_t)nf + 1) * 4, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemsetAsync(c->tie_list.p, 0, ((size_t)nf + 1) * 4, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->tie_list.p, tie_flag, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipStreamSynchronize(s));                                   // (the host arrays are the caller's)
+	hipLaunchKernelGGL(k_frag_meta, dim3((nf + 255) / 256), dim3(256), 0, s, c->frag_first.p, c->rd_len.p, nf, c->frag_meta.p);
+	for (int i = 0; i < CW_N; ++i) c->chain_who[i] = 0;
+	ChainPlan pl;
+	if (chain_plan(c, nullptr, nf, true, pl)) return -1;
+	AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));                           // what the lane kernels' streams wait for: here, the anchors in place
+	if (chain_small(c, pl) || chain_large(c, pl) || chain_ties(c, pl)) return -1;
+	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) AL_HIP_CHECK(hipStreamSynchronize(c->phys[p]));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	AL_HIP_CHECK(hipGetLastError());
+	AL_HIP_CHECK(hipMemcpy(nu_out, c->frag_nu.p, (size_t)nf * 4, hipMemcpyDeviceToHost));
+	AL_HIP_CHECK(hipMemcpy(u_out, c->u.p, (size_t)(total + nf + 1) * 8, hipMemcpyDeviceToHost));
+	AL_HIP_CHECK(hipMemcpy(uo_out, c->uo.p, (size_t)(total + nf + 1) * 4, hipMemcpyDeviceToHost));
+	if (total) AL_HIP_CHECK(hipMemcpy(chained_xy, c->chained.p, (size_t)total * 16, hipMemcpyDeviceToHost));
+	if (al_env().test_guard && al_dev_guard_check()) fprintf(stderr, "[airlift] GUARD: violations after al_dbg_chain\n");
+	if (counts) {
+		for (int i = 0; i < CW_N; ++i) counts[i] = c->chain_who[i];
+		counts[CW_N] = c->n_chain_fallback; counts[CW_N + 1] = pl.lds_ok; counts[CW_N + 2] = pl.tiles_ok; counts[CW_N + 3] = pl.tile_from;
+		counts[CW_N + 4] = pl.lb1; counts[CW_N + 5] = pl.lb65; counts[CW_N + 6] = pl.lb129; counts[CW_N + 7] = (uint64_t)pl.lmin;
+	}
+	return 0;
 }
 
 extern "C" int al_dbg_anchors(al_ctx_t *c, int f, uint64_t *xy, int cap, int *rep_len)

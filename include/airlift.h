@@ -263,6 +263,20 @@ int  al_dbg_ksw(al_ctx_t *ctx, int n, const uint8_t *seqs, size_t n_seq_bytes, c
  * in al_batch_stat's dp_jobs.  Returns 0; -2: a job lies outside its read, its contig or what the stage can emit for this batch (nothing ran);
  * -3: the batch's reads are too long for the stage to run DP jobs at all. */
 int  al_dbg_ext_dp(al_ctx_t *ctx, int n, const int64_t *jobs8, int32_t *out9, uint32_t *cig_out, int cig_cap, uint64_t *shadow8);
+/* Tap (parity tests): the chain stage on caller-supplied anchors, through the code the stage runs for a batch: the fragments are keyed into
+ * size classes and ordered, the small ones go to the lane kernels, the others to the tile kernel or the segment-wise kernels as the options and
+ * the environment switches decide, the flagged ones to the second round, and whatever the kernels hand back takes the fallback and the chain-order
+ * kernels.  Needs a batch uploaded with al_batch_upload and NOT run: its fragments, read lengths and longest fragment are what the kernels derive
+ * max_dist_x / max_dist_y from (dummy reads of the wanted lengths will do).  anchors_xy: (x, y) pairs of all fragments, each fragment's in
+ * ascending x; a_off[n_frag + 1]: first anchor of every fragment; tie_flag[n_frag]: 1 = the fragment has anchors of equal x (what the sort kernels
+ * flag: chained in the second round).  Out, laid out as the context's arrays: nu_out[n_frag]; u_out / uo_out[a_off[n_frag] + n_frag + 1], the
+ * chain list of fragment f from a_off[f] + f on (u = score << 32 | anchors; uo = offset of the chain's anchors in the fragment's range);
+ * chained_xy: a_off[n_frag] anchors.  counts[24] (may be NULL): fragments the lane kernels took up to 64 anchors, of 65 ... 128, those the
+ * wavefront kernel took instead, tile items, fragments in them, fragments handed back, deferred segments, those of them chained sixteen lanes
+ * each, fragments compacted, fragments through the segment-wise kernels, segments to the wavefront kernel, fragments to the chain-order kernels,
+ * fragments chained whole after them, size of the second round, fragments under AL_TEST_SEG_BIG, fragments of the fallback's virtual batches,
+ * n_chain_fallback, lds_ok, tiles_ok, tile_from, the list positions of 1, 65 and 129 anchors, lmin.  Returns 0; -2: offsets out of order. */
+int  al_dbg_chain(al_ctx_t *ctx, const uint64_t *anchors_xy, const uint64_t *a_off, const uint32_t *tie_flag, uint32_t *nu_out, uint64_t *u_out, uint32_t *uo_out, uint64_t *chained_xy, uint64_t *counts);
 
 /* Self-test of the multi-lane output path (offset exchange + pwrite, or ordered turns) with synthetic blocks; needs no GPU. */
 int  al_dbg_ordered_out_selftest(const char *path, int n_lanes, int n_batches, int use_offsets);
