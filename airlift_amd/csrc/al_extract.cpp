@@ -26,6 +26,7 @@
 #include "al_env.h"
 #include "al_seqio.h"
 #include "al_bam.h"
+#include "al_select.h"
 #include <chrono>
 
 namespace {
@@ -175,20 +176,50 @@ extern "C" int64_t al_extract_reads_ex(const char *bam_fn, const char *bed_fn, i
 namespace {
 struct FqRec { std::string name, seq, qual; };
 // seqtk subseq FQ LIST (seqtk.c:546-620): records whose name (first word of the header) is listed, in file order
-int subseq(const char *fn, const std::unordered_set<std::string> &want, std::vector<FqRec> &out)
+// from >= 0: the reader starts at that offset of the (inflated) stream, where a record starts; *n_read: the records it walked
+int subseq(const char *fn, const std::unordered_set<std::string> &want, std::vector<FqRec> &out, long long from = -1, uint64_t *n_read = nullptr)
 {
 	AlSeqReader rd;
 	if (!rd.open(fn)) { fprintf(stderr, "ERROR: failed to open file '%s'\n", fn); return -1; }
+	if (from > 0 && !rd.seek(from)) { fprintf(stderr, "ERROR: failed to seek in file '%s'\n", fn); return -1; }
 	AlChunk c;
 	for (;;) {
 		c.text.clear(); c.recs.clear();
 		if (!rd.read(c)) break;
+		if (n_read) ++*n_read;
 		const AlRec &r = c.recs[0];
 		const char *nm = c.text.data() + r.name;
 		if (!want.count(nm)) continue;
 		FqRec q; q.name = nm; q.seq.assign(c.text.data() + r.seq, r.len); if (r.qual != ~0u) q.qual.assign(c.text.data() + r.qual, r.len);
 		out.push_back(std::move(q));
 	}
+	return 0;
+}
+// --gpu-select (al_select.h): the same records, in the same order, with the names tested by k_fq_select (or its host twin); only the selected records
+// reach the host.  From the first record that is not strict four-line FASTQ the default reader above takes the rest of the file.
+struct SelOpt { unsigned flags = 0; int device = -1; size_t piece = 0; };
+int subseq_select(const char *fn, const std::unordered_set<std::string> &want, std::vector<FqRec> &out, const SelOpt &o)
+{
+	AlSelNames N;
+	if (al_sel_build(want, N)) { fprintf(stderr, "[ERROR] airlift: --gpu-select: the list of names exceeds 4 GB\n"); return -1; }
+	uint64_t handover = ~0ull; AlSelStat st; const char *backend = ""; size_t held = 0;
+	const auto t0 = std::chrono::steady_clock::now();
+	const int r = al_select_subseq(fn, N, (o.flags & AL_EXTRACT_SELECT_HOST) != 0, (o.flags & AL_EXTRACT_GPU_INFLATE) != 0, o.device, o.piece,
+		[&](const uint8_t *arena, const AlSelDesc *d, size_t n) -> int {
+			for (size_t k = 0; k < n; ++k) {
+				const char *p = (const char *)arena + d[k].off;
+				FqRec q; q.name.assign(p, d[k].name_len); q.seq.assign(p + d[k].name_len, d[k].len); q.qual.assign(p + d[k].name_len + d[k].len, d[k].len);
+				out.push_back(std::move(q));
+			}
+			return 0;
+		}, &handover, &st, &backend, &held);
+	if (r < 0) return -1;
+	if (r == 1) return subseq(fn, want, out);
+	if (handover != ~0ull && subseq(fn, want, out, (long long)handover, &st.handed)) return -1;
+	if (al_env().timing)
+		fprintf(stderr, "[airlift] extract-sequence: --gpu-select '%s' (%s): %llu pieces, %llu bytes in, %llu records tested, %llu selected, %llu handed to the default reader; file read %.3f s, copy up %.3f s, kernels %.3f s, copy down %.3f s, wall %.3f s; device bytes held at return: %zu\n",
+		        fn, backend, (unsigned long long)st.pieces, (unsigned long long)st.bytes_in, (unsigned long long)st.tested, (unsigned long long)st.selected, (unsigned long long)st.handed, st.read_s, st.up_s, st.kernel_s, st.down_s,
+		        std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(), held);
 	return 0;
 }
 std::string pair_key(const std::string &n) { const size_t l = n.size(); return l > 2 && n[l - 2] == '/' && (n[l - 1] == '1' || n[l - 1] == '2') ? n.substr(0, l - 2) : n; }
@@ -225,10 +256,11 @@ void names_of_rows(FILE *f, std::unordered_set<std::string> &l1, std::unordered_
 	}
 }
 // seqtk subseq of both files, repair.sh pairing, rename.sh names: sink(which, records, prefix) with which = 0 reads_1, 1 reads_2, 2 singletons
-template <class Sink> int subset_pair_rename(const char *fq1, const char *fq2, const std::unordered_set<std::string> &l1, const std::unordered_set<std::string> &l2, Sink sink, int64_t *n_pairs, int64_t *n_single)
+template <class Sink> int subset_pair_rename(const char *fq1, const char *fq2, const std::unordered_set<std::string> &l1, const std::unordered_set<std::string> &l2, Sink sink, int64_t *n_pairs, int64_t *n_single, const SelOpt &so = SelOpt())
 {
 	std::vector<FqRec> s1, s2;
-	if (subseq(fq1, l1, s1) || subseq(fq2, l2, s2)) return -1;
+	const bool sel = (so.flags & (AL_EXTRACT_GPU_SELECT | AL_EXTRACT_SELECT_HOST)) != 0;
+	if (sel ? (subseq_select(fq1, l1, s1, so) || subseq_select(fq2, l2, s2, so)) : (subseq(fq1, l1, s1) || subseq(fq2, l2, s2))) return -1;
 	// repair.sh: pair by name (a trailing /1 or /2 is not part of it); the rest are singletons
 	std::unordered_map<std::string, std::vector<size_t>> k2;
 	for (size_t i = 0; i < s2.size(); ++i) k2[pair_key(s2[i].name)].push_back(i);
@@ -252,6 +284,15 @@ template <class Sink> int subset_pair_rename(const char *fq1, const char *fq2, c
 // n_pairs / n_single receive the counts.  Returns 0, negative on error.
 extern "C" int al_extract_sequence(const char *fq1, const char *fq2, const char *rows_fn, const char *out_dir, int64_t *n_pairs, int64_t *n_single)
 {
+	return al_extract_sequence_ex(fq1, fq2, rows_fn, out_dir, n_pairs, n_single, 0, -1, 1, 0);
+}
+// flags: AL_EXTRACT_GPU_SELECT -- the names of both files are tested on `device` (-1: the default device) and only the selected records come back
+// (+ AL_EXTRACT_GPU_INFLATE: BGZF FASTQ files are inflated there as well); AL_EXTRACT_SELECT_HOST -- the same driver with the host twin.  piece_bytes: the
+// file piece (0: 8 MB).  flags == 0 is al_extract_sequence.  The selector's device and page-locked buffers are released before this returns.
+extern "C" int al_extract_sequence_ex(const char *fq1, const char *fq2, const char *rows_fn, const char *out_dir, int64_t *n_pairs, int64_t *n_single, unsigned flags, int device, int n_threads, size_t piece_bytes)
+{
+	(void)n_threads;
+	SelOpt so; so.flags = flags; so.device = device; so.piece = piece_bytes;
 	std::unordered_set<std::string> l1, l2;
 	{
 		FILE *f = strcmp(rows_fn, "-") == 0 ? stdin : fopen(rows_fn, "r");
@@ -261,7 +302,7 @@ extern "C" int al_extract_sequence(const char *fq1, const char *fq2, const char 
 	}
 	const std::string d = out_dir;
 	static const char *const fn[3] = {"/reads_1.fastq", "/reads_2.fastq", "/singletons.fastq"};
-	return subset_pair_rename(fq1, fq2, l1, l2, [&](int which, const std::vector<const FqRec *> &v, const char *prefix) { return write_fq(d + fn[which], v, prefix); }, n_pairs, n_single);
+	return subset_pair_rename(fq1, fq2, l1, l2, [&](int which, const std::vector<const FqRec *> &v, const char *prefix) { return write_fq(d + fn[which], v, prefix); }, n_pairs, n_single, so);
 }
 
 // N1 fused: extract_reads.sh + extract_sequence.sh in one call, nothing written to disk -- one pass over the BAM, the
@@ -286,6 +327,7 @@ extern "C" int al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, i
 	std::unordered_set<std::string> l1, l2;
 	{ FILE *f = fmemopen(rows, rows_len ? rows_len : 1, "r"); if (!f) { free(rows); return -1; } if (rows_len) names_of_rows(f, l1, l2); fclose(f); }
 	free(rows);
+	SelOpt so; so.flags = flags; so.device = device;
 	static const char *const nm[3] = {"airlift_reads_1", "airlift_reads_2", "airlift_singletons"};
 	const int rc = subset_pair_rename(fq1, fq2, l1, l2, [&](int which, const std::vector<const FqRec *> &v, const char *prefix) -> int {
 		const int fd = memfd_create(nm[which], 0);
@@ -297,7 +339,7 @@ extern "C" int al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, i
 		if (fclose(f) == EOF || w) { close(fd); return -1; }
 		fds[which] = fd;
 		return 0;
-	}, n_pairs, n_single);
+	}, n_pairs, n_single, so);
 	if (rc) for (int i = 0; i < 3; ++i) if (fds[i] >= 0) { close(fds[i]); fds[i] = -1; }
 	return rc;
 }

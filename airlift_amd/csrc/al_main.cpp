@@ -83,7 +83,9 @@ static int usage()
 	                "BAM:   --bam | --sorted-bam [-l LEVEL] [--sort-mem BYTES]; --gpu-deflate (BGZF blocks deflated on the GPU: one compressor for every -l above 0,\n"
 	                "       -l 0 stores; one device, one process: not with --devices of several lanes, --world, --rank, --ranked)\n"
 	                "input: --gpu-inflate (BGZF-compressed FASTQ files -- bgzip, bcl-convert, DRAGEN -- stay with the GPU's input parser: their members are\n"
-	                "       inflated on the GPU; decided per file; another gzip file, '-', or --world / --rank take the host reader as without the option)\n");
+	                "       inflated on the GPU; decided per file; another gzip file, '-', or --world / --rank take the host reader as without the option)\n"
+	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
+	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
 }
 
@@ -115,9 +117,20 @@ int main(int argc, char **argv)
 		return n < 0 || fflush(stdout) == EOF ? 1 : 0;
 	}
 	if (!strcmp(argv[1], "extract-sequence")) {    // N1: airlift-align extract-sequence FQ1 FQ2 ROWS OUTDIR   (extract_sequence.sh BINDIR FQ1 FQ2 BED THREAD OUTPUT)
-		if (argc < 6) { fprintf(stderr, "Usage: airlift-align extract-sequence reads_1.fq reads_2.fq rows.bed outdir\n"); return 1; }
+		// options first: --gpu-select[=host] (the names tested on the GPU, or by the kernels' host twin), --gpu-inflate (BGZF FASTQ inflated there too), --select-piece BYTES, --device D, -t N
+		unsigned xf = 0; int dev = -1, nt = 3, j = 2; size_t piece = 0;
+		for (; j < argc; ++j) {
+			if (!strcmp(argv[j], "--gpu-select")) xf |= AL_EXTRACT_GPU_SELECT;
+			else if (!strcmp(argv[j], "--gpu-select=host")) xf |= AL_EXTRACT_GPU_SELECT | AL_EXTRACT_SELECT_HOST;
+			else if (!strcmp(argv[j], "--gpu-inflate")) xf |= AL_EXTRACT_GPU_INFLATE;
+			else if (!strcmp(argv[j], "--select-piece") && j + 1 < argc) piece = (size_t)strtoull(argv[++j], nullptr, 10);
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
+			else break;
+		}
+		if (argc - j < 4) { fprintf(stderr, "Usage: airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"); return 1; }
 		int64_t np = 0, ns = 0;
-		const int rc = al_extract_sequence(argv[2], argv[3], argv[4], argv[5], &np, &ns);
+		const int rc = xf ? al_extract_sequence_ex(argv[j], argv[j + 1], argv[j + 2], argv[j + 3], &np, &ns, xf, dev, nt, piece) : al_extract_sequence(argv[j], argv[j + 1], argv[j + 2], argv[j + 3], &np, &ns);
 		if (rc == 0) fprintf(stderr, "[airlift] extract-sequence: %lld pairs, %lld singletons\n", (long long)np, (long long)ns);
 		return rc == 0 ? 0 : 1;
 	}
@@ -129,6 +142,8 @@ int main(int argc, char **argv)
 		for (int j = 2; j < argc; ++j) {
 			if (!strcmp(argv[j], "--noprune")) prune = 0;
 			else if (!strcmp(argv[j], "--gpu-inflate")) xf |= AL_EXTRACT_GPU_INFLATE;      // READS.bam is inflated on the run's device; the reader's buffers are gone before the mapper sizes its own
+			else if (!strcmp(argv[j], "--gpu-select")) xf |= AL_EXTRACT_GPU_SELECT;        // the names of both FASTQ files are tested on the run's device; the selector's buffers are gone before the index is built
+			else if (!strcmp(argv[j], "--gpu-select=host")) xf |= AL_EXTRACT_GPU_SELECT | AL_EXTRACT_SELECT_HOST;
 			else if (!strcmp(argv[j], "--readsize") && j + 1 < argc) read_size = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-t") && j + 1 < argc) n_threads = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-R") && j + 1 < argc) rg = argv[++j];
@@ -138,7 +153,7 @@ int main(int argc, char **argv)
 			else p.push_back(argv[j]);
 		}
 		apply_out_sel(mo, sel);
-		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] [--gpu-inflate] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
+		if (p.size() != 5 || !out_p || (prune && read_size <= 0)) { fprintf(stderr, "Usage: airlift-align remap [-t N] [-R RG] [--noprune | --readsize R] [--gpu-inflate] [--gpu-select[=host]] -o pairs.sam [--singletons single.sam] ref.fa reads.bam regions.bed reads_1.fq reads_2.fq\n"); return 1; }
 		if (!al_env().pg_plain) al_set_program_line(AL_MM_VERSION, argc, argv);
 		if (!k_given) setenv("AL_AUTO_BATCH", "1", 0);
 		int fds[3]; int64_t np = 0, ns = 0;

@@ -15,8 +15,8 @@
 #include <vector>
 #include "al_internal.h"
 #include "al_runtime.h"
+#include "al_dev_select.h"             // AlFqRec: one FASTQ record, offsets into its file's text
 
-struct AlFqRec { uint32_t name, name_len, seq, len, qual; };      // one FASTQ record: offsets into its file's text
 struct AlRdText { uint32_t name, name_len, seq, qual; };          // one read (fragment-major order): offsets into the text of its file
 struct AlBulk { uint64_t dst; uint32_t src; uint32_t len_flags; }; // SEQ / QUAL field of a SAM record: copied by k_sam_bulk (len | file << 27 | u2t << 28 | comp << 29 | rev << 30); bit 31: a tag value, src = offset into the tag arena
 
@@ -64,7 +64,7 @@ struct AlStreamSlot {
 	void release();
 };
 
-int  al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_files);
+int  al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_files);   // mi == nullptr: a slot for input only (no contig names)
 void al_stream_slot_destroy(AlStreamSlot &S);
 // text of file i: begin (room for cap_bytes), then host pieces appended in file order (each call returns when its copy is done)
 int  al_stream_begin_text(AlStreamSlot &S, int i, size_t cap_bytes);
@@ -83,6 +83,11 @@ int  al_inflate_launch(hipStream_t st, int cu4, const uint8_t *d_in, const AlInf
 // line index + record parse of the loaded text; decides what the batch takes (at most max_reads reads).  eof[i]: no more bytes of file i
 // will follow (a trailing unpaired read is taken; an unterminated last line counts).  Blocks until the device has answered.
 int  al_stream_parse(AlStreamSlot &S, const bool *eof, int max_reads, AlIngestResult *res);
+// the first half of it for one file, for a caller that takes records and not fragments (al_select.hip): line index of file i's text, k_fq_parse launched on
+// the slot's stream with first_bad at S.st.p + 2 + i; *lines = the text's complete lines (S.frec[i] holds lines / 4 records once the stream has run)
+int  al_stream_index_file(AlStreamSlot &S, int i, uint64_t *lines);
+// out[0 .. n) = exclusive prefix sums of in[0 .. n), on stream s (scratch: S.scan_tmp)
+int  al_stream_scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s);
 // bytes [from, from + n) of file i's device text back to the host (the carry of the next batch)
 int  al_stream_fetch_text(AlStreamSlot &S, int i, uint64_t from, uint64_t n, char *dst);
 // fragment / read arrays of the mapping context from the parsed records [rec_lo, rec_hi) = fragments [frag_lo, frag_hi) (names hashed,

@@ -471,7 +471,7 @@ k_paf_write(SamIn I, const uint64_t *__restrict__ sam_off, char *__restrict__ sa
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
 struct CastU64s { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
-static int scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
+int al_stream_scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
 {   // out[0 .. n) = exclusive prefix sums of in[0 .. n)
 	auto it = rocprim::make_transform_iterator(in, CastU64s());
 	size_t bytes = 0;
@@ -480,6 +480,7 @@ static int scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, siz
 	AL_HIP_CHECK(rocprim::exclusive_scan(S.scan_tmp.p, bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
 	return 0;
 }
+static int scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s) { return al_stream_scan_excl_u64(S, in, out, n, s); }
 
 void AlStreamSlot::release()
 {
@@ -499,6 +500,7 @@ int al_stream_slot_init(AlStreamSlot &S, const al_idx_t *mi, int device, int n_f
 	if (S.tabs.ensure(768) || S.st.ensure(16)) return -1;
 	uint8_t h[768]; memcpy(h, al_nt4(), 256); memcpy(h + 256, al_comp(), 256); for (int i = 0; i < 256; ++i) h[512 + i] = al_bam_code16((uint8_t)i);
 	AL_HIP_CHECK(hipMemcpy(S.tabs.p, h, 768, hipMemcpyHostToDevice));
+	if (!mi) return 0;
 	std::string names; std::vector<uint32_t> off(mi->seq.size() + 1);
 	for (size_t i = 0; i < mi->seq.size(); ++i) { off[i] = (uint32_t)names.size(); names += mi->seq[i].name; }
 	off[mi->seq.size()] = (uint32_t)names.size();
@@ -606,6 +608,40 @@ int al_stream_fetch_text(AlStreamSlot &S, int i, uint64_t from, uint64_t n, char
 	return 0;
 }
 
+// the two halves of a file's line index, each launched without waiting: tile counts and their scan (*h_lines is written when the stream has run); then,
+// with the number of lines known, the line starts and k_fq_parse over the lines / 4 records (first bad record: atomicMin into S.st.p[2 + i])
+static int index_count(AlStreamSlot &S, int i, size_t tiles, size_t tile_base, unsigned long long *h_lines, hipStream_t s)
+{
+	if (tiles) hipLaunchKernelGGL(k_nl_count, dim3((unsigned)tiles), dim3(256), 0, s, S.txt[i].p, S.txt_n[i], S.tile_cnt.p + tile_base);
+	AL_HIP_CHECK(hipMemsetAsync(S.tile_cnt.p + tile_base + tiles, 0, 4, s));
+	if (scan_excl_u64(S, S.tile_cnt.p + tile_base, S.tile_off.p + tile_base, tiles + 1, s)) return -1;
+	AL_HIP_CHECK(hipMemcpyAsync(h_lines, S.tile_off.p + tile_base + tiles, 8, hipMemcpyDeviceToHost, s));
+	return 0;
+}
+static int index_fill_parse(AlStreamSlot &S, int i, size_t tiles, size_t tile_base, uint64_t lines, hipStream_t s)
+{
+	if (S.ls[i].ensure(lines + 8)) return -1;
+	if (tiles) hipLaunchKernelGGL(k_nl_fill, dim3((unsigned)tiles), dim3(256), 0, s, S.txt[i].p, S.txt_n[i], S.tile_off.p + tile_base, S.ls[i].p);
+	else AL_HIP_CHECK(hipMemsetAsync(S.ls[i].p, 0, 4, s));
+	const uint64_t nrec = lines / 4;
+	if (S.frec[i].ensure(nrec + 1)) return -1;
+	if (nrec) hipLaunchKernelGGL(k_fq_parse, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, s, S.txt[i].p, S.ls[i].p, (uint32_t)nrec, S.frec[i].p, S.st.p + 2 + i);
+	return 0;
+}
+int al_stream_index_file(AlStreamSlot &S, int i, uint64_t *lines)
+{
+	hipStream_t s = S.io;
+	AL_HIP_CHECK(hipSetDevice(S.device));
+	const size_t tiles = (S.txt_n[i] + NL_TILE - 1) / NL_TILE;
+	if (S.tile_cnt.ensure(tiles + 4) || S.tile_off.ensure(tiles + 4)) return -1;
+	unsigned long long h = 0;
+	AL_HIP_CHECK(hipMemsetAsync(S.st.p + 2 + i, 0xff, 8, s));
+	if (index_count(S, i, tiles, 0, &h, s)) return -1;
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	*lines = h;
+	return index_fill_parse(S, i, tiles, 0, h, s);
+}
+
 int al_stream_parse(AlStreamSlot &S, const bool *eof, int max_reads, AlIngestResult *res)
 {
 	hipStream_t s = S.io;
@@ -619,21 +655,13 @@ int al_stream_parse(AlStreamSlot &S, const bool *eof, int max_reads, AlIngestRes
 	for (int i = 0; i < nf; ++i) { tiles[i] = (S.txt_n[i] + NL_TILE - 1) / NL_TILE; tile_base[i] = i ? tiles[0] + 1 : 0; }
 	if (S.tile_cnt.ensure(tiles[0] + tiles[1] + 4) || S.tile_off.ensure(tiles[0] + tiles[1] + 4)) return -1;
 	for (int i = 0; i < nf; ++i) {
-		if (tiles[i]) hipLaunchKernelGGL(k_nl_count, dim3((unsigned)tiles[i]), dim3(256), 0, s, S.txt[i].p, S.txt_n[i], S.tile_cnt.p + tile_base[i]);
-		AL_HIP_CHECK(hipMemsetAsync(S.tile_cnt.p + tile_base[i] + tiles[i], 0, 4, s));
-		if (scan_excl_u64(S, S.tile_cnt.p + tile_base[i], S.tile_off.p + tile_base[i], tiles[i] + 1, s)) return -1;
-		AL_HIP_CHECK(hipMemcpyAsync(&h_st[i], S.tile_off.p + tile_base[i] + tiles[i], 8, hipMemcpyDeviceToHost, s));
+		if (index_count(S, i, tiles[i], tile_base[i], &h_st[i], s)) return -1;
 	}
 	AL_HIP_CHECK(hipStreamSynchronize(s));
 	for (int i = 0; i < nf; ++i) {
-		uint64_t lines = h_st[i];
-		if (S.ls[i].ensure(lines + 8)) return -1;
-		if (tiles[i]) hipLaunchKernelGGL(k_nl_fill, dim3((unsigned)tiles[i]), dim3(256), 0, s, S.txt[i].p, S.txt_n[i], S.tile_off.p + tile_base[i], S.ls[i].p);
-		else AL_HIP_CHECK(hipMemsetAsync(S.ls[i].p, 0, 4, s));
+		const uint64_t lines = h_st[i];
+		if (index_fill_parse(S, i, tiles[i], tile_base[i], lines, s)) return -1;
 		res->lines[i] = lines;
-		const uint64_t nrec = lines / 4;
-		if (S.frec[i].ensure(nrec + 1)) return -1;
-		if (nrec) hipLaunchKernelGGL(k_fq_parse, dim3((unsigned)((nrec + 255) / 256)), dim3(256), 0, s, S.txt[i].p, S.ls[i].p, (uint32_t)nrec, S.frec[i].p, S.st.p + 2 + i);
 	}
 	AL_HIP_CHECK(hipMemcpyAsync(h_st, S.st.p, 4 * 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));

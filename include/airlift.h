@@ -225,11 +225,21 @@ int64_t al_extract_reads_ex(const char *bam_fn, const char *bed_fn, int read_siz
  * (BBMap repair.sh) and renaming (rename.sh: realigned_<n>, realigned_singleton_<n>) into out_dir/reads_1.fastq,
  * reads_2.fastq, singletons.fastq.  Returns 0, negative on error. */
 int  al_extract_sequence(const char *fq1, const char *fq2, const char *rows_fn, const char *out_dir, int64_t *n_pairs, int64_t *n_single);
+/* The same with a choice of selector.  flags & AL_EXTRACT_GPU_SELECT (the CLI's --gpu-select): the FASTQ bytes go to `device` (-1: the default device) as
+ * they are, kernels test every record's name against the selected names and only the selected records come back; with AL_EXTRACT_GPU_INFLATE as well, a BGZF
+ * FASTQ file is inflated there.  Another gzip file, or "-", takes the default reader, with a notice.  AL_EXTRACT_SELECT_HOST: the same driver with the
+ * function evaluated on the host (tests, machines without a GPU); it is also what runs, with a notice, where the device or its memory is refused.
+ * piece_bytes: the file piece (0: 8 MB; of a BGZF file 4 x AL_INFLATE_PIECE_KB of text).  n_threads is reserved.  The output is byte for byte that of al_extract_sequence; flags == 0 is that function. */
+#define AL_EXTRACT_GPU_SELECT 2u
+#define AL_EXTRACT_SELECT_HOST 4u
+int  al_extract_sequence_ex(const char *fq1, const char *fq2, const char *rows_fn, const char *out_dir, int64_t *n_pairs, int64_t *n_single,
+                            unsigned flags, int device, int n_threads, size_t piece_bytes);
 /* N1 fused: extract_reads.sh:8 + extract_sequence.sh:17-19 in one call, nothing written to disk.  The three FASTQ texts
  * (pairs file 1, pairs file 2, singletons) are left in anonymous memory files whose descriptors go to fds[0..2]; map them by path
  * ("/proc/self/fd/<n>") with al_map_file_frag -- `airlift-align remap` does exactly that -- and close() them.  0, negative on error. */
 int  al_extract_to_memory(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single);
-/* ... with flags, device, n_threads as al_extract_reads_ex; the reader's device and page-locked buffers are released before it returns. */
+/* ... with flags, device, n_threads as al_extract_reads_ex, and AL_EXTRACT_GPU_SELECT / AL_EXTRACT_SELECT_HOST as al_extract_sequence_ex (piece: the default);
+ * the reader's and the selector's device and page-locked buffers are released before it returns. */
 int  al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, int read_size, int prune, const char *fq1, const char *fq2, int fds[3], int64_t *n_pairs, int64_t *n_single,
                              unsigned flags, int device, int n_threads);
 /* Taps of the BGZF inflater (al_dev_inflate.h, al_inflate.hip; tests).  src[0, n) is a sequence of whole BGZF members: they are listed along the BSIZE
@@ -241,6 +251,14 @@ int  al_extract_to_memory_ex(const char *bam_fn, const char *bed_fn, int read_si
 int  al_dbg_bgzf_inflate_host(const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
 int  al_dbg_bgzf_inflate(int device, const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
 int  al_dbg_bgzf_inflate_guard(int device, const void *src, size_t n, void *dst, size_t cap, size_t *out_n, uint32_t *status, size_t n_status, size_t *n_members);
+/* Test taps of --gpu-select: one text and one list of names (each followed by '\n') through ONE pass of the product's kernels (al_dbg_fq_select) or of
+ * their host twin (al_dbg_fq_select_host).  flags[0, *n_rec): 0 / 1 per parsed record (n_flags of room); *first_bad: the first record that is not regular
+ * (~0: none); arena[0, *arena_n) and desc (three words per selected record in front of first_bad: arena offset, name length, sequence length; desc_cap
+ * records of room, *n_sel used).  0; -1: the device failed; -3: an array is too small (the counts are set). */
+int  al_dbg_fq_select_host(const void *text, size_t n, const char *names, size_t names_len, uint32_t *flags, size_t n_flags, uint64_t *n_rec, uint64_t *first_bad,
+                           void *arena, size_t arena_cap, size_t *arena_n, uint32_t *desc, size_t desc_cap, size_t *n_sel);
+int  al_dbg_fq_select(int device, const void *text, size_t n, const char *names, size_t names_len, uint32_t *flags, size_t n_flags, uint64_t *n_rec, uint64_t *first_bad,
+                      void *arena, size_t arena_cap, size_t *arena_n, uint32_t *desc, size_t desc_cap, size_t *n_sel);
 
 /* Tap (parity tests): the extension DP alone -- ksw_extd2_sse's result for n caller-supplied pairs, as the reference's --print-aln-seq
  * shows them (align.c:313-339).  seqs: nt4 codes (0..4); jobs6: {target offset, query offset, tlen, qlen, ksw flag, 0} per pair (the
