@@ -152,6 +152,11 @@ def load():
         L.al_extract_sequence_ex.argtypes = [cs, cs, cs, cs, i64p, i64p, C.c_uint, ci, ci, C.c_size_t]; L.al_extract_sequence_ex.restype = ci
         L.al_dbg_fq_select_host.argtypes = [vp, C.c_size_t, vp, C.c_size_t, u32p, C.c_size_t, u64p, u64p, vp, C.c_size_t, szp, u32p, C.c_size_t, szp]; L.al_dbg_fq_select_host.restype = ci
         L.al_dbg_fq_select.argtypes = [ci, vp, C.c_size_t, vp, C.c_size_t, u32p, C.c_size_t, u64p, u64p, vp, C.c_size_t, szp, u32p, C.c_size_t, szp]; L.al_dbg_fq_select.restype = ci
+    if hasattr(L, "al_map_tokens_regions"):   # (tokens --regions-bed / --merged-bed: the merged gap regions instead of SAM, and the merge's test taps)
+        u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64)
+        L.al_map_tokens_regions.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci]; L.al_map_tokens_regions.restype = ci
+        for f in (L.al_dbg_regions_merge, L.al_dbg_regions_merge_host):
+            f.argtypes = [C.c_uint64, u32p, u32p, u32p, u32p, C.c_uint64, ci, u32p, u32p, u32p, u32p, u64p]; f.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

@@ -11,6 +11,8 @@
 //   N3     airlift-align ... --bam | --sorted-bam [-l LEVEL]       BAM on stdout; sorted = mapped records in coordinate order,
 //                                                                   i.e. the result of `| samtools view -h -F4 | samtools sort -l5`
 //   N2     airlift-align tokens --read-size R --skip S [-t N] REF.fa GAPS.fa      gaps_to_fasta.py GAPS.fa R tokens.fa S ; samse REF x tokens.fa
+//          airlift-align tokens --read-size R --skip S [--regions-bed FILE] [--merged-bed FILE] REF.fa GAPS.fa   the merged regions of that SAM instead of it
+//                                                                   (extract_regions.sh + run_pipeline.sh:62): BED per gap sequence / across all of them, merged on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -84,6 +86,10 @@ static int usage()
 	                "       -l 0 stores; one device, one process: not with --devices of several lanes, --world, --rank, --ranked)\n"
 	                "input: --gpu-inflate (BGZF-compressed FASTQ files -- bgzip, bcl-convert, DRAGEN -- stay with the GPU's input parser: their members are\n"
 	                "       inflated on the GPU; decided per file; another gzip file, '-', or --world / --rank take the host reader as without the option)\n"
+	                "tokens: airlift-align tokens --read-size R --skip S [--regions-bed FILE] [--merged-bed FILE] ref.fa gaps.fa  (without the two options: SAM of the tokens;\n"
+	                "       with either: no SAM, the intervals of the mapped records sorted and merged on the GPU as sort-bed | mergeBed do -- --regions-bed within each gap\n"
+	                "       sequence, the gaps in file order, --merged-bed across all; FILE '-' is stdout (for one of them); one device, one process, not with --paf, --bam,\n"
+	                "       --sorted-bam, --count-candidates; --MD / --cs / --eqx / -Y change nothing there)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -96,10 +102,15 @@ int main(int argc, char **argv)
 	std::vector<const char *> pos; const char *rg = nullptr; int n_threads = 3, device = -1; std::vector<int> devices; bool count_only = false; int bam_mode = 0, bam_level = 5; bool gpu_deflate = false;
 	enum { MODE_MEM, MODE_ALN, MODE_SAMSE, MODE_MM2, MODE_TOKENS } mode = MODE_MM2; int tok_size = 0, tok_skip = 1;
 	bool prefilter = false; int pf[4] = {3, 3, 5, 3};          // adjacency e, GreedySnake e, k-mer size, rounds
-	const char *dump_fn = nullptr;
+	const char *dump_fn = nullptr, *regions_fn = nullptr, *merged_fn = nullptr;
 	OutSel sel;
 	int i = 1; bool k_given = false; int rank = -1, world = 0; const char *rendezvous = nullptr, *out_path = nullptr;
 	if (argc < 2) return usage();
+	for (int j = 2; j < argc; ++j)                                      // (decided before any mode reads its arguments)
+		if ((!strcmp(argv[j], "--regions-bed") || !strcmp(argv[j], "--merged-bed")) && strcmp(argv[1], "tokens") != 0) {
+			fprintf(stderr, "[ERROR] %s writes the merged regions of a tokens run (airlift-align tokens --read-size R --skip S %s FILE ref.fa gaps.fa): it cannot be combined with another mode\n", argv[j], argv[j]);
+			return 1;
+		}
 	al_set_opt(0, &io, &mo);
 	al_set_opt("sr", &io, &mo);
 	mo.flag |= AL_F_OUT_SAM | AL_F_CIGAR;
@@ -220,6 +231,8 @@ int main(int argc, char **argv)
 		}
 		else if (!strcmp(a, "--read-size") && i + 1 < argc) tok_size = atoi(argv[++i]);
 		else if (!strcmp(a, "--skip") && i + 1 < argc) tok_skip = atoi(argv[++i]);
+		else if (!strcmp(a, "--regions-bed") && i + 1 < argc) regions_fn = argv[++i];         // tokens: the merged regions per gap sequence instead of SAM
+		else if (!strcmp(a, "--merged-bed") && i + 1 < argc) merged_fn = argv[++i];          // tokens: ... merged across all gap sequences
 		else if (!strcmp(a, "--bam")) bam_mode = 1;
 		else if (!strcmp(a, "--sorted-bam")) bam_mode = 2;
 		else if (!strcmp(a, "-l") && i + 1 < argc) bam_level = atoi(argv[++i]);
@@ -248,6 +261,12 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "-o") && i + 1 < argc) out_path = argv[++i];                   // opened below, once it is known whether this is one of several processes (which open the merged file themselves)
 		else if (!strcmp(a, "--version")) { puts(al_version()); return 0; }
 		else { fprintf(stderr, "[WARNING] airlift-align: option '%s' ignored\n", a); }
+	}
+	if (regions_fn || merged_fn) {                                      // (decided before any device is opened)
+		const bool ranked = world > 1 || rank >= 0;
+		const char *why = sel.paf ? "--paf" : bam_mode == 2 ? "--sorted-bam" : bam_mode ? "--bam" : count_only ? "--count-candidates" : devices.size() > 1 ? "--devices of more than one lane" : ranked ? "--world / --rank / --ranked" : nullptr;
+		if (why) { fprintf(stderr, "[ERROR] --regions-bed / --merged-bed write the merged regions of a tokens run from one device, in one process: they cannot be combined with %s\n", why); return 1; }
+		if (regions_fn && merged_fn && !strcmp(regions_fn, "-") && !strcmp(merged_fn, "-")) { fprintf(stderr, "[ERROR] --regions-bed and --merged-bed cannot both be written to stdout: at most one of them may be '-'\n"); return 1; }
 	}
 	if (sel.paf && (mode != MODE_MM2 || bam_mode || count_only)) {     // (decided before any device is opened)
 		fprintf(stderr, "[ERROR] --paf writes PAF text from the -x sr mapping of reads: it cannot be combined with %s\n",
@@ -298,6 +317,16 @@ int main(int argc, char **argv)
 	if (!mi) { fprintf(stderr, "[ERROR] failed to open file '%s'\n", ref); return 1; }
 	if (dump_fn && !ref_is_idx && al_idx_dump(dump_fn, mi) != 0) { al_idx_destroy(mi); return 1; }
 	if (reads.empty()) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
+	if (mode == MODE_TOKENS && (regions_fn || merged_fn)) {   // ... and the regions of the tokens' alignments instead of their SAM
+		FILE *fr = nullptr, *fm = nullptr; int rc2 = 0;
+		auto open_out = [&](const char *fn, FILE *&f) { if (!fn) return; f = strcmp(fn, "-") ? fopen(fn, "wb") : stdout; if (!f) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fn); rc2 = 1; } };
+		open_out(regions_fn, fr); open_out(merged_fn, fm);
+		if (rc2 == 0) rc2 = al_map_tokens_regions(mi, reads[0], tok_size, tok_skip, &mo, n_threads, fr, fm, device);
+		al_idx_destroy(mi);
+		for (FILE *f : {fr, fm}) if (f && (f == stdout ? fflush(f) : fclose(f)) == EOF) rc2 = 1;
+		fflush(stderr);
+		_exit(rc2 == 0 ? 0 : 1);
+	}
 	if (mode == MODE_TOKENS) {   // gaps_to_fasta.py + single-end alignment of the tokens in one step (tokens are cut on the GPU)
 		const int rc2 = al_map_tokens_file(mi, reads[0], tok_size, tok_skip, &mo, n_threads, stdout, rg, device);
 		al_idx_destroy(mi);

@@ -353,6 +353,22 @@ int  al_batch_upload_windows(al_ctx_t *ctx, const al_winsrc_t *src, int n_tok, c
  * bases, named <sequence>_<start>) followed by the single-end alignment of the tokens (align_gaps.sh:14-15); SAM on `out`. */
 int  al_map_tokens_file(const al_idx_t *mi, const char *gaps_fn, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
                         FILE *out, const char *rg, int device);
+/* The same stage with the only thing AirLift reads from that SAM as its output (extract_regions.sh, run_pipeline.sh:62): the intervals
+ * [POS - 1, POS - 1 + reference span) of every mapped record the SAM run would print, sorted as sort-bed sorts (contig name in byte order,
+ * start, end) and merged as mergeBed merges (distance 0) -- on `regions` within each gap sequence of `gaps_fn`, the gaps one after the
+ * other in file order; on `merged` across all of them.  BED lines "contig\tstart\tend\n".  Either FILE may be NULL, not both.  The
+ * records stay on the device: the intervals are collected, sorted and merged there, no SAM text is made.  The tag and =/X options in
+ * `opt` have no effect.  Return codes as al_map_tokens_file. */
+int  al_map_tokens_regions(const al_idx_t *mi, const char *gaps_fn, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
+                           FILE *regions, FILE *merged, int device);
+/* Test taps of the region merge: n caller-given intervals {group, rank (of the contig's name), start, end} through the device list and
+ * its folds (al_dbg_regions_merge, on the current device) or through their host twin (al_dbg_regions_merge_host).  chunk > 0: the
+ * intervals are appended `chunk` at a time with a fold after each append (the fold between batches); 0: all at once.  per_gap != 0: the
+ * regions of every (group, rank); 0: merged across the groups (every group 0).  The o_* arrays have room for n; *n_out regions. */
+int  al_dbg_regions_merge(uint64_t n, const uint32_t *group, const uint32_t *rank, const uint32_t *start, const uint32_t *end, uint64_t chunk, int per_gap,
+                          uint32_t *o_group, uint32_t *o_rank, uint32_t *o_start, uint32_t *o_end, uint64_t *n_out);
+int  al_dbg_regions_merge_host(uint64_t n, const uint32_t *group, const uint32_t *rank, const uint32_t *start, const uint32_t *end, uint64_t chunk, int per_gap,
+                               uint32_t *o_group, uint32_t *o_rank, uint32_t *o_start, uint32_t *o_end, uint64_t *n_out);
 
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
