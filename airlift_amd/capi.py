@@ -121,6 +121,9 @@ def load():
     L.al_map_file_frag.argtypes = [vp, ci, C.POINTER(cs), C.POINTER(MapOpt), ci, vp, cs, ci]; L.al_map_file_frag.restype = ci
     L.al_map_file_frag_bam.argtypes = [vp, ci, C.POINTER(cs), C.POINTER(MapOpt), ci, vp, cs, ci, ci, ci]; L.al_map_file_frag_bam.restype = ci
     L.al_map_tokens_file.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, cs, ci]; L.al_map_tokens_file.restype = ci
+    L.al_device_reserve.argtypes = [ci, C.c_uint64]; L.al_device_reserve.restype = ci
+    L.al_device_reserve_peak.argtypes = []; L.al_device_reserve_peak.restype = C.c_uint64
+    L.al_device_reserve_report.argtypes = [vp]; L.al_device_reserve_report.restype = None   # (a FILE *)
     L.al_winsrc_create.argtypes = [vp, cs, C.c_uint64]; L.al_winsrc_create.restype = vp
     L.al_winsrc_destroy.argtypes = [vp]; L.al_winsrc_destroy.restype = None
     L.al_batch_upload_windows.argtypes = [vp, vp, ci, C.POINTER(C.c_uint64), ci, C.POINTER(cs)]; L.al_batch_upload_windows.restype = ci

@@ -642,7 +642,7 @@ int al_stream_map_files(const al_idx_t *mi, int n_fn, const char **fn, const al_
 					int64_t first = (int64_t)probe_mult * probe_reads;
 					if (long_input && !env.probe_mult) {   // at least three batches per context, at most 2^20 reads, within 60 % of the free memory at ~80 KB per read
 						size_t free_b = 0, total_b = 0;
-						double b = std::min(al_long_batch_cap(est0 * (double)NL), std::max(262144.0, est0 / (3.0 * n_ctx_lane)));   // (524 288 reads; 2^20 for very long inputs: al_runtime.hip)
+						double b = std::min(al_long_batch_cap(est0 * (double)NL), std::max(262144.0, est0 / (3.0 * n_ctx_lane)));   // (524 288 reads; 2^20 for very long inputs: al_devmem.cpp)
 						if (hipSetDevice(mappers[0]->device) == hipSuccess && al_dev_mem_info(&free_b, &total_b) == hipSuccess) b = std::min(b, 0.6 * (double)free_b / ((double)n_ctx_lane * (al_map_only(opt->flag) ? 65536.0 : 81920.0)));   // (a map-only run has no extension stage: ~17 KB per read less, measured 13.2 against 30.9 KB on a small reference)
 						first = std::max<int64_t>(first, (int64_t)b);
 					}
