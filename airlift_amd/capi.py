@@ -160,6 +160,12 @@ def load():
         L.al_map_tokens_regions.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci]; L.al_map_tokens_regions.restype = ci
         for f in (L.al_dbg_regions_merge, L.al_dbg_regions_merge_host):
             f.argtypes = [C.c_uint64, u32p, u32p, u32p, u32p, C.c_uint64, ci, u32p, u32p, u32p, u32p, u64p]; f.restype = ci
+    if hasattr(L, "al_map_tokens_bed_file"):   # (tokens --gaps-bed: the tokens cut from the indexed reference by the rows of a gaps BED, and the set-up kernel's test taps)
+        u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64)
+        L.al_map_tokens_bed_file.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, cs, ci]; L.al_map_tokens_bed_file.restype = ci
+        L.al_map_tokens_bed_regions.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci]; L.al_map_tokens_bed_regions.restype = ci
+        for f in (L.al_dbg_tokens_table, L.al_dbg_tokens_table_host):
+            f.argtypes = [C.c_uint32, C.c_char_p, C.c_size_t, u64p, u32p, ci, ci, ci, C.c_uint64, C.c_uint64, u64p, u32p, u64p, u32p]; f.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

@@ -13,6 +13,8 @@
 //   N2     airlift-align tokens --read-size R --skip S [-t N] REF.fa GAPS.fa      gaps_to_fasta.py GAPS.fa R tokens.fa S ; samse REF x tokens.fa
 //          airlift-align tokens --read-size R --skip S [--regions-bed FILE] [--merged-bed FILE] REF.fa GAPS.fa   the merged regions of that SAM instead of it
 //                                                                   (extract_regions.sh + run_pipeline.sh:62): BED per gap sequence / across all of them, merged on the GPU
+//          airlift-align tokens --read-size R --skip S --gaps-bed GAPS.bed [--regions-bed FILE] [--merged-bed FILE] REF.fa   the gap sequences are the BED's rows of
+//                                                                   REF.fa itself (extract_fasta_regions_with_bedfile.sh): no GAPS.fa, the tokens are cut from the index on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -90,6 +92,10 @@ static int usage()
 	                "       with either: no SAM, the intervals of the mapped records sorted and merged on the GPU as sort-bed | mergeBed do -- --regions-bed within each gap\n"
 	                "       sequence, the gaps in file order, --merged-bed across all; FILE '-' is stdout (for one of them); one device, one process, not with --paf, --bam,\n"
 	                "       --sorted-bam, --count-candidates; --MD / --cs / --eqx / -Y change nothing there)\n"
+	                "       airlift-align tokens --read-size R --skip S --gaps-bed FILE [--regions-bed FILE] [--merged-bed FILE] ref.fa  (no gaps.fa: a row 'name a b' of the\n"
+	                "       gaps BED is the sequence `samtools faidx ref.fa name:a-b` prints, named name:a-b -- the bases [max(a,1)-1, min(b, contig length)) -- and its tokens\n"
+	                "       are cut from the indexed reference on the GPU; SEQ of the SAM is therefore upper-case ACGTN where the FASTA run prints the file's own letters,\n"
+	                "       every other column and both BED files are the same; the group of --regions-bed is the BED row; refused like the two options above)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -102,13 +108,18 @@ int main(int argc, char **argv)
 	std::vector<const char *> pos; const char *rg = nullptr; int n_threads = 3, device = -1; std::vector<int> devices; bool count_only = false; int bam_mode = 0, bam_level = 5; bool gpu_deflate = false;
 	enum { MODE_MEM, MODE_ALN, MODE_SAMSE, MODE_MM2, MODE_TOKENS } mode = MODE_MM2; int tok_size = 0, tok_skip = 1;
 	bool prefilter = false; int pf[4] = {3, 3, 5, 3};          // adjacency e, GreedySnake e, k-mer size, rounds
-	const char *dump_fn = nullptr, *regions_fn = nullptr, *merged_fn = nullptr;
+	const char *dump_fn = nullptr, *regions_fn = nullptr, *merged_fn = nullptr, *gaps_bed_fn = nullptr;
 	OutSel sel;
 	int i = 1; bool k_given = false; int rank = -1, world = 0; const char *rendezvous = nullptr, *out_path = nullptr;
 	if (argc < 2) return usage();
 	for (int j = 2; j < argc; ++j)                                      // (decided before any mode reads its arguments)
 		if ((!strcmp(argv[j], "--regions-bed") || !strcmp(argv[j], "--merged-bed")) && strcmp(argv[1], "tokens") != 0) {
 			fprintf(stderr, "[ERROR] %s writes the merged regions of a tokens run (airlift-align tokens --read-size R --skip S %s FILE ref.fa gaps.fa): it cannot be combined with another mode\n", argv[j], argv[j]);
+			return 1;
+		}
+	for (int j = 2; j < argc; ++j)
+		if (!strcmp(argv[j], "--gaps-bed") && strcmp(argv[1], "tokens") != 0) {
+			fprintf(stderr, "[ERROR] --gaps-bed names the gap regions of a tokens run (airlift-align tokens --read-size R --skip S --gaps-bed GAPS.bed ref.fa): it cannot be combined with another mode\n");
 			return 1;
 		}
 	al_set_opt(0, &io, &mo);
@@ -233,6 +244,7 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--skip") && i + 1 < argc) tok_skip = atoi(argv[++i]);
 		else if (!strcmp(a, "--regions-bed") && i + 1 < argc) regions_fn = argv[++i];         // tokens: the merged regions per gap sequence instead of SAM
 		else if (!strcmp(a, "--merged-bed") && i + 1 < argc) merged_fn = argv[++i];          // tokens: ... merged across all gap sequences
+		else if (!strcmp(a, "--gaps-bed") && i + 1 < argc) gaps_bed_fn = argv[++i];            // tokens: the gap sequences are these regions of the reference itself
 		else if (!strcmp(a, "--bam")) bam_mode = 1;
 		else if (!strcmp(a, "--sorted-bam")) bam_mode = 2;
 		else if (!strcmp(a, "-l") && i + 1 < argc) bam_level = atoi(argv[++i]);
@@ -261,6 +273,12 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "-o") && i + 1 < argc) out_path = argv[++i];                   // opened below, once it is known whether this is one of several processes (which open the merged file themselves)
 		else if (!strcmp(a, "--version")) { puts(al_version()); return 0; }
 		else { fprintf(stderr, "[WARNING] airlift-align: option '%s' ignored\n", a); }
+	}
+	if (gaps_bed_fn) {                                                  // (decided before the reference is read or a device opened)
+		const bool ranked = world > 1 || rank >= 0;
+		const char *why = sel.paf ? "--paf" : bam_mode == 2 ? "--sorted-bam" : bam_mode ? "--bam" : count_only ? "--count-candidates" : devices.size() > 1 ? "--devices of more than one lane" : ranked ? "--world / --rank / --ranked" : nullptr;
+		if (why) { fprintf(stderr, "[ERROR] --gaps-bed cuts the tokens of a tokens run from the indexed reference on one device, in one process, for SAM or the merged regions: it cannot be combined with %s\n", why); return 1; }
+		if (pos.size() > 1) { fprintf(stderr, "[ERROR] --gaps-bed takes the place of the gap FASTA: give the reference alone (airlift-align tokens --read-size R --skip S --gaps-bed GAPS.bed ref.fa), not '%s' as well\n", pos[1]); return 1; }
 	}
 	if (regions_fn || merged_fn) {                                      // (decided before any device is opened)
 		const bool ranked = world > 1 || rank >= 0;
@@ -298,6 +316,9 @@ int main(int argc, char **argv)
 	} else if (mode == MODE_SAMSE) {
 		if (pos.size() < 3) return usage();
 		ref = pos[0]; reads.push_back(pos[2]);
+	} else if (gaps_bed_fn) {        // tokens --gaps-bed: the reference alone
+		if (pos.size() != 1) return usage();
+		ref = pos[0];
 	} else {
 		if ((pos.size() < 2 && !(dump_fn && pos.size() == 1)) || pos.size() > 3) return usage();   // (-d FILE ref.fa: index only, main.c:374-376)
 		ref = pos[0]; for (size_t j = 1; j < pos.size(); ++j) reads.push_back(pos[j]);
@@ -316,19 +337,21 @@ int main(int argc, char **argv)
 	if (al_env().timing) fprintf(stderr, "[airlift] index build %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
 	if (!mi) { fprintf(stderr, "[ERROR] failed to open file '%s'\n", ref); return 1; }
 	if (dump_fn && !ref_is_idx && al_idx_dump(dump_fn, mi) != 0) { al_idx_destroy(mi); return 1; }
-	if (reads.empty()) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
+	if (reads.empty() && !gaps_bed_fn) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
 	if (mode == MODE_TOKENS && (regions_fn || merged_fn)) {   // ... and the regions of the tokens' alignments instead of their SAM
 		FILE *fr = nullptr, *fm = nullptr; int rc2 = 0;
 		auto open_out = [&](const char *fn, FILE *&f) { if (!fn) return; f = strcmp(fn, "-") ? fopen(fn, "wb") : stdout; if (!f) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fn); rc2 = 1; } };
 		open_out(regions_fn, fr); open_out(merged_fn, fm);
-		if (rc2 == 0) rc2 = al_map_tokens_regions(mi, reads[0], tok_size, tok_skip, &mo, n_threads, fr, fm, device);
+		if (rc2 == 0) rc2 = gaps_bed_fn ? al_map_tokens_bed_regions(mi, gaps_bed_fn, tok_size, tok_skip, &mo, n_threads, fr, fm, device)
+		                                : al_map_tokens_regions(mi, reads[0], tok_size, tok_skip, &mo, n_threads, fr, fm, device);
 		al_idx_destroy(mi);
 		for (FILE *f : {fr, fm}) if (f && (f == stdout ? fflush(f) : fclose(f)) == EOF) rc2 = 1;
 		fflush(stderr);
 		_exit(rc2 == 0 ? 0 : 1);
 	}
 	if (mode == MODE_TOKENS) {   // gaps_to_fasta.py + single-end alignment of the tokens in one step (tokens are cut on the GPU)
-		const int rc2 = al_map_tokens_file(mi, reads[0], tok_size, tok_skip, &mo, n_threads, stdout, rg, device);
+		const int rc2 = gaps_bed_fn ? al_map_tokens_bed_file(mi, gaps_bed_fn, tok_size, tok_skip, &mo, n_threads, stdout, rg, device)
+		                            : al_map_tokens_file(mi, reads[0], tok_size, tok_skip, &mo, n_threads, stdout, rg, device);
 		al_idx_destroy(mi);
 		if (fflush(stdout) == EOF) return 1;
 		fflush(stderr);

@@ -125,6 +125,17 @@ struct al_ctx_s {
 };
 
 int al_upload_index(const al_idx_t *mi, int device, AlDevIndex *out);
+// token batches (al_runtime.hip): the counts and buffers of a batch of n_tok windows of read_len bases; the windows cut from S4 at the starts in tmp_u64b
+int al_windows_prepare(al_ctx_t *c, int n_tok, int read_len);
+int al_windows_cut(al_ctx_t *c, const uint32_t *S4, int n_tok, int read_len);
+// tokens --gaps-bed (al_tokens.hip): the region table on the device, and tokens [t0, t0 + n_tok) of it as the resident batch -- set up by k_tok_setup, cut from
+// the index's own S4.  host_mirrors: the two host arrays al_fetch_raw reads (the SAM sink) are filled.
+struct AlTokDev;
+AlTokDev *al_tokdev_open(int device, const uint64_t *first_tok, const uint64_t *src, const uint32_t *h_prefix, uint32_t n_rows);
+void al_tokdev_close(AlTokDev *T);
+int al_batch_upload_tokens(al_ctx_t *c, const AlTokDev *T, uint64_t t0, int n_tok, int read_len, int skip, bool host_mirrors);
+float al_tokdev_ms(const AlTokDev *T);     // k_tok_setup's device time so far (HIP events)
+int al_tokdev_fetch_s4(al_ctx_t *c, std::vector<uint32_t> &S4);   // the index's packed reference, device -> host (a device-built index has no host copy)
 void al_ctx_no_taps(al_ctx_t *c);         // see al_ctx_s::no_taps
 int al_run_align_stage(al_ctx_t *c);      // al_kernels_align.hip: KA (regs) + K5 (extension, MAPQ, pairing)
 // MD:Z / cs:Z tags of a batch's compacted records (--MD / --cs, al_kernels_tags.hip): value bytes of output record k at arena[off[k] .. off[k + 1])

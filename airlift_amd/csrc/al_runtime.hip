@@ -1438,13 +1438,39 @@ k_make_windows(const uint32_t *__restrict__ S4, const uint64_t *__restrict__ sta
 	rd_seq[(uint64_t)j * wpr + w] = v;
 }
 
+// What every token batch does before its reads exist: the batch's counts, the limit of the GPU path, the buffers al_batch_run expects (tmp_u64b: the window starts).
+int al_windows_prepare(al_ctx_t *c, int n_tok, int read_len)
+{
+	const int k = c->mi->k, wpr = (read_len + 7) / 8 + 1;
+	c->n_frag = n_tok; c->n_reads = n_tok; c->ran = false; c->max_qlen_sum = read_len; c->max_rd_len = n_tok ? read_len : 0; c->dev_batch = false;
+	if (read_len >= AL_MAX_READ_LEN) { fprintf(stderr, "[airlift] tokens of %d bases exceed the limit of the GPU path\n", read_len); return -3; }
+	const uint64_t mper = (uint64_t)(read_len >= k ? read_len - k + 1 : 0) + 1;
+	const uint64_t words = (uint64_t)n_tok * wpr, mtot = (uint64_t)n_tok * mper, bases = (uint64_t)n_tok * read_len;
+	c->n_bases = bases; c->mini_total = mtot; c->seq_words = words;
+	c->stat_bytes_in = (uint64_t)n_tok * (((uint64_t)read_len * 3 + 7) / 8);
+	const int n_frag = n_tok, n_reads = n_tok;
+	if (c->rd_seq.ensure(words + 1) || c->rd_off.ensure(n_reads + 1) || c->rd_len.ensure(n_reads + 1) || c->frag_first.ensure(n_frag + 1) || c->frag_hash.ensure(n_frag + 1) ||
+	    c->mini_off.ensure(n_reads + 1) || c->mini.ensure(mtot + 1) || c->mini_cnt.ensure(n_reads + 1) || c->match.ensure(mtot + 1) || c->heap_ws.ensure(mtot + 1) ||
+	    c->frag_nm.ensure(n_frag + 1) || c->frag_na.ensure(n_frag + 1) || c->frag_rep.ensure(n_frag + 1) || c->frag_nu.ensure(n_frag + 1) || c->a_off.ensure(n_frag + 2) ||
+	    c->rechain_list.ensure(n_frag + 1) || c->tmp_u32.ensure(n_frag + 2) || c->tmp_u64.ensure(n_frag + 2) || c->counters.ensure(32) || c->tmp_u64b.ensure(n_tok + 1)) return -1;
+	return 0;
+}
+// the reads of the prepared batch cut from S4 at the starts in tmp_u64b (queued on the context's stream)
+int al_windows_cut(al_ctx_t *c, const uint32_t *S4, int n_tok, int read_len)
+{
+	const int wpr = (read_len + 7) / 8 + 1; const uint64_t words = (uint64_t)n_tok * wpr;
+	if (words) hipLaunchKernelGGL(k_make_windows, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, c->stream, S4, c->tmp_u64b.p, n_tok, read_len, wpr, c->rd_seq.p);
+	AL_HIP_CHECK(hipMemsetAsync(c->rd_seq.p + words, 0, 4, c->stream));
+	return 0;
+}
+
 extern "C" int al_batch_upload_windows(al_ctx_t *c, const al_winsrc_t *src, int n_tok, const uint64_t *start, int read_len, const char *const *qnames)
 {
 	if (!c || !src || n_tok < 0 || read_len <= 0 || src->device != c->device) return -1;
 	AL_HIP_CHECK(hipSetDevice(c->device));
 	const int k = c->mi->k, wpr = (read_len + 7) / 8 + 1;
-	c->n_frag = n_tok; c->n_reads = n_tok; c->ran = false; c->max_qlen_sum = read_len; c->max_rd_len = n_tok ? read_len : 0; c->dev_batch = false;
-	if (read_len >= AL_MAX_READ_LEN) { fprintf(stderr, "[airlift] tokens of %d bases exceed the limit of the GPU path\n", read_len); return -3; }
+	int rc = al_windows_prepare(c, n_tok, read_len);
+	if (rc == -3) return rc;
 	c->h_rd_len.assign(n_tok + 1, (uint32_t)read_len); c->h_rd_len[n_tok] = 0;
 	c->h_rd_off.resize(n_tok + 1); c->h_mini_off.resize(n_tok + 1); c->h_flip.assign(n_tok, 0);
 	c->h_frag_first.resize(n_tok + 1); c->h_frag_hash.resize(n_tok + 1);
@@ -1454,17 +1480,10 @@ extern "C" int al_batch_upload_windows(al_ctx_t *c, const al_winsrc_t *src, int 
 		for (size_t i = lo; i < hi; ++i) c->h_frag_hash[i] = qname_hash(qnames ? qnames[i] : nullptr, read_len, c->opt.seed);
 	});
 	for (int i = 0; i < n_tok; ++i) if (start[i] + (uint64_t)read_len > src->n_bases) { fprintf(stderr, "[airlift] al_batch_upload_windows: window %d leaves the source\n", i); return -2; }
-	const uint64_t words = (uint64_t)n_tok * wpr, mtot = (uint64_t)n_tok * mper, bases = (uint64_t)n_tok * read_len;
-	c->n_bases = bases; c->mini_total = mtot; c->seq_words = words;
-	c->stat_bytes_in = (uint64_t)n_tok * (((uint64_t)read_len * 3 + 7) / 8);
+	if (rc) return rc;
 	hipStream_t s = c->stream; const int n_frag = n_tok, n_reads = n_tok;
-	if (c->rd_seq.ensure(words + 1) || c->rd_off.ensure(n_reads + 1) || c->rd_len.ensure(n_reads + 1) || c->frag_first.ensure(n_frag + 1) || c->frag_hash.ensure(n_frag + 1) ||
-	    c->mini_off.ensure(n_reads + 1) || c->mini.ensure(mtot + 1) || c->mini_cnt.ensure(n_reads + 1) || c->match.ensure(mtot + 1) || c->heap_ws.ensure(mtot + 1) ||
-	    c->frag_nm.ensure(n_frag + 1) || c->frag_na.ensure(n_frag + 1) || c->frag_rep.ensure(n_frag + 1) || c->frag_nu.ensure(n_frag + 1) || c->a_off.ensure(n_frag + 2) ||
-	    c->rechain_list.ensure(n_frag + 1) || c->tmp_u32.ensure(n_frag + 2) || c->tmp_u64.ensure(n_frag + 2) || c->counters.ensure(32) || c->tmp_u64b.ensure(n_tok + 1)) return -1;
 	AL_HIP_CHECK(hipMemcpyAsync(c->tmp_u64b.p, start, (size_t)n_tok * 8, hipMemcpyHostToDevice, s));
-	if (words) hipLaunchKernelGGL(k_make_windows, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, s, src->S4, c->tmp_u64b.p, n_tok, read_len, wpr, c->rd_seq.p);
-	AL_HIP_CHECK(hipMemsetAsync(c->rd_seq.p + words, 0, 4, s));
+	if ((rc = al_windows_cut(c, src->S4, n_tok, read_len)) != 0) return rc;
 	AL_HIP_CHECK(hipMemcpyAsync(c->rd_off.p, c->h_rd_off.data(), (size_t)(n_reads + 1) * 8, hipMemcpyHostToDevice, s));
 	AL_HIP_CHECK(hipMemcpyAsync(c->rd_len.p, c->h_rd_len.data(), (size_t)(n_reads + 1) * 4, hipMemcpyHostToDevice, s));
 	AL_HIP_CHECK(hipMemcpyAsync(c->frag_first.p, c->h_frag_first.data(), (size_t)(n_frag + 1) * 4, hipMemcpyHostToDevice, s));

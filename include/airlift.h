@@ -369,6 +369,24 @@ int  al_dbg_regions_merge(uint64_t n, const uint32_t *group, const uint32_t *ran
                           uint32_t *o_group, uint32_t *o_rank, uint32_t *o_start, uint32_t *o_end, uint64_t *n_out);
 int  al_dbg_regions_merge_host(uint64_t n, const uint32_t *group, const uint32_t *rank, const uint32_t *start, const uint32_t *end, uint64_t chunk, int per_gap,
                                uint32_t *o_group, uint32_t *o_rank, uint32_t *o_start, uint32_t *o_end, uint64_t *n_out);
+/* The two stages above with the gaps BED in place of the gap FASTA: a row "name \t a \t b" of `bed_fn` (further columns ignored, empty lines skipped)
+ * stands for what `samtools faidx REF name:a-b` prints for the indexed reference -- the header "name:a-b" from the literal text of the fields, the bases
+ * [max(a, 1) - 1, min(b, contig length)) of contig `name` -- and is tiled as a sequence of GAPS.fa is.  The tokens are set up and cut on the device from
+ * the index's own 4-bit reference, so SEQ of the SAM is upper-case ACGTN; every other column, and both BED outputs (group = BED row), are those of the
+ * FASTA run over the equivalent GAPS.fa.  A row with fewer than three fields, a non-numeric a or b, b < a or a contig the index does not have is refused
+ * with its file and line number (-1), before any device is opened.  Return codes otherwise as al_map_tokens_file / al_map_tokens_regions. */
+int  al_map_tokens_bed_file(const al_idx_t *mi, const char *bed_fn, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
+                            FILE *out, const char *rg, int device);
+int  al_map_tokens_bed_regions(const al_idx_t *mi, const char *bed_fn, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
+                               FILE *regions, FILE *merged, int device);
+/* Test taps of the token set-up: n_rows regions given by their names ("name:a-b", NUL-terminated, one after the other in names[0, names_len)), first
+ * bases src[] and lengths len[]; tokens [t0, t0 + n) of their table through k_tok_setup on the current device (al_dbg_tokens_table) or through its host
+ * twin (al_dbg_tokens_table_host): o_start[i] the first base of token t0 + i's window, o_hash[i] its fragment hash.  o_first_tok (n_rows + 1) and
+ * o_h_prefix (n_rows) receive the table when they are not NULL.  No index, no mapping.  -1: arguments, or tokens beyond the table. */
+int  al_dbg_tokens_table(uint32_t n_rows, const char *names, size_t names_len, const uint64_t *src, const uint32_t *len, int read_size, int skip, int seed,
+                         uint64_t t0, uint64_t n, uint64_t *o_start, uint32_t *o_hash, uint64_t *o_first_tok, uint32_t *o_h_prefix);
+int  al_dbg_tokens_table_host(uint32_t n_rows, const char *names, size_t names_len, const uint64_t *src, const uint32_t *len, int read_size, int skip, int seed,
+                              uint64_t t0, uint64_t n, uint64_t *o_start, uint32_t *o_hash, uint64_t *o_first_tok, uint32_t *o_h_prefix);
 
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
