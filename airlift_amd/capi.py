@@ -166,6 +166,13 @@ def load():
         L.al_map_tokens_bed_regions.argtypes = [vp, cs, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci]; L.al_map_tokens_bed_regions.restype = ci
         for f in (L.al_dbg_tokens_table, L.al_dbg_tokens_table_host):
             f.argtypes = [C.c_uint32, C.c_char_p, C.c_size_t, u64p, u32p, ci, ci, ci, C.c_uint64, C.c_uint64, u64p, u32p, u64p, u32p]; f.restype = ci
+    if hasattr(L, "al_chain_beds"):   # (chain-beds / tokens --chain: the chain file's region logic, and its test taps)
+        u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64); u32 = C.c_uint32
+        L.al_chain_beds.argtypes = [cs, ci, ci, cs, vp, vp, vp, C.c_uint, ci]; L.al_chain_beds.restype = ci
+        L.al_map_tokens_chain_file.argtypes = [vp, cs, ci, ci, ci, C.POINTER(MapOpt), ci, vp, cs, ci, vp]; L.al_map_tokens_chain_file.restype = ci
+        L.al_map_tokens_chain_regions.argtypes = [vp, cs, ci, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci, vp, vp, vp]; L.al_map_tokens_chain_regions.restype = ci
+        for f in (L.al_dbg_chainreg, L.al_dbg_chainreg_host):
+            f.argtypes = [C.c_uint64, u32p, u32p, u32p, u32p, u32, u32p, u32p, u32, u32p, C.c_uint64, u32p, u32p, u32p, u32, u32p, u32p, ci, ci, u32p, u64p, u32p, u64p, u32p, u64p]; f.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

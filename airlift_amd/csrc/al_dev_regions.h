@@ -117,6 +117,8 @@ int  al_regions_take(AlRegions *R, al_ctx_s *c, uint32_t tok0);
 int  al_regions_append(AlRegions *R, const AlRegIv *iv, uint64_t n, bool fold);     // (the tap) caller-given intervals
 // the last fold; per_gap / merged (either may be null) receive the regions
 int  al_regions_finish(AlRegions *R, std::vector<AlRegIv> *per_gap, std::vector<AlRegIv> *merged);
+// after al_regions_finish with `merged`: where the merged regions {0, rank, start, end} lie on the device (tokens --chain reads them there), and the device
+void al_regions_device_list(const AlRegions *R, const AlRegIv **list, uint64_t *n, int *device);
 struct AlRegionsStat { double ms_intervals, ms_fold; uint64_t n_raw, n_fold, bytes_h2d, bytes_d2h; };
 void al_regions_stat(const AlRegions *R, AlRegionsStat *st);
 void al_regions_close(AlRegions *R);

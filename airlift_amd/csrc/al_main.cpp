@@ -15,6 +15,11 @@
 //                                                                   (extract_regions.sh + run_pipeline.sh:62): BED per gap sequence / across all of them, merged on the GPU
 //          airlift-align tokens --read-size R --skip S --gaps-bed GAPS.bed [--regions-bed FILE] [--merged-bed FILE] REF.fa   the gap sequences are the BED's rows of
 //                                                                   REF.fa itself (extract_fasta_regions_with_bedfile.sh): no GAPS.fa, the tokens are cut from the index on the GPU
+//          airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E [--gaps-out FILE] [--regions-bed F] [--merged-bed F] [--retired-bed F] [--constant-bed F] REF.fa
+//                                                                   the gaps BED is made from the chain file on the GPU (2_get_updated_regions_bed.py, run_pipeline.sh:32), and the
+//                                                                   retired / constant regions come from the same process (get_retired_regions.py :68, get_constant_regions.py :79)
+//          airlift-align chain-beds --read-size R [--max-errors E] [--gaps-out FILE] [--constant-bed FILE] [--merged-in MERGED.bed --retired-bed FILE] [--host] [--device D] CHAIN
+//                                                                   the three scripts alone, file for file
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -96,6 +101,14 @@ static int usage()
 	                "       gaps BED is the sequence `samtools faidx ref.fa name:a-b` prints, named name:a-b -- the bases [max(a,1)-1, min(b, contig length)) -- and its tokens\n"
 	                "       are cut from the indexed reference on the GPU; SEQ of the SAM is therefore upper-case ACGTN where the FASTA run prints the file's own letters,\n"
 	                "       every other column and both BED files are the same; the group of --regions-bed is the BED row; refused like the two options above)\n"
+	                "       airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E [--gaps-out FILE] [--regions-bed FILE] [--merged-bed FILE] [--retired-bed FILE]\n"
+	                "       [--constant-bed FILE] ref.fa  (no gaps BED either: the rows 2_get_updated_regions_bed.py CHAIN R E writes -- the gaps between the chain file's blocks padded\n"
+	                "       by R + E, clamped to tSize and merged -- are computed on the GPU and tiled as --gaps-bed tiles them; --gaps-out writes them; --retired-bed: what\n"
+	                "       get_retired_regions.py R MERGED CHAIN makes of the run's merged regions, taken where they lie on the GPU; --constant-bed: get_constant_regions.py's rows;\n"
+	                "       --retired-bed / --constant-bed put the run in regions mode like --merged-bed: no SAM; refused like --gaps-bed, and beside it or a gaps.fa)\n"
+	                "chain-beds: airlift-align chain-beds --read-size R [--max-errors E] [--gaps-out FILE] [--constant-bed FILE] [--merged-in MERGED.bed --retired-bed FILE] [--host]\n"
+	                "       [--device D] chain  (the three scripts alone; at least one output, '-' is stdout for one of them; --gaps-out needs --max-errors, --retired-bed needs\n"
+	                "       --merged-in; --host: the kernels' host twin, no device is opened; malformed input is refused as FILE:LINE: reason)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -109,6 +122,7 @@ int main(int argc, char **argv)
 	enum { MODE_MEM, MODE_ALN, MODE_SAMSE, MODE_MM2, MODE_TOKENS } mode = MODE_MM2; int tok_size = 0, tok_skip = 1;
 	bool prefilter = false; int pf[4] = {3, 3, 5, 3};          // adjacency e, GreedySnake e, k-mer size, rounds
 	const char *dump_fn = nullptr, *regions_fn = nullptr, *merged_fn = nullptr, *gaps_bed_fn = nullptr;
+	const char *chain_fn = nullptr, *retired_fn = nullptr, *constant_fn = nullptr, *gaps_out_fn = nullptr; int max_errors = -1;
 	OutSel sel;
 	int i = 1; bool k_given = false; int rank = -1, world = 0; const char *rendezvous = nullptr, *out_path = nullptr;
 	if (argc < 2) return usage();
@@ -122,6 +136,45 @@ int main(int argc, char **argv)
 			fprintf(stderr, "[ERROR] --gaps-bed names the gap regions of a tokens run (airlift-align tokens --read-size R --skip S --gaps-bed GAPS.bed ref.fa): it cannot be combined with another mode\n");
 			return 1;
 		}
+	for (int j = 2; j < argc; ++j)
+		if (!strcmp(argv[j], "--chain") && strcmp(argv[1], "tokens") != 0) {
+			fprintf(stderr, "[ERROR] --chain names the chain file of a tokens run (airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E ref.fa; the scripts alone: airlift-align chain-beds): it cannot be combined with another mode\n");
+			return 1;
+		}
+	if (!strcmp(argv[1], "chain-beds")) {          // 2_get_updated_regions_bed.py + get_constant_regions.py + get_retired_regions.py
+		int R = 0, E = -1, dev = -1; unsigned cf = 0; const char *g_fn = nullptr, *c_fn = nullptr, *r_fn = nullptr, *m_fn = nullptr; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "--read-size") && j + 1 < argc) R = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--max-errors") && j + 1 < argc) E = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--gaps-out") && j + 1 < argc) g_fn = argv[++j];
+			else if (!strcmp(argv[j], "--constant-bed") && j + 1 < argc) c_fn = argv[++j];
+			else if (!strcmp(argv[j], "--retired-bed") && j + 1 < argc) r_fn = argv[++j];
+			else if (!strcmp(argv[j], "--merged-in") && j + 1 < argc) m_fn = argv[++j];
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--host")) cf |= AL_CHAIN_HOST;
+			else p.push_back(argv[j]);
+		}
+		const int n_stdout = (g_fn && !strcmp(g_fn, "-")) + (c_fn && !strcmp(c_fn, "-")) + (r_fn && !strcmp(r_fn, "-"));
+		const char *why = p.size() != 1 || R <= 0 ? "" : (!g_fn && !c_fn && !r_fn) ? "at least one of --gaps-out, --constant-bed, --retired-bed is required" : (g_fn && E < 0) ? "--gaps-out needs --max-errors E (0 or more)"
+		                : (r_fn && !m_fn) ? "--retired-bed needs --merged-in MERGED.bed" : n_stdout > 1 ? "at most one output may be '-' (stdout)" : nullptr;
+		if (why && !*why) { fprintf(stderr, "Usage: airlift-align chain-beds --read-size R [--max-errors E] [--gaps-out FILE] [--constant-bed FILE] [--merged-in MERGED.bed --retired-bed FILE] [--host] [--device D] chain\n"); return 1; }
+		if (why) { fprintf(stderr, "[ERROR] chain-beds: %s\n", why); return 1; }
+		// the outputs are buffered and opened only once the rows exist: a refused input writes nothing
+		FILE *tg = g_fn ? tmpfile() : nullptr, *tc = c_fn ? tmpfile() : nullptr, *tr = r_fn ? tmpfile() : nullptr;
+		if ((g_fn && !tg) || (c_fn && !tc) || (r_fn && !tr)) { perror("[ERROR] chain-beds: tmpfile"); return 1; }
+		int rc2 = al_chain_beds(p[0], R, E, m_fn, tg, tc, tr, cf, dev) == 0 ? 0 : 1;
+		auto copy_out = [&](FILE *t, const char *fn) {
+			if (!t || rc2) return;
+			FILE *o = strcmp(fn, "-") ? fopen(fn, "wb") : stdout;
+			if (!o) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fn); rc2 = 1; return; }
+			char buf[1 << 16]; size_t k; rewind(t);
+			while ((k = fread(buf, 1, sizeof(buf), t)) > 0) if (fwrite(buf, 1, k, o) != k) { rc2 = 1; break; }
+			if ((o == stdout ? fflush(o) : fclose(o)) == EOF) rc2 = 1;
+		};
+		copy_out(tg, g_fn); copy_out(tc, c_fn); copy_out(tr, r_fn);
+		fflush(stderr);
+		_exit(rc2);
+	}
 	al_set_opt(0, &io, &mo);
 	al_set_opt("sr", &io, &mo);
 	mo.flag |= AL_F_OUT_SAM | AL_F_CIGAR;
@@ -245,6 +298,11 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "--regions-bed") && i + 1 < argc) regions_fn = argv[++i];         // tokens: the merged regions per gap sequence instead of SAM
 		else if (!strcmp(a, "--merged-bed") && i + 1 < argc) merged_fn = argv[++i];          // tokens: ... merged across all gap sequences
 		else if (!strcmp(a, "--gaps-bed") && i + 1 < argc) gaps_bed_fn = argv[++i];            // tokens: the gap sequences are these regions of the reference itself
+		else if (!strcmp(a, "--chain") && i + 1 < argc) chain_fn = argv[++i];                  // tokens: the gap regions are made from this chain file, on the GPU
+		else if (!strcmp(a, "--max-errors") && i + 1 < argc) max_errors = atoi(argv[++i]);
+		else if (!strcmp(a, "--gaps-out") && i + 1 < argc) gaps_out_fn = argv[++i];            // tokens --chain: the gaps rows, as 2_get_updated_regions_bed.py writes them
+		else if (!strcmp(a, "--retired-bed") && i + 1 < argc) retired_fn = argv[++i];          // tokens --chain: the retired regions instead of SAM
+		else if (!strcmp(a, "--constant-bed") && i + 1 < argc) constant_fn = argv[++i];        // tokens --chain: the constant regions instead of SAM
 		else if (!strcmp(a, "--bam")) bam_mode = 1;
 		else if (!strcmp(a, "--sorted-bam")) bam_mode = 2;
 		else if (!strcmp(a, "-l") && i + 1 < argc) bam_level = atoi(argv[++i]);
@@ -273,6 +331,22 @@ int main(int argc, char **argv)
 		else if (!strcmp(a, "-o") && i + 1 < argc) out_path = argv[++i];                   // opened below, once it is known whether this is one of several processes (which open the merged file themselves)
 		else if (!strcmp(a, "--version")) { puts(al_version()); return 0; }
 		else { fprintf(stderr, "[WARNING] airlift-align: option '%s' ignored\n", a); }
+	}
+	if (!chain_fn && (retired_fn || constant_fn || gaps_out_fn)) {
+		fprintf(stderr, "[ERROR] %s writes rows made from the chain file of a tokens run: it needs --chain CHAIN (airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E ref.fa)\n", retired_fn ? "--retired-bed" : constant_fn ? "--constant-bed" : "--gaps-out");
+		return 1;
+	}
+	if (chain_fn) {                                                     // (decided before the reference is read or a device opened)
+		const bool ranked = world > 1 || rank >= 0;
+		const char *outs[5] = {regions_fn, merged_fn, retired_fn, constant_fn, gaps_out_fn}; int n_stdout = 0;
+		for (const char *o : outs) n_stdout += o && !strcmp(o, "-");
+		const bool bed_mode = regions_fn || merged_fn || retired_fn || constant_fn;
+		const char *why = sel.paf ? "--paf" : bam_mode == 2 ? "--sorted-bam" : bam_mode ? "--bam" : count_only ? "--count-candidates" : devices.size() > 1 ? "--devices of more than one lane" : ranked ? "--world / --rank / --ranked" : nullptr;
+		if (why) { fprintf(stderr, "[ERROR] --chain makes the gap regions of a tokens run from the chain file on one device, in one process, for SAM or the merged regions: it cannot be combined with %s\n", why); return 1; }
+		if (gaps_bed_fn) { fprintf(stderr, "[ERROR] --chain takes the place of --gaps-bed (the gaps BED is made from the chain file): give one of them, not both\n"); return 1; }
+		if (pos.size() > 1) { fprintf(stderr, "[ERROR] --chain takes the place of the gap FASTA: give the reference alone (airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E ref.fa), not '%s' as well\n", pos[1]); return 1; }
+		if (max_errors < 0) { fprintf(stderr, "[ERROR] --chain needs --max-errors E (0 or more): the gaps are padded by the read size plus E\n"); return 1; }
+		if (n_stdout > (bed_mode ? 1 : 0)) { fprintf(stderr, "[ERROR] --chain: %s\n", bed_mode ? "at most one of the BED outputs may be '-' (stdout)" : "--gaps-out cannot be '-' beside the SAM on stdout"); return 1; }
 	}
 	if (gaps_bed_fn) {                                                  // (decided before the reference is read or a device opened)
 		const bool ranked = world > 1 || rank >= 0;
@@ -316,7 +390,7 @@ int main(int argc, char **argv)
 	} else if (mode == MODE_SAMSE) {
 		if (pos.size() < 3) return usage();
 		ref = pos[0]; reads.push_back(pos[2]);
-	} else if (gaps_bed_fn) {        // tokens --gaps-bed: the reference alone
+	} else if (gaps_bed_fn || chain_fn) {        // tokens --gaps-bed / --chain: the reference alone
 		if (pos.size() != 1) return usage();
 		ref = pos[0];
 	} else {
@@ -337,7 +411,18 @@ int main(int argc, char **argv)
 	if (al_env().timing) fprintf(stderr, "[airlift] index build %.3f s\n", (ts1.tv_sec - ts0.tv_sec) + 1e-9 * (ts1.tv_nsec - ts0.tv_nsec));
 	if (!mi) { fprintf(stderr, "[ERROR] failed to open file '%s'\n", ref); return 1; }
 	if (dump_fn && !ref_is_idx && al_idx_dump(dump_fn, mi) != 0) { al_idx_destroy(mi); return 1; }
-	if (reads.empty() && !gaps_bed_fn) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
+	if (reads.empty() && !gaps_bed_fn && !chain_fn) { al_idx_destroy(mi); fflush(stderr); _exit(0); }       // (index only)
+	if (mode == MODE_TOKENS && chain_fn) {   // the gap regions from the chain file; SAM, or the BED outputs instead of it
+		FILE *f[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; const char *fn[5] = {regions_fn, merged_fn, retired_fn, constant_fn, gaps_out_fn}; int rc2 = 0;
+		for (int j = 0; j < 5 && rc2 == 0; ++j) if (fn[j]) { f[j] = strcmp(fn[j], "-") ? fopen(fn[j], "wb") : stdout; if (!f[j]) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fn[j]); rc2 = 1; } }
+		if (rc2 == 0) rc2 = (regions_fn || merged_fn || retired_fn || constant_fn) ? al_map_tokens_chain_regions(mi, chain_fn, max_errors, tok_size, tok_skip, &mo, n_threads, f[0], f[1], device, f[2], f[3], f[4])
+		                                                                           : al_map_tokens_chain_file(mi, chain_fn, max_errors, tok_size, tok_skip, &mo, n_threads, stdout, rg, device, f[4]);
+		al_idx_destroy(mi);
+		for (FILE *o : f) if (o && (o == stdout ? fflush(o) : fclose(o)) == EOF) rc2 = 1;
+		if (fflush(stdout) == EOF) rc2 = 1;
+		fflush(stderr);
+		_exit(rc2 == 0 ? 0 : 1);
+	}
 	if (mode == MODE_TOKENS && (regions_fn || merged_fn)) {   // ... and the regions of the tokens' alignments instead of their SAM
 		FILE *fr = nullptr, *fm = nullptr; int rc2 = 0;
 		auto open_out = [&](const char *fn, FILE *&f) { if (!fn) return; f = strcmp(fn, "-") ? fopen(fn, "wb") : stdout; if (!f) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fn); rc2 = 1; } };

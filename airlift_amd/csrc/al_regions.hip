@@ -122,6 +122,7 @@ void al_regions_close(AlRegions *R)
 	delete R;
 }
 void al_regions_stat(const AlRegions *R, AlRegionsStat *st) { *st = R->st; }
+void al_regions_device_list(const AlRegions *R, const AlRegIv **list, uint64_t *n, int *device) { *list = R->list.p; *n = R->n; *device = R->device; }
 
 // the list becomes its regions, in place (n: their number)
 int AlRegions::fold()

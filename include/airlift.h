@@ -388,6 +388,41 @@ int  al_dbg_tokens_table(uint32_t n_rows, const char *names, size_t names_len, c
 int  al_dbg_tokens_table_host(uint32_t n_rows, const char *names, size_t names_len, const uint64_t *src, const uint32_t *len, int read_size, int skip, int seed,
                               uint64_t t0, uint64_t n, uint64_t *o_start, uint32_t *o_hash, uint64_t *o_first_tok, uint32_t *o_h_prefix);
 
+/* ---- the chain file's region logic (chain-beds, tokens --chain): 2_get_updated_regions_bed.py, get_constant_regions.py and get_retired_regions.py ----
+ * Comments ('#' first), blank lines, headers "chain score tName tSize tStrand tStart tEnd qName qSize qStrand qStart qEnd id" and alignment lines
+ * "size dt dq" / "size" of `chain_fn` are read on the host; the pad / clamp / sort / merge / invert of the three scripts runs on `device` (-1: the
+ * default device), or with AL_CHAIN_HOST in `flags` through the kernels' host twin, which opens no device.  Inclusive rows "name\tstart\tend\n":
+ *   gaps      the gaps between the blocks, padded by read_size + max_errors, clamped to the contig and merged where they overlap (2_get_updated_regions_bed.py)
+ *   constant  the blocks as they are, contig by contig in order of first header (get_constant_regions.py)
+ *   retired   what neither a block nor a row of `merged_fn` ("contig start end", the numbers as written), each padded by read_size, covers -- with the
+ *             script's tail rule: the stretch behind a contig's last region is a row only when the contig already has one (get_retired_regions.py)
+ * Any FILE may be NULL, not all; gaps needs max_errors >= 0, retired needs merged_fn.  Malformed input (a data line before the first header, a field
+ * count other than 1 or 3, a non-numeric field, size 0, a line after a chain's 1-field line, tSize >= 2^31, a tStrand other than '+', a block or gap
+ * that ends beyond tSize; a merged row with fewer than 3 fields, end < start, start beyond the contig, or a contig no header names) is refused as
+ * FILE:LINE: reason with -1, before any device is opened.  The scripts' chatter on stdout is not printed. */
+#define AL_CHAIN_HOST 1u
+int  al_chain_beds(const char *chain_fn, int read_size, int max_errors, const char *merged_fn, FILE *gaps, FILE *constant, FILE *retired, unsigned flags, int device);
+/* tokens with the chain file in place of the gaps BED: the gaps rows above are computed on the device and tiled exactly as al_map_tokens_bed_file /
+ * al_map_tokens_bed_regions tile the rows of the file the script writes (a row "name a b" is the sequence name:a-b).  `gaps` (may be NULL) receives those
+ * rows.  A tName the index lacks is refused (-1); a tSize that differs from the contig's length gets one notice, and rules the arithmetic.  _regions:
+ * `retired` takes the run's merged regions from the device list where they lie; a merged contig no header names takes its length from the index.
+ * `regions`, `merged`, `retired`, `constant` may each be NULL, not all four. */
+int  al_map_tokens_chain_file(const al_idx_t *mi, const char *chain_fn, int max_errors, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
+                              FILE *out, const char *rg, int device, FILE *gaps);
+int  al_map_tokens_chain_regions(const al_idx_t *mi, const char *chain_fn, int max_errors, int read_size, int skip, const al_mapopt_t *opt, int n_threads,
+                                 FILE *regions, FILE *merged, int device, FILE *retired, FILE *constant, FILE *gaps);
+/* Test taps of the region logic on a parsed line table: lines {chain, size, dt, three} in file order, chains {c_slot, c_tstart}, slots L[]; for the
+ * retired step (n_retired != NULL) merged rows {m_slot, m_start, m_end} in the slots of that step, rslot_of[n_slot] the step's slot of every chain
+ * slot and RL[n_rslot] the lengths.  Through the kernels on the current device (al_dbg_chainreg) or their host twin (al_dbg_chainreg_host).  Rows come
+ * back as triples slot, start, end: o_gaps and o_constant have room for 3 * n numbers, o_retired for 6 * (n + n_m); an output whose count pointer is NULL
+ * is not computed.  -1: arguments, or a table that breaks what the parser guarantees. */
+int  al_dbg_chainreg(uint64_t n, const uint32_t *chain, const uint32_t *size, const uint32_t *dt, const uint32_t *three, uint32_t n_chain, const uint32_t *c_slot, const uint32_t *c_tstart,
+                     uint32_t n_slot, const uint32_t *L, uint64_t n_m, const uint32_t *m_slot, const uint32_t *m_start, const uint32_t *m_end, uint32_t n_rslot, const uint32_t *rslot_of, const uint32_t *RL,
+                     int R, int E, uint32_t *o_gaps, uint64_t *n_gaps, uint32_t *o_constant, uint64_t *n_constant, uint32_t *o_retired, uint64_t *n_retired);
+int  al_dbg_chainreg_host(uint64_t n, const uint32_t *chain, const uint32_t *size, const uint32_t *dt, const uint32_t *three, uint32_t n_chain, const uint32_t *c_slot, const uint32_t *c_tstart,
+                          uint32_t n_slot, const uint32_t *L, uint64_t n_m, const uint32_t *m_slot, const uint32_t *m_start, const uint32_t *m_end, uint32_t n_rslot, const uint32_t *rslot_of, const uint32_t *RL,
+                          int R, int E, uint32_t *o_gaps, uint64_t *n_gaps, uint32_t *o_constant, uint64_t *n_constant, uint32_t *o_retired, uint64_t *n_retired);
+
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
 	uint64_t n_frag, n_reads, n_bases;
