@@ -3,10 +3,8 @@
 //   (scan)          segmented sum of size + dt over the lines of every chain (al_chn_sum_op): T[i] = tStart + the sum before line i
 //   k_chn_expand    lane per line: its padded gap, its padded block (retired step) and its block as it is (constant rows), each as {slot, start, end, index}
 //   k_chn_expand_m  lane per merged region (retired step): the row padded, its slot from the row itself (uploaded) or from its rank (the run's device list)
-//   chn_fold        (merge sort)    by (slot, start, index): one rocPRIM merge sort of the 16-byte elements under al_chn_less
-//                   (scan)          segmented inclusive max-scan of `end` (al_reg_scan_op) over the slot's prefix -- see FORM OF THE MERGE in the header
-//                   (scan)          exclusive sum of the head flags (al_chn_head, strict or not): every element's region number, and their count
-//                   k_chn_compact   one element per region: the head writes slot and start, the region's last element its running maximum
+//   ChainRegDev::fold  the fold of al_fold.h under AlChnFold (merge sort by (slot, start, index), max-scan over the slot's prefix -- see FORM OF THE MERGE in
+//                   the header --, head sum strict or not, k_fold_compact): the elements of a slot that is some become the regions reg[]
 //   k_chn_invert    lane per region: its leading hole into row 2j, and the slot's hole count (one atomic per hole)
 //   k_chn_tail      lane per region: the tail of the last region of a slot that has a hole, into row 2j + 1
 //   k_chn_gather    the rows that are some, in order, to the front (exclusive sum of their flags)
@@ -16,11 +14,11 @@
 #include <stdlib.h>
 #include <string.h>
 #include <chrono>
-#include <rocprim/rocprim.hpp>
 #include "al_internal.h"
 #include "al_device.h"
 #include "al_runtime.h"
 #include "al_dev_chainreg.h"
+#include "al_fold.h"
 
 // T of line i from the inclusive sums
 __device__ __forceinline__ uint32_t chn_T(const AlChnLine &l, const uint64_t *__restrict__ tsum, const uint32_t *__restrict__ c_tstart, uint32_t i)
@@ -66,38 +64,17 @@ k_chn_expand_m(const AlRegIv *__restrict__ M, uint32_t n_m, const uint32_t *__re
 	out[i] = v;
 }
 
-struct ChnLess { __host__ __device__ bool operator()(const AlChnIv &a, const AlChnIv &b) const { return al_chn_less(a, b); } };
 struct ChnLessIdx { __host__ __device__ bool operator()(const AlChnIv &a, const AlChnIv &b) const { return al_chn_less_idx(a, b); } };
 struct ChnSumOp { __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return al_chn_sum_op(a, b); } };
 struct ChnSumIn {
 	const AlChnLine *l;
 	__host__ __device__ uint64_t operator()(uint32_t i) const { return al_chn_sum_elem(i == 0 || l[i - 1].chain != l[i].chain, l[i].size + l[i].dt); }
 };
-struct ChnMaxOp { __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return al_reg_scan_op(a, b); } };
-struct ChnMaxIn {
-	const AlChnIv *s;
-	__host__ __device__ uint64_t operator()(uint32_t i) const { return al_reg_scan_elem(i == 0 || s[i - 1].slot != s[i].slot, s[i].end); }
-};
-struct ChnHeadIn {             // element i of the head sum's input (i == n: the sum's last element, the total)
-	const AlChnIv *s; const uint64_t *m; uint32_t n; bool strict;
-	__host__ __device__ uint32_t operator()(uint32_t i) const { return i < n && al_chn_head(s, m, i, strict) ? 1u : 0u; }
-};
 struct ChnSomeIn {             // row i is some (i == n: the total)
 	const AlChnIv *r; uint32_t n;
 	__host__ __device__ uint32_t operator()(uint32_t i) const { return i < n && r[i].slot != AL_CHN_NONE ? 1u : 0u; }
 };
 
-__global__ void __launch_bounds__(256)
-k_chn_compact(const AlChnIv *__restrict__ s, const uint64_t *__restrict__ m, const uint32_t *__restrict__ idx, uint32_t n, AlChnIv *__restrict__ reg)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint32_t k = idx[i], k_next = idx[i + 1];                      // idx[i + 1] - idx[i]: 1 when i is a head; idx has n + 1 entries, idx[n] = the number of regions
-	const bool head = k_next != k, last = i + 1 == n || idx[i + 2] != k_next;
-	const uint32_t r = head ? k : k - 1;                                  // the region i belongs to (element 0 is a head, so k >= 1 where i is none)
-	if (head) { reg[r].slot = s[i].slot; reg[r].start = s[i].start; reg[r].idx = r; }
-	if (last) reg[r].end = (uint32_t)m[i];
-}
 __global__ void __launch_bounds__(256)
 k_chn_invert(const AlChnIv *__restrict__ reg, uint32_t k, AlChnIv *__restrict__ rows /* [2k] */, uint32_t *__restrict__ holes, uint32_t n_rslot)
 {
@@ -125,7 +102,7 @@ k_chn_gather(const AlChnIv *__restrict__ rows, const uint32_t *__restrict__ idx,
 	if (idx[i + 1] != idx[i]) out[idx[i]] = rows[i];                      // (idx has n + 1 entries, idx[n] <= n rows are written)
 }
 
-#define CHN_CHECK(x) do { const hipError_t e__ = (x); if (e__ != hipSuccess) { fprintf(stderr, "[airlift] chainreg: %s: %s\n", #x, hipGetErrorString(e__)); return -1; } } while (0)
+#define CHN_CHECK(x) AL_HIP_CHECK_AS("chainreg", x)
 #define CHN_LAUNCH(kern, n, ...) kern<<<dim3(((uint32_t)(n) + 255) / 256), dim3(256), 0, s>>>(__VA_ARGS__)
 
 namespace {
@@ -159,10 +136,8 @@ struct ChainRegDev {
 	{
 		if (idx.ensure((size_t)n + 2)) return AL_ERR_NOMEM;
 		auto it = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), in);
-		size_t bytes = 0;
-		CHN_CHECK(rocprim::exclusive_scan(nullptr, bytes, it, idx.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
-		if (tmp.ensure(bytes + 16)) return AL_ERR_NOMEM;
-		CHN_CHECK(rocprim::exclusive_scan(tmp.p, bytes, it, idx.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s));
+		const int r = al_prim_run(tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, it, idx.p, 0u, (size_t)n + 1, rocprim::plus<uint32_t>(), s); }, "chainreg");
+		if (r) return r;
 		CHN_CHECK(hipMemcpyAsync(total, idx.p + n, 4, hipMemcpyDeviceToHost, s));
 		CHN_CHECK(hipStreamSynchronize(s));
 		st.bytes_d2h += 4;
@@ -171,30 +146,18 @@ struct ChainRegDev {
 	template <class Less> int sort(const AlChnIv *in, uint32_t n, Less less)
 	{
 		if (sorted.ensure(n)) return AL_ERR_NOMEM;
-		size_t bytes = 0;
-		CHN_CHECK(rocprim::merge_sort(nullptr, bytes, in, sorted.p, (size_t)n, less, s));
-		if (tmp.ensure(bytes + 16)) return AL_ERR_NOMEM;
-		CHN_CHECK(rocprim::merge_sort(tmp.p, bytes, in, sorted.p, (size_t)n, less, s));
-		return 0;
+		return al_prim_run(tmp, [&](void *t, size_t &b) { return rocprim::merge_sort(t, b, in, sorted.p, (size_t)n, less, s); }, "chainreg");
 	}
 	// the n_all elements of `in` become their regions reg[0, *k); only the first n of the sorted list are of a slot that is some (the others sort behind them)
 	int fold(const AlChnIv *in, uint32_t n_all, uint32_t n, bool strict, uint32_t *k)
 	{
 		*k = 0;
 		if (n == 0) return 0;
-		int r = sort(in, n_all, ChnLess());
+		if (sorted.ensure(n_all) || run_max.ensure(n) || idx.ensure((size_t)n + 1) || reg.ensure(n)) return AL_ERR_NOMEM;
+		const int r = al_fold_enqueue<AlChnFold>("chainreg", in, n_all, n, strict, reg.p, nullptr, sorted.p, run_max.p, idx.p, tmp, s);
 		if (r) return r;
-		if (run_max.ensure(n) || reg.ensure(n)) return AL_ERR_NOMEM;
-		auto in_max = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), ChnMaxIn{sorted.p});
-		size_t bytes = 0;
-		CHN_CHECK(rocprim::inclusive_scan(nullptr, bytes, in_max, run_max.p, (size_t)n, ChnMaxOp(), s));
-		if (tmp.ensure(bytes + 16)) return AL_ERR_NOMEM;
-		CHN_CHECK(rocprim::inclusive_scan(tmp.p, bytes, in_max, run_max.p, (size_t)n, ChnMaxOp(), s));
-		if ((r = sum_flags(ChnHeadIn{sorted.p, run_max.p, n, strict}, n, k)) != 0) return r;
-		if (*k == 0 || *k > n) { fprintf(stderr, "[airlift] chainreg: the fold of %u intervals left %u\n", n, *k); return -1; }
-		CHN_LAUNCH(k_chn_compact, n, (const AlChnIv *)sorted.p, (const uint64_t *)run_max.p, (const uint32_t *)idx.p, n, reg.p);
-		CHN_CHECK(hipGetLastError());
-		return 0;
+		st.bytes_d2h += 4;
+		return al_fold_count("chainreg", idx.p, n, s, k);
 	}
 	int run(const AlChnIn &in, int R, int E, std::vector<AlChnIv> *gaps, std::vector<AlChnIv> *constant, std::vector<AlChnIv> *retired);
 };
@@ -224,10 +187,7 @@ int ChainRegDev::run(const AlChnIn &in, int R, int E, std::vector<AlChnIv> *gaps
 	CHN_CHECK(hipEventRecord(ev[0], s));
 	if (n) {
 		auto in_sum = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), ChnSumIn{line.p});
-		size_t bytes = 0;
-		CHN_CHECK(rocprim::inclusive_scan(nullptr, bytes, in_sum, tsum.p, (size_t)n, ChnSumOp(), s));
-		if (tmp.ensure(bytes + 16)) return AL_ERR_NOMEM;
-		CHN_CHECK(rocprim::inclusive_scan(tmp.p, bytes, in_sum, tsum.p, (size_t)n, ChnSumOp(), s));
+		if ((r = al_prim_run(tmp, [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, in_sum, tsum.p, (size_t)n, ChnSumOp(), s); }, "chainreg")) != 0) return r;
 		CHN_LAUNCH(k_chn_expand, n, (const AlChnLine *)line.p, (const uint64_t *)tsum.p, n, (const uint32_t *)c_slot.p, (const uint32_t *)c_tstart.p, in.n_chain,
 		                   (const uint32_t *)L.p, in.n_slot, (const uint32_t *)rslot_of.p, (const uint32_t *)RL.p, in.n_rslot, (uint32_t)(R + (E > 0 ? E : 0)), (uint32_t)R, n_m,
 		                   gaps ? a.p : nullptr, retired ? b.p + n_m : nullptr, constant ? rows.p : nullptr, bad.p);

@@ -16,7 +16,7 @@
 //     [g, g - 1], kept: once padded it marks the surroundings of an insertion).
 //  3. pad([a, b], p, L) = [a >= p ? a - p : 0, b + p <= L - 1 ? b + p : L - 1]                                         (al_chn_pad)
 //  4. merge(strict): order (slot, start, input index); within a slot an element joins the current region iff start < region.end (strict) or
-//     start <= region.end; the region's end becomes the maximum.                                                         (al_chn_less, al_chn_head)
+//     start <= region.end; the region's end becomes the maximum.                                                         (AlChnFold, al_dev_fold.h)
 //  5. Gaps rows = merge(strict) over pad(G[i], R + E, L[slot]), slot by slot.
 //  6. Constant rows = B[i], unpadded, unmerged, ordered (slot, input index).
 //  7. Retired rows, given merged regions M (rows "contig start end", the numbers as written, inclusive): the slots of this step are M's contigs in order
@@ -26,7 +26,7 @@
 //     first base and bare behind gets no row).
 //
 // FORM OF THE MERGE.  The device compares an element's start with the running maximum of `end` over the slot's PREFIX in sorted order (one segmented scan,
-// al_reg_scan_op of al_dev_regions.h), the scripts with the maximum over the current REGION.  They are the same number: every element of an earlier region
+// al_fold_scan_op of al_dev_fold.h), the scripts and the twin with the maximum over the current REGION.  They are the same number: every element of an earlier region
 // of the slot ends at or before (strict) / before (not strict) the start of the head of the next region, that start is <= every later start of the slot
 // (sorted), and every start is <= its own end (no inverted interval: the parser's last rule, p >= 1 for the empty gaps, and M's rows are refused unless
 // start <= end and start < L).  So the earlier regions' maxima never exceed an end of the current region, and the prefix maximum is the region's.
@@ -39,7 +39,7 @@
 #include <string>
 #include <vector>
 #include <unordered_map>
-#include "al_dev_regions.h"       // AL_DHD, al_reg_scan_elem / al_reg_scan_op
+#include "al_dev_regions.h"       // AlRegIv; al_dev_fold.h
 
 struct alignas(16) AlChnLine { uint32_t chain, size, dt, three; };
 struct alignas(16) AlChnIv { uint32_t slot, start, end, idx; };
@@ -79,13 +79,13 @@ AL_DHD AlChnIv al_chn_block(const AlChnLine &l, uint32_t T, uint32_t slot, uint3
 	if (p) al_chn_pad(v.start, v.end, p, L, &v.start, &v.end);
 	return v;
 }
-// element i of the sorted list s[] (running maxima m[] of `end` over the slot's prefix) starts a region
-AL_DHD bool al_chn_head(const AlChnIv *s, const uint64_t *m, uint64_t i, bool strict)
-{
-	if (i == 0 || s[i - 1].slot != s[i].slot) return true;
-	const uint32_t mx = (uint32_t)m[i - 1];
-	return strict ? s[i].start >= mx : s[i].start > mx;
-}
+// the fold of al_dev_fold.h: a segment per slot; a region's idx is its number
+struct AlChnFold {
+	typedef AlChnIv Elem;
+	AL_DHD_M bool less(const AlChnIv &a, const AlChnIv &b) { return al_chn_less(a, b); }
+	AL_DHD_M bool same_seg(const AlChnIv &a, const AlChnIv &b) { return a.slot == b.slot; }
+	AL_DHD_M void head(AlChnIv &r, const AlChnIv &h, uint32_t k) { r.slot = h.slot; r.start = h.start; r.idx = k; }
+};
 // region j of the sorted regions r[0, k): its leading hole (slot AL_CHN_NONE: none)
 AL_DHD AlChnIv al_chn_hole(const AlChnIv *r, uint64_t j)
 {
@@ -145,17 +145,6 @@ static inline void al_chn_T_host(const AlChnIn &in, std::vector<uint32_t> &T)
 		T[i] = in.c_tstart[l.chain] + (uint32_t)acc - (l.size + l.dt);
 	}
 }
-// v becomes its regions, as the scripts' interval_merge makes them: sorted (stable by start within a slot), one pass, the end compared is the region's
-static inline void al_chn_merge_host(std::vector<AlChnIv> &v, bool strict)
-{
-	std::sort(v.begin(), v.end(), [](const AlChnIv &a, const AlChnIv &b) { return al_chn_less(a, b); });
-	size_t k = 0;
-	for (size_t i = 0; i < v.size(); ++i) {
-		if (k && v[k - 1].slot == v[i].slot && (strict ? v[i].start < v[k - 1].end : v[i].start <= v[k - 1].end)) { if (v[i].end > v[k - 1].end) v[k - 1].end = v[i].end; }
-		else v[k++] = v[i];
-	}
-	v.resize(k);
-}
 static inline void al_chn_gaps_host(const AlChnIn &in, const uint32_t *T, uint32_t p, std::vector<AlChnIv> &rows)
 {
 	rows.clear();
@@ -164,7 +153,7 @@ static inline void al_chn_gaps_host(const AlChnIn &in, const uint32_t *T, uint32
 		const AlChnIv g = al_chn_gap(in.line[i], T[i], s, p, in.L[s], (uint32_t)i);
 		if (g.slot != AL_CHN_NONE) rows.push_back(g);
 	}
-	al_chn_merge_host(rows, true);
+	al_fold_host<AlChnFold>(rows, true);
 }
 static inline void al_chn_constant_host(const AlChnIn &in, const uint32_t *T, std::vector<AlChnIv> &rows)
 {
@@ -182,7 +171,7 @@ static inline void al_chn_retired_host(const AlChnIn &in, const uint32_t *T, uin
 		al_chn_pad(v.start, v.end, p, in.RL[s], &v.start, &v.end);        // (p may be 0: the pad of nothing)
 		u.push_back(v);
 	}
-	al_chn_merge_host(u, false);
+	al_fold_host<AlChnFold>(u, false);
 	rows.clear();
 	std::vector<uint32_t> holes(in.n_rslot, 0);
 	for (size_t j = 0; j < u.size(); ++j) {

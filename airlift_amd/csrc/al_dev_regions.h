@@ -4,13 +4,11 @@
 //
 // THE FUNCTION.  Input: intervals {group, rank, start, end} -- [start, end) on the contig whose NAME has rank `rank` in byte order, found by a token of
 // gap sequence `group` (the index of its '>' entry in GAPS.fa).  Output: the intervals of every (group, rank) merged as `sort-bed | mergeBed` (distance 0)
-// merges them, in the order (group, rank, start, end):
+// merges them, in the order (group, rank, start, end): the fold of al_dev_fold.h under AlRegFold, with the plain rule --
 //
 //  1. Order.  al_reg_less: (group, rank, start, end), all unsigned.
-//  2. Running maximum.  In that order M[i] = the largest end of the elements of i's (group, rank) segment up to and including i: an inclusive scan with
-//     al_reg_scan_op over (segment starts here, end) pairs, (f1, m1) + (f2, m2) = (f1 | f2, f2 ? m2 : max(m1, m2)), which is associative.
-//  3. Heads.  Element i starts a region when it starts a segment or start[i] > M[i - 1]: a book-ended interval (start == M) joins, a nested one does not
-//     shorten the region (M, not the previous end, is compared).
+//  2. Segments.  al_reg_same_seg: one per (group, rank).
+//  3. Heads.  Element i starts a region when it starts a segment or start[i] > M[i - 1]: a book-ended interval (start == M) joins.
 //  4. Regions.  Region k = {group, rank, start of its head, M of its last element}.
 //
 // Merging is idempotent and merging merged regions with further intervals equals merging all the raw intervals, so the list may be folded (replaced by
@@ -23,7 +21,7 @@
 #include <algorithm>
 #include <string>
 #include <vector>
-#include "al_dev_deflate.h"       // AL_DHD
+#include "al_dev_fold.h"
 
 #define AL_REG_FOLD_CAP (1u << 21)   // intervals the device list may hold before it is folded in place: a run holds at most this many plus one batch's
 
@@ -37,31 +35,14 @@ AL_DHD bool al_reg_less(const AlRegIv &a, const AlRegIv &b)
 	return a.end < b.end;
 }
 AL_DHD bool al_reg_same_seg(const AlRegIv &a, const AlRegIv &b) { return a.group == b.group && a.rank == b.rank; }
-// a scan element: bit 32 = a segment starts at (or inside) what the element covers, low word = the running maximum of `end` since then
-AL_DHD uint64_t al_reg_scan_elem(bool seg_start, uint32_t end) { return (seg_start ? 1ull << 32 : 0ull) | end; }
-AL_DHD uint64_t al_reg_scan_op(uint64_t a, uint64_t b)
-{
-	const uint32_t ma = (uint32_t)a, mb = (uint32_t)b;
-	return ((a | b) & (1ull << 32)) | ((b >> 32 & 1) ? mb : (ma > mb ? ma : mb));
-}
-// element i of the sorted list s[] (running maxima m[] of its predecessors) starts a region
-AL_DHD bool al_reg_head(const AlRegIv *s, const uint64_t *m, uint64_t i) { return i == 0 || !al_reg_same_seg(s[i - 1], s[i]) || s[i].start > (uint32_t)m[i - 1]; }
+struct AlRegFold {
+	typedef AlRegIv Elem;
+	AL_DHD_M bool less(const AlRegIv &a, const AlRegIv &b) { return al_reg_less(a, b); }
+	AL_DHD_M bool same_seg(const AlRegIv &a, const AlRegIv &b) { return al_reg_same_seg(a, b); }
+	AL_DHD_M void head(AlRegIv &r, const AlRegIv &h, uint32_t) { r.group = h.group; r.rank = h.rank; r.start = h.start; }
+};
 // the record the SAM writer prints for a hit (write_batch, al_pipeline.cpp): every hit, without the secondary ones (id != parent) under AL_F_NO_PRINT_2ND
 AL_DHD bool al_reg_printed(int32_t id, int32_t parent, bool no_print_2nd) { return !(no_print_2nd && id != parent); }
-
-// ---- the host twin ---------------------------------------------------------------------------------------------------------------------------------------------
-// v becomes its regions (sort, then one pass); zero_group: every group is set to 0 first (the merge across all gaps)
-static inline void al_regions_merge_host(std::vector<AlRegIv> &v, bool zero_group = false)
-{
-	if (zero_group) for (AlRegIv &x : v) x.group = 0;
-	std::sort(v.begin(), v.end(), [](const AlRegIv &a, const AlRegIv &b) { return al_reg_less(a, b); });
-	size_t k = 0;
-	for (size_t i = 0; i < v.size(); ++i) {
-		if (k && al_reg_same_seg(v[k - 1], v[i]) && v[i].start <= v[k - 1].end) { if (v[i].end > v[k - 1].end) v[k - 1].end = v[i].end; }
-		else v[k++] = v[i];
-	}
-	v.resize(k);
-}
 
 // Contig names in the order of sort-bed / sortBed (bytes, unsigned): rank_of[rid] and the name of every rank.  Contigs of one name share a rank.
 static inline void al_regions_ranks(const std::vector<std::string> &names, std::vector<uint32_t> &rank_of, std::vector<std::string> &name_of)
@@ -91,7 +72,8 @@ static inline void al_regions_bed(std::string &o, const AlRegIv *v, size_t n, co
 	}
 }
 
-// The taps' schedule on the twin: the intervals are appended `chunk` at a time (0: all at once) with a fold after every append, then folded once more;
+// ---- the host twin ---------------------------------------------------------------------------------------------------------------------------------------------
+// The taps' schedule on the twin (al_fold_host): the intervals are appended `chunk` at a time (0: all at once) with a fold after every append, then folded once more;
 // !per_gap: the fold with the groups zeroed follows.
 static inline void al_regions_chunked_host(const AlRegIv *in, uint64_t n, uint64_t chunk, bool per_gap, std::vector<AlRegIv> &v)
 {
@@ -99,10 +81,10 @@ static inline void al_regions_chunked_host(const AlRegIv *in, uint64_t n, uint64
 	for (uint64_t at = 0; at < n; ) {
 		const uint64_t m = chunk ? std::min(chunk, n - at) : n;
 		v.insert(v.end(), in + at, in + at + m); at += m;
-		if (chunk) al_regions_merge_host(v);
+		if (chunk) al_fold_host<AlRegFold>(v, false);
 	}
-	al_regions_merge_host(v);
-	if (!per_gap) al_regions_merge_host(v, true);
+	al_fold_host<AlRegFold>(v, false);
+	if (!per_gap) { for (AlRegIv &x : v) x.group = 0; al_fold_host<AlRegFold>(v, false); }
 }
 
 // ---- the device list (al_regions.hip) ------------------------------------------------------------------------------------------------------------------------

@@ -20,7 +20,6 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -33,6 +32,7 @@
 #include "al_io.h"
 #include "al_seqio.h"
 #include "al_runtime.h"
+#include "al_prim.h"
 
 #define AL_ISEG 256            // reference positions per lane
 
@@ -176,7 +176,6 @@ k_tab_insert(const uint64_t *__restrict__ uniq, const uint32_t *__restrict__ cou
 	}
 }
 
-struct CastU64I { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
 
 #define IDX_CHECK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { \
 	fprintf(stderr, "[airlift] HIP error %s at %s:%d: %s\n", hipGetErrorName(e_), __FILE__, __LINE__, hipGetErrorString(e_)); goto fail; } } while (0)
@@ -240,7 +239,7 @@ extern "C" al_idx_t *al_idx_build_device(const char *fn, const al_idxopt_t *io, 
 	if (n_seg) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_ref_sketch<0>), dim3((unsigned)((n_seg + 63) / 64)), dim3(64), (size_t)w * 64 * 16, st,
 	                              d.S4, d.seq_off, d.seq_len, d_segf, n_seq, n_seg, w, k, d_cnt, (const uint64_t *)nullptr, (uint64_t *)nullptr, (uint64_t *)nullptr);
 	{
-		auto it = rocprim::make_transform_iterator((const uint32_t *)d_cnt, CastU64I());
+		auto it = rocprim::make_transform_iterator((const uint32_t *)d_cnt, AlCastU64());
 		IDX_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, it, d_off, (uint64_t)0, (size_t)((int)(n_seg + 1)), rocprim::plus<uint64_t>(), st));
 		IDX_CHECK(al_dev_malloc(&d_tmp, tmp_bytes + 16));
 		IDX_CHECK(rocprim::exclusive_scan(d_tmp, tmp_bytes, it, d_off, (uint64_t)0, (size_t)((int)(n_seg + 1)), rocprim::plus<uint64_t>(), st));
@@ -276,7 +275,7 @@ extern "C" al_idx_t *al_idx_build_device(const char *fn, const al_idxopt_t *io, 
 		al_dev_free(d_tmp); d_tmp = nullptr;
 		d_koff = d_y2; d_y2 = nullptr;                                    // reuse
 		{
-			auto it = rocprim::make_transform_iterator((const uint32_t *)d_kcnt, CastU64I());
+			auto it = rocprim::make_transform_iterator((const uint32_t *)d_kcnt, AlCastU64());
 			IDX_CHECK(rocprim::exclusive_scan(nullptr, tmp_bytes, it, d_koff, (uint64_t)0, (size_t)((int)n_keys), rocprim::plus<uint64_t>(), st));
 			IDX_CHECK(al_dev_malloc(&d_tmp, tmp_bytes + 16));
 			IDX_CHECK(rocprim::exclusive_scan(d_tmp, tmp_bytes, it, d_koff, (uint64_t)0, (size_t)((int)n_keys), rocprim::plus<uint64_t>(), st));

@@ -10,7 +10,6 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
@@ -19,6 +18,7 @@
 #include "al_internal.h"
 #include "al_device.h"
 #include "al_runtime.h"
+#include "al_prim.h"
 #include "al_dev_regs.h"
 
 #define AL_LREG 6                // hits per mate held in LDS
@@ -2868,16 +2868,7 @@ k_map_only_wave(const uint32_t *__restrict__ frag_first, const int32_t *__restri
 
 // ---------------------------------------------------------------------------------------------
 // host side of the stage
-struct CastU64b { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
-static int scan32(al_ctx_t *c, const uint32_t *in, uint64_t *out, int n)
-{
-	auto it = rocprim::make_transform_iterator((const uint32_t *)in, CastU64b());
-	size_t bytes = 0;
-	AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, it, out, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), c->stream));
-	if (c->scan_tmp.ensure(bytes + 16)) return -1;
-	AL_HIP_CHECK(rocprim::exclusive_scan(c->scan_tmp.p, bytes, it, out, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), c->stream));
-	return 0;
-}
+static int scan32(al_ctx_t *c, const uint32_t *in, uint64_t *out, int n) { return al_prim_scan_u32_u64(c->scan_tmp, in, out, (size_t)(n + 1), c->stream) ? -1 : 0; }
 
 __global__ void k_lower_bounds(const uint32_t *, uint32_t, LbThr, uint32_t *);   // al_kernels_seed.hip
 struct AlignState {            // lives in al_ctx_s::align_state (opaque there)
@@ -2926,10 +2917,7 @@ void al_align_state_free(al_ctx_t *c)
 static int ext_dp_sort_jobs(al_ctx_t *c, AlignState *A, uint32_t nj, hipStream_t s)
 {
 	(void)c;
-	size_t bytes = 0;
-	AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
-	if (A->sort_tmp.ensure(bytes + 16)) return -1;
-	AL_HIP_CHECK(rocprim::radix_sort_pairs(A->sort_tmp.p, bytes, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s));
+	if (al_prim_run(A->sort_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, A->job_key.p, A->job_key2.p, A->job_idx.p, A->job_idx2.p, (int)nj, 0, 24, s); })) return -1;
 	return 0;
 }
 
@@ -3119,10 +3107,7 @@ int al_run_align_stage(al_ctx_t *c)
 		regs_n0 = A->regs_n0.p;
 		AL_HIP_CHECK(hipMemsetAsync(regs_n0, 0xff, (size_t)nf * 4, s));
 		hipLaunchKernelGGL(k_iota, dim3((nf + 255) / 256), dim3(256), 0, s, c->chain_idx.p, (uint32_t)nf);
-		size_t bytes = 0;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->frag_nu.p, c->chain_key.p, (const uint32_t *)c->chain_idx.p, c->chain_idx2.p, nf, 0, 32, s));
-		if (c->scan_tmp.ensure(bytes + 16)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->frag_nu.p, c->chain_key.p, (const uint32_t *)c->chain_idx.p, c->chain_idx2.p, nf, 0, 32, s));
+		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->frag_nu.p, c->chain_key.p, (const uint32_t *)c->chain_idx.p, c->chain_idx2.p, nf, 0, 32, s); })) return -1;
 		uint32_t init[7] = {(uint32_t)nf, (uint32_t)nf, (uint32_t)nf, (uint32_t)nf, (uint32_t)nf, (uint32_t)nf, (uint32_t)nf}, lb[7];
 		AL_HIP_CHECK(hipMemcpyAsync(c->lb_buf.p, init, 28, hipMemcpyHostToDevice, s));
 		LbThr T; T.n = 7; T.v[0] = 5; T.v[1] = 65; T.v[2] = 1025; T.v[3] = 8193; T.v[4] = 2049; T.v[5] = 4097; T.v[6] = 257; for (int i = 7; i < 16; ++i) T.v[i] = 0xffffffffu;
@@ -3298,10 +3283,7 @@ int al_run_align_stage(al_ctx_t *c)
 		if (!((c->P.dbg >> 18) & 1)) {
 			if (A->ford_key.ensure(nf + 1) || A->ford_idx.ensure(nf + 1) || A->ford.ensure(nf + 1)) return -1;
 			hipLaunchKernelGGL(k_iota, dim3((nf + 255) / 256), dim3(256), 0, s, A->ford_idx.p, (uint32_t)nf);
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs_desc(nullptr, bytes, (const uint32_t *)A->n_jobs.p, A->ford_key.p, (const uint32_t *)A->ford_idx.p, A->ford.p, nf, 0, 16, s));
-			if (A->sort_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs_desc(A->sort_tmp.p, bytes, (const uint32_t *)A->n_jobs.p, A->ford_key.p, (const uint32_t *)A->ford_idx.p, A->ford.p, nf, 0, 16, s));
+			if (al_prim_run(A->sort_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs_desc(t, b, (const uint32_t *)A->n_jobs.p, A->ford_key.p, (const uint32_t *)A->ford_idx.p, A->ford.p, nf, 0, 16, s); })) return -1;
 			frag_ord = A->ford.p;
 		}
 		if (scan32(c, A->n_jobs.p, A->job_off.p, nf) || scan32(c, A->n_sc.p, A->sc_off.p, nf)) return -1;

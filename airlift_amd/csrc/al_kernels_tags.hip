@@ -12,11 +12,11 @@
 #include <hip/hip_runtime.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <stdio.h>
 #include "al_internal.h"
 #include "al_device.h"
 #include "al_runtime.h"
+#include "al_prim.h"
 
 #define TG 16                              // lanes per read
 
@@ -201,8 +201,6 @@ k_eqx_fix(AlReg *__restrict__ out, uint64_t n_out, const uint32_t *__restrict__ 
 	else r.cigar_off = (uint32_t)off[k];
 }
 
-struct CastU64t { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
-
 template <int MODE>
 static void launch_tag(const TagIn &I, bool write, uint32_t *len, const uint64_t *off, char *tag, hipStream_t s)
 {
@@ -220,11 +218,7 @@ int al_run_eqx_stage(al_ctx_t *c, AlReg *out, const uint64_t *out_off, uint64_t 
 	TagIn I{out, out_off, arena, c->rd_seq.p, c->rd_off.p, c->di.S4, c->di.seq_off, (uint32_t)c->n_reads};
 	const dim3 g((unsigned)(((uint64_t)I.n_reads * TG + 255) / 256)), b(256);
 	if (I.n_reads) hipLaunchKernelGGL((k_eqx<false>), g, b, 0, s, I, E.len.p, (const uint64_t *)nullptr, (uint32_t *)nullptr);
-	auto it = rocprim::make_transform_iterator((const uint32_t *)E.len.p, CastU64t());
-	size_t tb = 0;
-	AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, it, E.off.p, (uint64_t)0, (size_t)n_out + 1, rocprim::plus<uint64_t>(), s));
-	if (c->scan_tmp.ensure(tb + 16)) return -1;
-	AL_HIP_CHECK(rocprim::exclusive_scan(c->scan_tmp.p, tb, it, E.off.p, (uint64_t)0, (size_t)n_out + 1, rocprim::plus<uint64_t>(), s));
+	if (al_prim_scan_u32_u64(c->scan_tmp, E.len.p, E.off.p, (size_t)n_out + 1, s)) return -1;
 	uint64_t words = 0;
 	AL_HIP_CHECK(hipMemcpyAsync(&words, E.off.p + n_out, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
@@ -253,11 +247,7 @@ int al_run_tag_stage(al_ctx_t *c, const AlReg *out, const uint64_t *out_off, uin
 		else if (mode == 1) launch_tag<1>(I, false, T.len.p, nullptr, nullptr, s);
 		else launch_tag<2>(I, false, T.len.p, nullptr, nullptr, s);
 	}
-	auto it = rocprim::make_transform_iterator((const uint32_t *)T.len.p, CastU64t());
-	size_t tb = 0;
-	AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, tb, it, T.off.p, (uint64_t)0, (size_t)n_out + 1, rocprim::plus<uint64_t>(), s));
-	if (c->scan_tmp.ensure(tb + 16)) return -1;
-	AL_HIP_CHECK(rocprim::exclusive_scan(c->scan_tmp.p, tb, it, T.off.p, (uint64_t)0, (size_t)n_out + 1, rocprim::plus<uint64_t>(), s));
+	if (al_prim_scan_u32_u64(c->scan_tmp, T.len.p, T.off.p, (size_t)n_out + 1, s)) return -1;
 	uint64_t bytes = 0;
 	AL_HIP_CHECK(hipMemcpyAsync(&bytes, T.off.p + n_out, 8, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));

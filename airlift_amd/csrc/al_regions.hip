@@ -2,23 +2,20 @@
 //
 //   k_reg_intervals  lane per token of the resident batch: the records the SAM writer would print, read where al_batch_run left them (out_off / out), each
 //                    appended as {group, contig rank, rs, re} to the device list; a wavefront reserves its slots with one atomic
-//   al_regions_fold  (merge sort)   the list by (group, rank, start, end): one rocPRIM merge sort of the 16-byte elements under al_reg_less
-//                    (scan)         segmented inclusive max-scan of `end` (al_reg_scan_op) -- the running maximum every later element is compared with
-//                    (scan)         exclusive sum of the head flags (al_reg_head): every element's region number, and their count
-//                    k_reg_compact  one element per region back to the front of the list: the head writes group, rank and start, the region's last
-//                                   element its running maximum
+//   AlRegions::fold  the list becomes its regions in place: the fold of al_fold.h under AlRegFold (merge sort, max-scan, head sum, k_fold_compact), plain rule;
+//                    k_fold_compact leaves the new count where k_reg_intervals adds to it
 //   k_reg_zero_group the groups of the per-gap regions set to 0: the merge across all gaps is the same fold once more
 // The list is folded whenever it holds more than AL_REG_FOLD_CAP intervals, and once at the end; only the regions are copied to the host.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
-#include <rocprim/rocprim.hpp>
 #include "al_internal.h"
 #include "al_device.h"
 #include "al_runtime.h"
 #include "al_stream.h"
 #include "al_dev_regions.h"
+#include "al_fold.h"
 
 __global__ void __launch_bounds__(256)
 k_reg_intervals(const uint64_t *__restrict__ out_off, const AlReg *__restrict__ out, uint32_t n_tok, uint32_t tok0, const uint32_t *__restrict__ g_first, const uint32_t *__restrict__ g_id, uint32_t n_g,
@@ -55,29 +52,6 @@ k_reg_intervals(const uint64_t *__restrict__ out_off, const AlReg *__restrict__ 
 	}
 }
 
-struct RegLess { __host__ __device__ bool operator()(const AlRegIv &a, const AlRegIv &b) const { return al_reg_less(a, b); } };
-struct RegScanOp { __host__ __device__ uint64_t operator()(uint64_t a, uint64_t b) const { return al_reg_scan_op(a, b); } };
-struct RegScanIn {             // element i of the max-scan's input
-	const AlRegIv *s;
-	__host__ __device__ uint64_t operator()(uint32_t i) const { return al_reg_scan_elem(i == 0 || !al_reg_same_seg(s[i - 1], s[i]), s[i].end); }
-};
-struct RegHeadIn {             // element i of the head sum's input (i == n: the sum's last element, the total)
-	const AlRegIv *s; const uint64_t *m; uint32_t n;
-	__host__ __device__ uint32_t operator()(uint32_t i) const { return i < n && al_reg_head(s, m, i) ? 1u : 0u; }
-};
-
-__global__ void __launch_bounds__(256)
-k_reg_compact(const AlRegIv *__restrict__ s, const uint64_t *__restrict__ m, const uint32_t *__restrict__ idx, uint32_t n, AlRegIv *__restrict__ list, unsigned long long *__restrict__ cnt)
-{
-	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-	if (i >= n) return;
-	const uint32_t k = idx[i], k_next = idx[i + 1];                      // idx[i + 1] - idx[i]: 1 when i is a head; idx[n] = the number of regions
-	const bool head = k_next != k, last = i + 1 == n || idx[i + 2] != k_next;
-	const uint32_t reg = head ? k : k - 1;                               // the region i belongs to
-	if (head) { const AlRegIv v = s[i]; list[reg].group = v.group; list[reg].rank = v.rank; list[reg].start = v.start; }
-	if (last) list[reg].end = (uint32_t)m[i];
-	if (i + 1 == n) cnt[0] = idx[n];
-}
 __global__ void __launch_bounds__(256)
 k_reg_zero_group(AlRegIv *__restrict__ list, uint32_t n)
 {
@@ -85,7 +59,7 @@ k_reg_zero_group(AlRegIv *__restrict__ list, uint32_t n)
 	if (i < n) list[i].group = 0;
 }
 
-#define REG_CHECK(x) do { const hipError_t e__ = (x); if (e__ != hipSuccess) { fprintf(stderr, "[airlift] regions: %s: %s\n", #x, hipGetErrorString(e__)); return -1; } } while (0)
+#define REG_CHECK(x) AL_HIP_CHECK_AS("regions", x)
 
 struct AlRegions {
 	int device = 0; bool no_print_2nd = true; uint32_t n_seq = 0, n_g = 0;
@@ -133,26 +107,13 @@ int AlRegions::fold()
 	auto nomem = [&]() { fprintf(stderr, "[airlift] regions: no device memory to fold %u intervals\n", m); return AL_ERR_NOMEM; };
 	if (sorted.ensure(m) || run_max.ensure(m) || idx.ensure((size_t)m + 1)) return nomem();
 	REG_CHECK(hipEventRecord(ev[0], s));
-	size_t bytes = 0;
-	REG_CHECK(rocprim::merge_sort(nullptr, bytes, list.p, sorted.p, (size_t)m, RegLess(), s));
-	if (tmp.ensure(bytes + 16)) return nomem();
-	REG_CHECK(rocprim::merge_sort(tmp.p, bytes, list.p, sorted.p, (size_t)m, RegLess(), s));
-	auto in_max = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), RegScanIn{sorted.p});
-	REG_CHECK(rocprim::inclusive_scan(nullptr, bytes, in_max, run_max.p, (size_t)m, RegScanOp(), s));
-	if (tmp.ensure(bytes + 16)) return nomem();
-	REG_CHECK(rocprim::inclusive_scan(tmp.p, bytes, in_max, run_max.p, (size_t)m, RegScanOp(), s));
-	auto in_head = rocprim::make_transform_iterator(rocprim::make_counting_iterator<uint32_t>(0u), RegHeadIn{sorted.p, run_max.p, m});
-	REG_CHECK(rocprim::exclusive_scan(nullptr, bytes, in_head, idx.p, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), s));
-	if (tmp.ensure(bytes + 16)) return nomem();
-	REG_CHECK(rocprim::exclusive_scan(tmp.p, bytes, in_head, idx.p, 0u, (size_t)m + 1, rocprim::plus<uint32_t>(), s));
-	hipLaunchKernelGGL(k_reg_compact, dim3((m + 255) / 256), dim3(256), 0, s, (const AlRegIv *)sorted.p, (const uint64_t *)run_max.p, (const uint32_t *)idx.p, m, list.p, cnt.p);
-	REG_CHECK(hipGetLastError());
+	int r = al_fold_enqueue<AlRegFold>("regions", list.p, m, m, false, list.p, cnt.p, sorted.p, run_max.p, idx.p, tmp, s);
+	if (r) return r == AL_ERR_NOMEM ? nomem() : r;
 	REG_CHECK(hipEventRecord(ev[1], s));
-	unsigned long long h = 0;
-	REG_CHECK(hipMemcpy(&h, cnt.p, 8, hipMemcpyDeviceToHost));
+	uint32_t h = 0;
+	if ((r = al_fold_count("regions", idx.p, m, s, &h)) != 0) return r;
 	float ms = 0; REG_CHECK(hipEventElapsedTime(&ms, ev[0], ev[1]));
-	st.ms_fold += ms; ++st.n_fold; st.bytes_d2h += 8;
-	if (h == 0 || h > n) { fprintf(stderr, "[airlift] regions: the fold of %u intervals left %llu\n", m, h); return -1; }
+	st.ms_fold += ms; ++st.n_fold; st.bytes_d2h += 4;
 	n = h;
 	return 0;
 }

@@ -5,13 +5,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include "al_internal.h"
 #include "al_device.h"
 #include <mutex>
 #include <vector>
 #include "al_runtime.h"
+#include "al_prim.h"
 #include "al_dev_sort.h"
 #include "al_io.h"
 
@@ -295,17 +295,10 @@ extern "C" int al_batch_upload(al_ctx_t *c, int n_frag, const int *n_segs, const
 }
 
 // ---------------------------------------------------------------------------------------------
-struct CastU64 { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
-
 static int scan_u32_to_u64(al_ctx_t *c, const uint32_t *in, uint64_t *out, int n, hipStream_t st = nullptr, DevBuf<unsigned char> *tmp = nullptr)
 {
-	hipStream_t s_ = st ? st : c->stream; DevBuf<unsigned char> &T_ = tmp ? *tmp : c->scan_tmp;   // out[0..n] = exclusive prefix sums (n+1 entries; in[n] must be readable: callers pad with 0)
-	auto it = rocprim::make_transform_iterator((const uint32_t *)in, CastU64());
-	size_t bytes = 0;
-	AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, it, out, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), s_));
-	if (T_.ensure(bytes + 16)) return -1;
-	AL_HIP_CHECK(rocprim::exclusive_scan(T_.p, bytes, it, out, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), s_));
-	return 0;
+	// out[0..n] = exclusive prefix sums (n+1 entries; in[n] must be readable: callers pad with 0)
+	return al_prim_scan_u32_u64(tmp ? *tmp : c->scan_tmp, in, out, (size_t)(n + 1), st ? st : c->stream) ? -1 : 0;
 }
 
 struct SizeThr { uint32_t v[28]; int n; };
@@ -358,10 +351,7 @@ static int lower_bounds(al_ctx_t *c, const uint32_t *keys, uint32_t n, const uin
 }
 static int sort_u32_pairs(al_ctx_t *c, const uint32_t *k_in, uint32_t *k_out, const uint32_t *v_in, uint32_t *v_out, int n)
 {
-	size_t bytes = 0;
-	AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, k_in, k_out, v_in, v_out, n, 0, 32, c->stream));
-	if (c->scan_tmp.ensure(bytes + 16)) return -1;
-	AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, k_in, k_out, v_in, v_out, n, 0, 32, c->stream));
+	if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, k_in, k_out, v_in, v_out, n, 0, 32, c->stream); })) return -1;
 	return 0;
 }
 
@@ -420,10 +410,7 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 	uint32_t lb[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                // starts of classes 2 .. 9 in the class-ordered list of the n1 others
 	if (n1 > 0) {
 		{   // stable sort by size class only (4 bits: one radix pass)
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, n1, 0, 4, s));
-			if (c->scan_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, n1, 0, 4, s));
+			if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, n1, 0, 4, s); })) return -1;
 		}
 		static const uint32_t thr[8] = {2, 3, 4, 5, 6, 7, 8, 9};
 		if (lower_bounds(c, c->seg_key.p, (uint32_t)n1, thr, 8, lb)) return -1;
@@ -589,10 +576,7 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 			// the deferred segments by size class (stable: inside a class they keep the tiles' order, i.e. memory order inside a tile)
 			if (c->seg_key.ensure((size_t)n_def + 1) || c->seg_ord.ensure((size_t)n_def + 1) || c->seg_t1.ensure((size_t)n_def + 1)) return -1;
 			hipLaunchKernelGGL(k_iota_u32, dim3((n_def + 255) / 256), dim3(256), 0, s, c->seg_t1.p, n_def);
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, (int)n_def, 0, 4, s));
-			if (c->scan_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, (int)n_def, 0, 4, s));
+			if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, (int)n_def, 0, 4, s); })) return -1;
 			static const uint32_t thr[8] = {1, 2, 3, 4, 5, 6, 7, 8};
 			uint32_t lb[8];
 			if (lower_bounds(c, c->seg_key.p, n_def, thr, 8, lb)) return -1;
@@ -649,11 +633,8 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 	if (n_fb > 0) {
 		c->n_chain_fallback += n_fb; c->chain_who[CW_HANDED_BACK] += n_fb;
 		// (the list the kernels appended to atomically, in ascending fragment order: the same virtual batch on every run)
-		size_t bytes = 0;
 		if (c->fbk_list.ensure((size_t)n_fb + 2)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const uint32_t *)c->fb_list.p, c->fbk_list.p, (int)n_fb, 0, 32, s));
-		if (c->scan_tmp.ensure(bytes + 16)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_keys(c->scan_tmp.p, bytes, (const uint32_t *)c->fb_list.p, c->fbk_list.p, (int)n_fb, 0, 32, s));
+		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->fb_list.p, c->fbk_list.p, (int)n_fb, 0, 32, s); })) return -1;
 		if (chain_fallback(c, c->fbk_list.p, (int)n_fb, lds_ok)) return -1;
 	}
 	if (ev(ST_SEG_CHAIN_WAVE)) return -1;
@@ -698,10 +679,7 @@ static int chain_plan(al_ctx_t *c, const uint32_t *list, int nl, bool first, Cha
 		for (int i = 0; i < 28; ++i) ST.v[i] = i < ST.n ? T[i] : 0xffffffffu;
 		if (c->chain_cls.ensure((size_t)nl + 1)) return -1;
 		hipLaunchKernelGGL(k_size_class, dim3((nl + 255) / 256), dim3(256), 0, s, first ? (const uint32_t *)c->frag_na.p : (const uint32_t *)c->tmp_u32.p, nl, ST, c->chain_cls.p);
-		size_t bytes = 0;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
-		if (c->scan_tmp.ensure(bytes + 16)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_pairs(c->scan_tmp.p, bytes, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s));
+		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->chain_cls.p, c->chain_key.p, first ? (const uint32_t *)c->chain_idx.p : list, c->chain_idx2.p, nl, 0, 5, s); })) return -1;
 		uint32_t thr_cls[15];                                                 // count >= thr[k]  <=>  class >= (rank of thr[k] among the thresholds) + 1
 		for (int k = 0; k < 15; ++k) thr_cls[k] = (uint32_t)(std::lower_bound(T.begin(), T.end(), thr[k]) - T.begin()) + 1u;
 		if (lower_bounds(c, c->chain_key.p, (uint32_t)nl, thr_cls, 15, lb)) return -1;
@@ -819,11 +797,8 @@ static int chain_ties(al_ctx_t *c, const ChainPlan &pl)
 	if (!first && c->n_spec > 0) c->spec_idle = n_spec_used ? 0u : c->spec_idle + 1u;
 	c->chain_who[CW_TIE_ROUND] += n_tie;
 	if (n_tie > 0) {
-		size_t bytes = 0;    // ascending fragment ids: a deterministic order (the collection above appends atomically)
 		if (c->tie_sorted.ensure((size_t)n_tie + 2)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
-		if (c->scan_tmp.ensure(bytes + 16)) return -1;
-		AL_HIP_CHECK(rocprim::radix_sort_keys(c->scan_tmp.p, bytes, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s));
+		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s); })) return -1;   // ascending fragment ids: a deterministic order (the collection above appends atomically)
 		if (tiles_ok) {
 			TileSched S; for (int k = 0; k < 6; ++k) { S.ent[k] = 0; S.item[k] = 0; } S.ent[6] = n_tie; S.item[6] = n_tie; S.n_items = n_tie;   // a fragment per item, any size
 			if (chain_tiles(c, c->tie_sorted.p, S, nullptr, lmin, false, lds_ok)) return -1;
@@ -979,10 +954,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 			int rbits = 0; while ((1ULL << rbits) < nb) ++rbits;
 			rocprim::double_buffer<uint64_t> dk(ka, kbuf);
 			const unsigned end_bit = (unsigned)(16 + 1 + rid_bits + pos_bits + rbits);
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, dk, (size_t)nbig, 16u, end_bit, sb));
-			if (c->big_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::radix_sort_keys(c->big_tmp.p, bytes, dk, (size_t)nbig, 16u, end_bit, sb));
+			if (al_prim_run(c->big_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, dk, (size_t)nbig, 16u, end_bit, sb); })) return -1;
 			hipLaunchKernelGGL(k_anchor_big_scatter, dim3(nb), dim3(256), 0, sb, dk.current(), order + b0, (int)nb, c->big_off.p, c->a_off.p,
 			                   c->mini_off.p, c->frag_first.p, c->rd_len.p, c->match.p, c->frag_nm.p, c->anchors.p, c->tie_list.p, rid_bits, pos_bits, c->mi->k);
 			b0 += nb;
@@ -1110,11 +1082,8 @@ int al_run_seed_stages(al_ctx_t *c)
 			// fragment order first -- that also makes the second-pass layout the same on every run -- and start the second pass
 			// n_frag slots further so that its u[] entries cannot land on those of the last first-pass fragments.
 			{
-				size_t bytes = 0;
 				if (c->rechain_sorted.ensure(n + 1)) return -1;
-				AL_HIP_CHECK(rocprim::radix_sort_keys(nullptr, bytes, (const uint32_t *)c->rechain_list.p, c->rechain_sorted.p, (int)n, 0, 32, s));
-				if (c->scan_tmp.ensure(bytes + 16)) return -1;
-				AL_HIP_CHECK(rocprim::radix_sort_keys(c->scan_tmp.p, bytes, (const uint32_t *)c->rechain_list.p, c->rechain_sorted.p, (int)n, 0, 32, s));
+				if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->rechain_list.p, c->rechain_sorted.p, (int)n, 0, 32, s); })) return -1;
 			}
 			if (run_seed_chain(c, c->rechain_sorted.p, (int)n, c->opt.max_occ, c->n_anchor_pass1 + (uint64_t)c->n_frag, false)) return -1;
 		}

@@ -50,7 +50,7 @@ k_fq_gather(const uint8_t *__restrict__ t, const AlFqRec *__restrict__ rec, uint
 
 namespace {
 
-#define SEL_CHECK(x) do { const hipError_t e__ = (x); if (e__ != hipSuccess) { fprintf(stderr, "[airlift] --gpu-select: %s: %s\n", #x, hipGetErrorString(e__)); return -1; } } while (0)
+#define SEL_CHECK(x) AL_HIP_CHECK_AS("--gpu-select", x)
 
 struct AlSelDevBackend : AlSelBackend {
 	int device = 0; bool open_ok = false, bgzf = false;

@@ -15,13 +15,13 @@
 #include <stdlib.h>
 #include <string.h>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 #include <algorithm>
 #include <vector>
 #include <string>
 #include "al_internal.h"
 #include "al_device.h"
 #include "al_runtime.h"
+#include "al_prim.h"
 #include "al_io.h"
 #include "al_stream.h"
 #include "al_dev_inflate.h"
@@ -470,15 +470,9 @@ k_paf_write(SamIn I, const uint64_t *__restrict__ sam_off, char *__restrict__ sa
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-struct CastU64s { __host__ __device__ uint64_t operator()(const uint32_t &v) const { return (uint64_t)v; } };
 int al_stream_scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s)
 {   // out[0 .. n) = exclusive prefix sums of in[0 .. n)
-	auto it = rocprim::make_transform_iterator(in, CastU64s());
-	size_t bytes = 0;
-	AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-	if (S.scan_tmp.ensure(bytes + 16)) return -1;
-	AL_HIP_CHECK(rocprim::exclusive_scan(S.scan_tmp.p, bytes, it, out, (uint64_t)0, n, rocprim::plus<uint64_t>(), s));
-	return 0;
+	return al_prim_scan_u32_u64(S.scan_tmp, in, out, n, s) ? -1 : 0;
 }
 static int scan_excl_u64(AlStreamSlot &S, const uint32_t *in, uint64_t *out, size_t n, hipStream_t s) { return al_stream_scan_excl_u64(S, in, out, n, s); }
 
@@ -677,15 +671,9 @@ int al_stream_parse(AlStreamSlot &S, const bool *eof, int max_reads, AlIngestRes
 		if (n > 0) {
 			if (S.se_key.ensure(n + 2) || S.se_run.ensure(n + 2) || S.se_fs.ensure(n + 2) || S.se_fidx.ensure(n + 2)) return -1;
 			hipLaunchKernelGGL(k_se_same, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, S.txt[0].p, S.frec[0].p, (uint32_t)n, S.se_key.p);
-			size_t bytes = 0;
-			AL_HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, S.se_key.p, S.se_run.p, n, rocprim::maximum<uint32_t>(), s));
-			if (S.scan_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::inclusive_scan(S.scan_tmp.p, bytes, S.se_key.p, S.se_run.p, n, rocprim::maximum<uint32_t>(), s));
+			if (al_prim_run(S.scan_tmp, [&](void *t, size_t &b) { return rocprim::inclusive_scan(t, b, S.se_key.p, S.se_run.p, n, rocprim::maximum<uint32_t>(), s); })) return -1;
 			hipLaunchKernelGGL(k_se_flag, dim3((unsigned)((n + 256) / 256)), dim3(256), 0, s, S.se_run.p, (uint32_t)n, S.se_fs.p);
-			bytes = 0;
-			AL_HIP_CHECK(rocprim::exclusive_scan(nullptr, bytes, S.se_fs.p, S.se_fidx.p, 0u, n + 1, rocprim::plus<uint32_t>(), s));
-			if (S.scan_tmp.ensure(bytes + 16)) return -1;
-			AL_HIP_CHECK(rocprim::exclusive_scan(S.scan_tmp.p, bytes, S.se_fs.p, S.se_fidx.p, 0u, n + 1, rocprim::plus<uint32_t>(), s));
+			if (al_prim_run(S.scan_tmp, [&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, S.se_fs.p, S.se_fidx.p, 0u, n + 1, rocprim::plus<uint32_t>(), s); })) return -1;
 			uint32_t last_fs = 0, nfr = 0;
 			AL_HIP_CHECK(hipMemcpyAsync(&last_fs, S.se_fs.p + (n - 1), 4, hipMemcpyDeviceToHost, s));
 			AL_HIP_CHECK(hipMemcpyAsync(&nfr, S.se_fidx.p + n, 4, hipMemcpyDeviceToHost, s));

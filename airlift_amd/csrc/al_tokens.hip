@@ -31,7 +31,7 @@ k_tok_setup(AlTokTab T, uint64_t t0, uint32_t n_tok, int R, int S, int seed, uin
 	O.start[i] = start; O.frag_hash[i] = hash;
 }
 
-#define TOK_CHECK(x) do { const hipError_t e__ = (x); if (e__ != hipSuccess) { fprintf(stderr, "[airlift] tokens: %s: %s\n", #x, hipGetErrorString(e__)); return -1; } } while (0)
+#define TOK_CHECK(x) AL_HIP_CHECK_AS("tokens", x)
 
 struct AlTokDev {
 	int device = 0; uint32_t n_rows = 0; uint64_t n_tok = 0;
