@@ -179,6 +179,8 @@ def load():
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci
     if hasattr(L, "al_dbg_chain"):
         L.al_dbg_chain.argtypes = [vp] * 9; L.al_dbg_chain.restype = ci
+    if hasattr(L, "al_dbg_seed"):
+        L.al_dbg_seed.argtypes = [vp, vp, ci, vp]; L.al_dbg_seed.restype = ci
     L.al_version.restype = cs
     L.al_gen_cs.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs, ci]; L.al_gen_cs.restype = ci
     L.al_gen_MD.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(ci), vp, C.POINTER(Reg), cs]; L.al_gen_MD.restype = ci
@@ -357,6 +359,28 @@ class Context:
         if rc != 0:
             raise AirliftError("al_dbg_chain failed: %d" % rc)
         return nu, u, uo, ch[:tot], dict(zip(self.CHAIN_COUNTS, (int(x) for x in cnt)))
+
+    SEED_COUNTS = ("small", "reg_2_1_128", "reg_4_1_256", "reg_8_1_512", "reg_16_1_512", "reg_8_4_1024", "reg_16_4_1024", "reg_16_8_1024", "sort1024", "merge_frags", "merge_tiles", "merge_passes",
+                   "radix_frags", "radix_chunks", "flag_all", "compact", "rid_bits", "pos_bits", "rank_bits", "nl", "lb65", "lb129", "lb257", "lb513", "lb1025", "lb2049", "lb4097", "lb_big",
+                   "heap_merges", "spec_made", "spec_taken", "flagged", "heap_lanes2", "heap_lanes1", "heap_serial0", "heap_wave", "heap_serial48", "heap_serial96", "sketch_form", "sketch_pb")
+
+    def seed(self, second=None):
+        """al_dbg_seed: the seed stage of the uploaded batch without the chaining: the first pass, and with `second` (ascending fragment ids) the
+        re-chain pass of those fragments with max_occ.  Returns one dict per pass: frag_na, frag_nm, frag_rep, a_off, flags (the pass's tie_list
+        word per fragment), anchors ((n, 2) uint64, all of the batch so far; fragment f's lie at a_off[f]), counts by name (heap_merges: of this pass)."""
+        L = load(); nf = self.n_frag; out = []
+        for lst in ([None] if second is None else [None, np.ascontiguousarray(second, dtype=np.uint32)]):
+            cnt = np.zeros(40, dtype=np.uint64)
+            rc = L.al_dbg_seed(self.h, None if lst is None else lst.ctypes.data_as(C.c_void_p), 0 if lst is None else len(lst), cnt.ctypes.data_as(C.c_void_p))
+            if rc != 0:
+                raise AirliftError("al_dbg_seed failed: %d" % rc)
+            d = dict(zip(self.SEED_COUNTS, (int(x) for x in cnt)))
+            d["rank_bits"] -= 64; d["sketch_pb"] -= 64
+            a_off = self.tap("a_off", np.uint64, nf + 1).copy(); na = self.tap("frag_na", np.uint32, nf).copy()
+            tot = int((a_off[:nf].astype(np.int64) + na).max()) if nf else 0
+            out.append({"frag_na": na, "frag_nm": self.tap("frag_nm", np.uint32, nf).copy(), "frag_rep": self.tap("frag_rep", np.int32, nf).copy(), "a_off": a_off,
+                        "flags": self.tap("tie_list", np.uint32, nf).copy(), "anchors": self.tap("anchors", np.uint64, tot * 2).reshape(-1, 2).copy(), "counts": d})
+        return out
 
     def alser_count(self):
         v = C.c_int64()

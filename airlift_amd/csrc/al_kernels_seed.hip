@@ -1,8 +1,17 @@
 // al_kernels_seed.hip -- CDNA4 (gfx950) kernels K1..K4 of the re-alignment path:
 //   K1 k_sketch       minimizer sketch, one lane per read            (mm_sketch, sketch.c:77-143)
 //   K2 k_seed         hash probes + occurrence filter, lane/fragment  (collect_matches, map.c:90-123; mm_idx_get, index.c:81-98)
-//   K3 k_anchor_sort_small / k_anchor_sort / k_anchor_heap   anchor expansion + x-sort, wave/fragment; exact heap merge of
-//                     equal-key fragments, lane/fragment          (collect_seed_hits_heap, map.c:149-213)
+//   K3 anchor expansion + x-sort by size class, then the exact heap merge of the fragments with equal x (collect_seed_hits_heap, map.c:149-213):
+//        k_anchor_sort_small                          up to 64 anchors, a wavefront per fragment (rank sort)
+//        k_anchor_sort_reg<PER, NW, MCAP>             65 ... 8192 anchors, register network on compact 64-bit keys (seven instantiations)
+//        k_anchor_sort<1024>                          65 ... 1024 anchors when the keys are not compact (more than 32 768 contigs), bitonic sort in LDS
+//        k_anchor_run_sort / _run_cuts / _run_merge   above 8192 anchors: runs sorted by the register network, merged pairwise (k_big_tiles, k_big_tile_ent lay them out)
+//        k_anchor_big_expand / _big_scatter           ... or the device-wide radix sort of composite keys (AL_BIG_MERGE=0; always when the keys are not compact)
+//        k_anchor_heap_lanes<1|2, 16>                 flagged fragments of up to 63 / 126 lists: the heap in the lanes of a wavefront
+//        k_anchor_heap<0|48|96, LANES>                more lists, and every class behind AL_HEAP_OLD=1: serial heap per lane, in LDS or HBM scratch
+//        k_anchor_heap_wave<128, 32>                  behind AL_HEAP_OLD=1: a wavefront per large fragment of up to 128 lists
+//        k_spec_count / _pick / _layout / _mark / _apply   merges of giant re-seeded fragments made ahead of the re-chain pass
+//        k_collect_flagged_blk                        the merge kernels' list (k_size_class, k_flag_list, k_gather_na, k_scatter_off of al_runtime.hip: classes and offsets)
 //   K4 k_chain_lds    chaining DP + backtrack, lane/fragment, rows in LDS; k_chain: wave/fragment for > 128 anchors
 //                                                                  (mm_chain_dp, chain.c:22-162)
 // Integer / byte work, HBM- and latency-bound: no MFMA.  64-wide wavefronts throughout.
@@ -685,7 +694,8 @@ template __global__ void k_anchor_heap_wave<128, 32>(const uint64_t *, const uin
 // ks_heapmake is the same step from the nodes n/2 .. 1.  Occurrence lists: list l belongs to the lane of node l + 1; its next
 // position waits in a register of that lane, the RING positions behind it in that lane's LDS ring, refilled from HBM by all lanes
 // together when the list about to advance has run dry.  Up to 63 (NSET 1) / 126 (NSET 2) lists; larger fragments keep the serial form.
-// Checked against the serial emulation by a model of these steps (tests/test_heap_lanes_model.py) and by the tie-order goldens.
+// Checked against a host restatement of ks_heapmake / ks_heapdown by the harness tests/csrc/heap_lanes_test.hip (tests/test_gpu_heap_lanes.py), against the
+// reference's collect_seed_hits_heap on directed tied fragments (tests/test_gpu_seed_directed.py) and by the tie-order goldens.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ uint32_t d_sel_mask(uint64_t mask, uint32_t if_set, uint32_t if_clear)
 {   // per lane: bit `lane` of a wave-uniform mask picks (one v_cndmask with the mask as its SGPR-pair condition)

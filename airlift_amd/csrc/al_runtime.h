@@ -38,6 +38,7 @@ struct AlRegOut {            // per-read result header copied back to the host
 };
 
 #define AL_CHAIN_WHO_N 16                  // counters of al_ctx_s::chain_who (al_runtime.hip: CW_*)
+#define AL_SEED_WHO_N 32                   // counters of al_ctx_s::seed_who (al_runtime.hip: SW_*)
 struct al_ctx_s {
 	const al_idx_t *mi = nullptr;
 	al_mapopt_t opt;
@@ -99,6 +100,9 @@ struct al_ctx_s {
 	DevBuf<uint32_t> seg_cnt, seg_cnt0, seg_t1, vs_na, vs_meta, vs_cls, seg_key, seg_idx, seg_ord, fb_list, fb2_list, fb3_list, big_na, big_nt, big_tent, big_cuts, tie_frags, tie_sorted, heap_cnt;
 	uint64_t n_chain_fallback = 0;
 	uint64_t chain_who[AL_CHAIN_WHO_N] = {};          // which chaining kernels took how much of the last pass (al_runtime.hip: CW_*), for the al_dbg_chain tap
+	DevBuf<unsigned long long> seed_cnt;                 // the al_dbg_seed tap: a count per heap-merge launch of the pass (al_runtime.hip: HF_*), in the place of counters[0]
+	uint64_t seed_who[AL_SEED_WHO_N] = {};            // which anchor-sort kernels took how many fragments of the last pass (al_runtime.hip: SW_*), for the al_dbg_seed tap
+	bool seed_tap_pass1 = false;                      // al_dbg_seed ran the first pass on the resident batch: its second pass may follow
 	int max_qlen_sum = 0;                 // longest fragment of the resident batch
 	int max_rd_len = 0;                   // longest read of the resident batch
 	bool attr_chain_order = false, attr_regs_heavy = false;   // > 64 KB dynamic-LDS opt-in of two kernels: per device (hipFuncSetAttribute acts on the current device), kept per context

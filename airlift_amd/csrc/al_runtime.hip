@@ -186,7 +186,7 @@ static void ctx_release_buffers(al_ctx_t *c)
 	al_align_state_free(c);
 	for (int p = 1; p < c->n_phys; ++p) if (c->phys[p]) (void)hipStreamSynchronize(c->phys[p]);
 	c->spec_busy = false; c->spec_pending = false; c->n_spec = 0;
-	c->spec_match.release(); c->spec_meta.release(); c->spec_cnt.release(); c->spec_use.release(); c->spec_v32.release(); c->spec_v64.release(); c->spec_anchors.release(); c->spec_na2.release();
+	c->spec_match.release(); c->spec_meta.release(); c->spec_cnt.release(); c->spec_use.release(); c->spec_v32.release(); c->spec_v64.release(); c->spec_anchors.release(); c->spec_na2.release(); c->seed_cnt.release();
 	if (c->stream) (void)hipStreamSynchronize(c->stream);
 	c->rd_seq.release(); c->rd_len.release(); c->frag_first.release(); c->frag_hash.release(); c->mini_cnt.release(); c->frag_nm.release(); c->frag_na.release();
 	c->frag_nu.release(); c->rechain_list.release(); c->rechain_sorted.release(); c->tmp_u32.release(); c->rd_off.release(); c->mini_off.release(); c->a_off.release(); c->u.release();
@@ -239,7 +239,7 @@ extern "C" int al_batch_upload(al_ctx_t *c, int n_frag, const int *n_segs, const
 	const unsigned char *nt4 = al_nt4();
 	int n_reads = 0;
 	for (int f = 0; f < n_frag; ++f) { if (n_segs[f] < 1 || n_segs[f] > 2) { fprintf(stderr, "[airlift] fragments must have 1 or 2 segments\n"); return -2; } n_reads += n_segs[f]; }
-	c->n_frag = n_frag; c->n_reads = n_reads; c->ran = false;
+	c->n_frag = n_frag; c->n_reads = n_reads; c->ran = false; c->seed_tap_pass1 = false;
 	c->h_rd_len.resize(n_reads + 1); c->h_rd_off.resize(n_reads + 1); c->h_mini_off.resize(n_reads + 1); c->h_flip.assign(n_reads, 0);
 	c->h_frag_first.resize(n_frag + 1); c->h_frag_hash.resize(n_frag + 1);
 	uint64_t words = 0, mtot = 0, bases = 0; int r = 0, max_qsum = 0;
@@ -359,6 +359,12 @@ static int sort_u32_pairs(al_ctx_t *c, const uint32_t *k_in, uint32_t *k_out, co
 enum { CW_LANE_LO, CW_LANE_MID, CW_WAVE_MID, CW_TILE_ITEMS, CW_TILE_FRAGS, CW_HANDED_BACK, CW_DEFERRED, CW_DEFERRED_COOP, CW_COMPACTED, CW_LEGACY_FRAGS, CW_WAVE_SEGS, CW_ORDER_FRAGS,
        CW_WHOLE_WAVE, CW_TIE_ROUND, CW_SEG_BIG, CW_FALLBACK_FRAGS, CW_N };
 static_assert(CW_N <= AL_CHAIN_WHO_N, "al_ctx_t::chain_who holds a counter per CW_* name");
+// ... and which anchor-sort kernels got how many fragments of a pass (run_seed_chain; al_dbg_seed reports them).  SW_REG0 + i: the seven
+// k_anchor_sort_reg instantiations in the order <2,1,128> <4,1,256> <8,1,512> <16,1,512> <8,4,1024> <16,4,1024> <16,8,1024>
+enum { SW_SMALL, SW_REG0, SW_SORT1024 = SW_REG0 + 7, SW_MERGE_FRAGS, SW_MERGE_TILES, SW_MERGE_PASSES, SW_RADIX_FRAGS, SW_RADIX_CHUNKS, SW_FLAG_ALL, SW_COMPACT, SW_RID_BITS, SW_POS_BITS, SW_RANK_BITS /* + 64 */,
+       SW_NL, SW_LB65, SW_LB129, SW_LB257, SW_LB513, SW_LB1025, SW_LB2049, SW_LB4097, SW_LB_BIG, SW_N };
+enum { HF_LANES2, HF_LANES1, HF_HEAP0, HF_WAVE, HF_HEAP48, HF_HEAP96, HF_N };   // the heap-merge launches: k_anchor_heap_lanes<2|1>, k_anchor_heap<0>, k_anchor_heap_wave, k_anchor_heap<48|96>
+static_assert(SW_N <= AL_SEED_WHO_N, "al_ctx_t::seed_who holds a counter per SW_* name");
 
 #define LCH(C, L, LO, AOFF, NA, CH, UO, NU, LIST, N, SEG, UOFF, WS, STRIDE) do { const int n__ = (N); if (n__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_lds<C, L>), dim3((n__ + L - 1) / L), dim3(64), 0, s, c->anchors.p, AOFF, NA, c->frag_first.p, c->rd_len.p, CH, UO, NU, WS, LIST, n__, LO, c->P, c->counters.p, SEG, UOFF, STRIDE); } while (0)
 
@@ -808,8 +814,11 @@ static int chain_ties(al_ctx_t *c, const ChainPlan &pl)
 	return 0;
 }
 
-static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max_occ, uint64_t base_off, bool first)
+// chain == false (the al_dbg_seed tap): seeding, anchor collection and the sorts and merges only -- the same launches on the same streams in the same order,
+// with the event waits that join the side streams, without chain_small / chain_large / chain_ties
+static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max_occ, uint64_t base_off, bool first, bool chain = true)
 {
+	for (int i = 0; i < SW_N; ++i) c->seed_who[i] = 0;
 	hipStream_t s = c->stream;
 	const int nl = n_list;
 	if (nl == 0) return 0;
@@ -899,7 +908,11 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		const char *const e3 = al_env().test_big_chunk;                // tests: fragments per device-wide sort
 		uint32_t chunk_max = rank_bits >= 31 ? 0x7fffffffu : rank_bits >= 1 ? (1u << rank_bits) : 1u;
 		if (e3 && atoi(e3) > 0) chunk_max = std::min<uint32_t>(chunk_max, (uint32_t)atoi(e3));
+		uint64_t *const sw = c->seed_who;
+		sw[SW_RID_BITS] = (uint64_t)rid_bits; sw[SW_POS_BITS] = (uint64_t)pos_bits; sw[SW_RANK_BITS] = (uint64_t)(rank_bits + 64); sw[SW_NL] = (uint64_t)nl;
+		sw[SW_LB65] = lb65; sw[SW_LB129] = lb129; sw[SW_LB257] = lb257; sw[SW_LB513] = lb513; sw[SW_LB1025] = lb1025; sw[SW_LB2049] = lb2049; sw[SW_LB4097] = lb4097; sw[SW_LB_BIG] = lb_big;
 		if (rank_bits < 0 && lb_big < (uint32_t)nl) {                       // (no such index in practice: > 2^46 contig-id x position range) exact merge for all of them
+			sw[SW_FLAG_ALL] += (uint32_t)nl - lb_big;
 			hipLaunchKernelGGL(k_flag_list, dim3(((uint32_t)nl - lb_big + 255) / 256), dim3(256), 0, sb, order + lb_big, (int)((uint32_t)nl - lb_big), c->tie_list.p);
 		}
 		// (round 5) runs of 8192 anchors sorted by the register network, then merged pairwise (k_anchor_run_sort / k_anchor_run_merge): one to six passes of 8 bytes
@@ -930,6 +943,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 			hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_run_sort<16, 8, 1024>), dim3(nt32), dim3(512), 0, sb, c->di.pos, c->frag_first.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
 			                   order + lb_big, (int)nb, (const uint64_t *)c->big_toff.p, (const uint32_t *)c->big_tent.p, (const uint64_t *)c->big_off.p, c->big_k0.p, c->tie_list.p, rid_bits, run_len, tile);
 			int n_pass = 1; while (((uint64_t)run_len << n_pass) < mx) ++n_pass;
+			sw[SW_MERGE_FRAGS] += nb; sw[SW_MERGE_TILES] += nt32; sw[SW_MERGE_PASSES] += (uint64_t)n_pass;
 			const RunMergeOut O{c->a_off.p, c->mini_off.p, c->frag_first.p, c->rd_len.p, c->match.p, c->anchors.p, c->tie_list.p, rid_bits, c->mi->k};
 			for (int p = 0; p < n_pass; ++p) {
 				const uint64_t *kin = (p & 1) ? c->big_k1.p : c->big_k0.p; uint64_t *kout = (p & 1) ? c->big_k0.p : c->big_k1.p;
@@ -957,28 +971,30 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 			if (al_prim_run(c->big_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, dk, (size_t)nbig, 16u, end_bit, sb); })) return -1;
 			hipLaunchKernelGGL(k_anchor_big_scatter, dim3(nb), dim3(256), 0, sb, dk.current(), order + b0, (int)nb, c->big_off.p, c->a_off.p,
 			                   c->mini_off.p, c->frag_first.p, c->rd_len.p, c->match.p, c->frag_nm.p, c->anchors.p, c->tie_list.p, rid_bits, pos_bits, c->mi->k);
-			b0 += nb;
+			b0 += nb; sw[SW_RADIX_FRAGS] += nb; ++sw[SW_RADIX_CHUNKS];
 		}
 		AL_HIP_CHECK(hipEventRecord(c->ev_ovl[1], sb));
 		if (lb65 > 0) hipLaunchKernelGGL(k_anchor_sort_small, dim3(lb65), dim3(64), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
 		                                 c->a_off.p, c->anchors.p, c->tie_list.p, tie_cnt, order, (int)lb65, c->counters.p, c->mi->k);
+		sw[SW_SMALL] += lb65;
 		if (ev(ST_ANCHOR_SORT_S)) return -1;
 		const bool compact = 33 + rid_bits + 16 <= 64;                   // strand | contig | position | list in one 64-bit key
-#define LREG(P, W, M, A, B) do { if ((B) > (A)) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_sort_reg<P, W, M>), dim3((B) - (A)), dim3(64 * W), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
-		                                        c->a_off.p, c->anchors.p, c->tie_list.p, order + (A), (int)((B) - (A)), c->mi->k, rid_bits); } while (0)
-		if (compact) { LREG(2, 1, 128, lb65, std::min(lb129, lb1025)); LREG(4, 1, 256, lb129, lb257); LREG(8, 1, 512, lb257, lb513); LREG(16, 1, 512, lb513, lb1025); }
-		else if (lb1025 > lb65) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_sort<1024>), dim3(lb1025 - lb65), dim3(64), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
-		                                           c->a_off.p, c->anchors.p, c->tie_list.p, tie_cnt, order + lb65, (int)(lb1025 - lb65), c->counters.p, c->mi->k);
+#define LREG(I, P, W, M, A, B) do { if ((B) > (A)) { sw[SW_REG0 + (I)] += (B) - (A); hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_sort_reg<P, W, M>), dim3((B) - (A)), dim3(64 * W), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
+		                                        c->a_off.p, c->anchors.p, c->tie_list.p, order + (A), (int)((B) - (A)), c->mi->k, rid_bits); } } while (0)
+		sw[SW_COMPACT] = compact ? 1 : 0;
+		if (compact) { LREG(0, 2, 1, 128, lb65, std::min(lb129, lb1025)); LREG(1, 4, 1, 256, lb129, lb257); LREG(2, 8, 1, 512, lb257, lb513); LREG(3, 16, 1, 512, lb513, lb1025); }
+		else if (lb1025 > lb65) { sw[SW_SORT1024] += lb1025 - lb65; hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_sort<1024>), dim3(lb1025 - lb65), dim3(64), 0, s, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
+		                                           c->a_off.p, c->anchors.p, c->tie_list.p, tie_cnt, order + lb65, (int)(lb1025 - lb65), c->counters.p, c->mi->k); }
 		if (ev(ST_ANCHOR_SORT)) return -1;
 		// fragments of up to 128 anchors are in order: their chaining (ovl1, below) may start -- unless a test lowered the block sorts' bound
 		// below 129 anchors (AL_TEST_SORT_BLK): then some of them are sorted by the block kernels below, and the event follows those
 		const bool small_by_blk = lb1025 < lb129;
 		if (!small_by_blk) AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));
-		LREG(8, 4, 1024, lb1025, lb2049); LREG(16, 4, 1024, lb2049, lb4097); LREG(16, 8, 1024, lb4097, lb_big);   // (non-compact keys: t_big == t_blk, empty ranges)
+		LREG(4, 8, 4, 1024, lb1025, lb2049); LREG(5, 16, 4, 1024, lb2049, lb4097); LREG(6, 16, 8, 1024, lb4097, lb_big);   // (non-compact keys: t_big == t_blk, empty ranges)
 		if (small_by_blk) AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));
 #undef LREG
 		// (enqueued before the merge kernels of the side streams below: whichever hardware queue ovl1 shares, these do not wait behind one of those)
-		if (chain_small(c, pl)) return -1;
+		if (chain && chain_small(c, pl)) return -1;
 		if (ev(ST_ANCHOR_SORT_BLK)) return -1;
 		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[1], 0));                 // the device-wide sort (ovl0, started before the tile sorts)
 		if (ev(ST_ANCHOR_SORT_BIG)) return -1;
@@ -1011,10 +1027,12 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		// (only the streams that get a kernel below: aux1 has none unless AL_HEAP_OLD=1, and where it shares a stream with the merges made ahead its
 		//  join would make the main stream wait for those)
 		const bool heap_old = al_env().heap_old;
+		// every merge kernel counts its fragments in counters[0]; the tap gives each launch a word of its own instead (seed_cnt, HF_*), so that it can say which form took what
+		auto hc = [&](int form) -> unsigned long long * { return chain ? c->counters.p : c->seed_cnt.p + form; };
 		const bool aux_used[3] = {true, heap_old, true};
 		for (int i = 0; i < 3; ++i) if (aux_used[i]) AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0 + i), c->ev_fj[0], 0));
-#define LHEAP(H, LN, LO, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap<H, LN>), dim3((nl + LN - 1) / LN), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
-		                                  c->a_off.p, c->anchors.p, c->heap_ws.p, c->tie_list.p, (const uint32_t *)c->tie_frags.p, nl, LO, c->counters.p, c->mi->k, (const uint32_t *)n_heap_d, wave_na_min)
+#define LHEAP(H, LN, LO, ST, HC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap<H, LN>), dim3((nl + LN - 1) / LN), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
+		                                  c->a_off.p, c->anchors.p, c->heap_ws.p, c->tie_list.p, (const uint32_t *)c->tie_frags.p, nl, LO, HC, c->mi->k, (const uint32_t *)n_heap_d, wave_na_min)
 		// A lane of the lane kernels pops ~1 us per anchor with its 63 neighbours busy, the wavefront kernel 0.8 us with a wavefront to itself: in a
 		// small batch the lane kernels' longest fragment is what the main stream ends up waiting for (131 k pairs of C4: 18 -> 11 ms with the bound
 		// at 8192 anchors), in a large one the wavefront kernel's share is (C5, 500 k pairs: 652 vs 672 ms): the bound follows the batch.
@@ -1023,26 +1041,26 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		// Round 5: the heap in the lanes of a wavefront (k_anchor_heap_lanes: a fixed number of wave-wide instructions per pop instead of an LDS round trip
 		// per sift level) for every flagged fragment of up to 126 lists; the serial forms remain for more lists and behind AL_HEAP_OLD=1 (tests, A/B).
 		if (!heap_old) {
-#define LHL(NS, LO, ST) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_lanes<NS, 16>), dim3(std::min(nl, 65536)), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
-		                                    c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, LO, c->counters.p, c->mi->k)
-			LHL(2, 63, c->on(AL_ROLE_SIDE)); LHL(1, -1, c->on(AL_ROLE_AUX0));
+#define LHL(NS, LO, ST, HC) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_lanes<NS, 16>), dim3(std::min(nl, 65536)), dim3(64), 0, ST, c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p, \
+		                                    c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, LO, HC, c->mi->k)
+			LHL(2, 63, c->on(AL_ROLE_SIDE), hc(HF_LANES2)); LHL(1, -1, c->on(AL_ROLE_AUX0), hc(HF_LANES1));
 #undef LHL
-			{ const uint32_t wave_na_min = 0xffffffffu; LHEAP(0, 64, 126, c->on(AL_ROLE_AUX2)); }
+			{ const uint32_t wave_na_min = 0xffffffffu; LHEAP(0, 64, 126, c->on(AL_ROLE_AUX2), hc(HF_HEAP0)); }
 		} else {
 		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_anchor_heap_wave<128, 32>), dim3(std::min(nl, 65536)), dim3(64), 0, c->on(AL_ROLE_SIDE), c->di.pos, c->frag_first.p, c->rd_len.p, c->mini_off.p, c->match.p, c->frag_nm.p, c->frag_na.p,
-		                   c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, wave_na_min, c->counters.p, c->mi->k);
-		LHEAP(48, 64, -1, c->on(AL_ROLE_AUX0)); LHEAP(96, 32, 48, c->on(AL_ROLE_AUX1)); LHEAP(0, 64, 96, c->on(AL_ROLE_AUX2));
+		                   c->a_off.p, c->anchors.p, (const uint32_t *)c->tie_list.p, (const uint32_t *)c->tie_frags.p, (const uint32_t *)n_heap_d, wave_na_min, hc(HF_WAVE), c->mi->k);
+		LHEAP(48, 64, -1, c->on(AL_ROLE_AUX0), hc(HF_HEAP48)); LHEAP(96, 32, 48, c->on(AL_ROLE_AUX1), hc(HF_HEAP96)); LHEAP(0, 64, 96, c->on(AL_ROLE_AUX2), hc(HF_HEAP0));
 		}
 #undef LHEAP
 		for (int i = 0; i < 3; ++i) if (aux_used[i]) { AL_HIP_CHECK(hipEventRecord(c->ev_aux[i], c->on(AL_ROLE_AUX0 + i))); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_aux[i], 0)); }
 		AL_HIP_CHECK(hipEventRecord(evs[1], c->on(AL_ROLE_SIDE)));
 		if (ev(ST_ANCHOR_HEAP)) return -1;
 	}
-	if (chain_large(c, pl)) return -1;
+	if (chain && chain_large(c, pl)) return -1;
 	// second round: the fragments whose anchors the side stream merged, any size
 	AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_side[first ? 1 : 3], 0));
 	if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
-	if (chain_ties(c, pl)) return -1;
+	if (chain && chain_ties(c, pl)) return -1;
 	AL_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -1051,6 +1069,7 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 int al_run_seed_stages(al_ctx_t *c)
 {
 	hipStream_t s = c->stream;
+	c->seed_tap_pass1 = false;
 	AL_HIP_CHECK(hipSetDevice(c->device));
 	AL_HIP_CHECK(hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), s));
 	AL_HIP_CHECK(hipEventRecord(c->ev[0], s));
@@ -1234,6 +1253,69 @@ extern "C" int al_dbg_chain(al_ctx_t *c, const uint64_t *anchors_xy, const uint6
 	return 0;
 }
 
+// Tap (parity tests): what al_run_seed_stages runs of a pass without the chaining -- see include/airlift.h.  list == nullptr: the first pass on the
+// uploaded batch (k_sketch, k_frag_meta, the seed and anchor half of run_seed_chain); a list: the re-chain pass of those fragments (ascending ids, in
+// the place of k_rechain_test's sorted list) with opt.max_occ, after a first pass of this tap on the same batch.  The results stay on the device for
+// al_dbg_copy (frag_na, frag_nm, frag_rep, a_off, anchors, tie_list, mini ...); counts[]: seed_who, then four device counters.
+extern "C" int al_dbg_seed(al_ctx_t *c, const uint32_t *list, int n_list, uint64_t *counts)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_seed: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	const bool first = list == nullptr;
+	if (!first) {
+		if (!c->seed_tap_pass1 || n_list <= 0 || n_list > c->n_frag || !(c->opt.max_occ > c->opt.mid_occ)) return -2;
+		for (int i = 0; i < n_list; ++i) if (list[i] >= (uint32_t)c->n_frag || (i > 0 && list[i] <= list[i - 1])) return -2;
+	}
+	AL_HIP_CHECK(hipSetDevice(c->device));
+	al_nomem_flag() = false;
+	hipStream_t s = c->stream;
+	if (c->seed_cnt.ensure(8)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(c->seed_cnt.p, 0, 8 * sizeof(unsigned long long), s));
+	int sk_form = 0, sk_pb = 0;
+	if (first) {
+		c->seed_tap_pass1 = false; c->n_rechain = 0; c->ran = false;
+		AL_HIP_CHECK(hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), s));
+		AL_HIP_CHECK(hipEventRecord(c->ev[0], s));
+		const int nr = c->n_reads, w = c->mi->w, k = c->mi->k;
+		const bool sk_wide = al_sketch_wide(k, c->max_rd_len);
+		sk_pb = sk_wide ? -1 : al_sketch_pos_bits(k); sk_form = nr <= 0 ? 0 : sk_wide ? 3 : w == 11 ? 1 : 2;   // (k_sketch picks d_sketch_wide, d_sketch<11> or d_sketch<0> by these two arguments)
+		if (nr > 0) hipLaunchKernelGGL(k_sketch, dim3((nr + 63) / 64), dim3(64), (size_t)w * 64 * (sk_wide ? 12 : 8), s, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->mini_off.p, c->mini.p, c->mini_cnt.p, nr, w, k, sk_wide ? -1 : al_sketch_pos_bits(k));
+		AL_HIP_CHECK(hipEventRecord(c->ev[ST_SKETCH + 1], s));
+		if (c->frag_meta.ensure((size_t)c->n_frag + 1)) return -1;
+		hipLaunchKernelGGL(k_frag_meta, dim3((c->n_frag + 255) / 256), dim3(256), 0, s, c->frag_first.p, c->rd_len.p, c->n_frag, c->frag_meta.p);
+		if (run_seed_chain(c, nullptr, c->n_frag, c->opt.mid_occ, 0, true, false)) return -1;
+	} else {
+		const uint32_t n = (uint32_t)n_list;
+		if (c->a_off_p1.ensure(c->n_frag + 2) || c->frag_na_p1.ensure(c->n_frag + 1) || c->frag_rep_p1.ensure(c->n_frag + 1) || c->rechain_sorted.ensure(n + 1)) return -1;
+		AL_HIP_CHECK(hipMemcpyAsync(c->a_off_p1.p, c->a_off.p, (size_t)(c->n_frag + 1) * 8, hipMemcpyDeviceToDevice, s));
+		AL_HIP_CHECK(hipMemcpyAsync(c->frag_na_p1.p, c->frag_na.p, (size_t)c->n_frag * 4, hipMemcpyDeviceToDevice, s));
+		AL_HIP_CHECK(hipMemcpyAsync(c->frag_rep_p1.p, c->frag_rep.p, (size_t)c->n_frag * 4, hipMemcpyDeviceToDevice, s));
+		AL_HIP_CHECK(hipMemcpyAsync(c->rechain_sorted.p, list, (size_t)n * 4, hipMemcpyHostToDevice, s));
+		AL_HIP_CHECK(hipStreamSynchronize(s));                                   // (the list is the caller's)
+		c->n_rechain = n; c->seed_tap_pass1 = false;
+		if (run_seed_chain(c, c->rechain_sorted.p, (int)n, c->opt.max_occ, c->n_anchor_pass1 + (uint64_t)c->n_frag, false, false)) return -1;
+	}
+	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) AL_HIP_CHECK(hipStreamSynchronize(c->phys[p]));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	AL_HIP_CHECK(hipGetLastError());
+	if (first) c->seed_tap_pass1 = true;
+	if (al_env().test_guard && al_dev_guard_check()) fprintf(stderr, "[airlift] GUARD: violations after al_dbg_seed\n");
+	if (counts) {
+		for (int i = 0; i < SW_N; ++i) counts[i] = c->seed_who[i];
+		unsigned long long heaps = 0, form[8] = {}; uint32_t flagged = 0, spec[4] = {0, 0, 0, 0};
+		AL_HIP_CHECK(hipMemcpy(form, c->seed_cnt.p, sizeof(form), hipMemcpyDeviceToHost));
+		for (int i = 0; i < HF_N; ++i) { heaps += form[i]; counts[SW_N + 4 + i] = form[i]; }   // this pass's heap merges by launch (HF_*)
+		counts[SW_N + 4 + HF_N] = (uint64_t)sk_form;                           // first pass: 1 d_sketch<11>, 2 d_sketch<0>, 3 d_sketch_wide; 0: no sketch in this call
+		counts[SW_N + 5 + HF_N] = (uint64_t)(sk_pb + 64);                      // ... and the position bits of its packed entry + 64 (63: the wide form)
+		if (c->heap_cnt.p) AL_HIP_CHECK(hipMemcpy(&flagged, c->heap_cnt.p + (first ? 0 : 1), 4, hipMemcpyDeviceToHost));
+		if (c->n_spec > 0 && c->spec_cnt.p) AL_HIP_CHECK(hipMemcpy(spec, c->spec_cnt.p, 16, hipMemcpyDeviceToHost));
+		counts[SW_N] = heaps;                                                // heap merges of this pass, every form
+		counts[SW_N + 1] = c->n_spec;                                        // merges made ahead of the re-chain pass
+		counts[SW_N + 2] = first ? 0 : spec[2];                              // ... and how many of them it took
+		counts[SW_N + 3] = flagged;                                          // fragments on the merge kernels' list (flag word 1)
+	}
+	return 0;
+}
+
 extern "C" int al_dbg_anchors(al_ctx_t *c, int f, uint64_t *xy, int cap, int *rep_len)
 {
 	if (!c || f < 0 || f >= c->n_frag) return -1;
@@ -1310,6 +1392,8 @@ extern "C" int64_t al_dbg_copy(al_ctx_t *c, const char *name, void *dst, int64_t
 	else if (!strcmp(name, "mini_cnt")) src = c->mini_cnt.p, bytes = nr * 4;
 	else if (!strcmp(name, "frag_na")) src = c->frag_na.p, bytes = nf * 4;
 	else if (!strcmp(name, "frag_na_p1")) src = p1 ? c->frag_na_p1.p : c->frag_na.p, bytes = nf * 4;
+	else if (!strcmp(name, "frag_nm")) src = c->frag_nm.p, bytes = nf * 4;
+	else if (!strcmp(name, "tie_list")) src = c->tie_list.p, bytes = c->tie_list.p ? nf * 4 : 0;   // the last pass's flag word per fragment: 0 sorted, 1 merged by a heap kernel, 2 taken from a merge made ahead
 	else if (!strcmp(name, "frag_rep")) src = c->frag_rep.p, bytes = nf * 4;
 	else if (!strcmp(name, "frag_rep_p1")) src = p1 ? c->frag_rep_p1.p : c->frag_rep.p, bytes = nf * 4;
 	else if (!strcmp(name, "frag_nu")) src = c->frag_nu.p, bytes = nf * 4;

@@ -295,6 +295,21 @@ int  al_dbg_ext_dp(al_ctx_t *ctx, int n, const int64_t *jobs8, int32_t *out9, ui
  * fragments chained whole after them, size of the second round, fragments under AL_TEST_SEG_BIG, fragments of the fallback's virtual batches,
  * n_chain_fallback, lds_ok, tiles_ok, tile_from, the list positions of 1, 65 and 129 anchors, lmin.  Returns 0; -2: offsets out of order. */
 int  al_dbg_chain(al_ctx_t *ctx, const uint64_t *anchors_xy, const uint64_t *a_off, const uint32_t *tie_flag, uint32_t *nu_out, uint64_t *u_out, uint32_t *uo_out, uint64_t *chained_xy, uint64_t *counts);
+/* Tap (parity tests): the seed stage of a pass as a batch run launches it -- sketch, seed lookup, anchor collection, the sorts and the merges of the
+ * flagged fragments, on their streams and in their order -- without the chaining.  Needs a batch uploaded with al_batch_upload.  list == NULL: the
+ * first pass (mid_occ) on every fragment.  list[n_list], ascending fragment ids: the re-chain pass of those fragments with max_occ, in the place of
+ * the list the first pass's chains would have selected; once, after a first pass of this tap on the same batch; needs max_occ > mid_occ; the merges
+ * the first pass made ahead are taken as a run takes them.  The pass's results stay in the context for al_dbg_copy: "frag_na", "frag_nm",
+ * "frag_rep", "a_off", "anchors", "tie_list" (per fragment: 0 sorted, 1 merged by a heap kernel, 2 taken from a merge made ahead), "mini" ...
+ * counts[40] (may be NULL), fragments of this pass per sort kernel: k_anchor_sort_small; k_anchor_sort_reg <2,1,128> <4,1,256> <8,1,512> <16,1,512>
+ * <8,4,1024> <16,4,1024> <16,8,1024>; k_anchor_sort<1024>; the run merge's fragments, tiles and passes; the device radix sort's fragments and
+ * chunks; fragments flagged wholesale (rank_bits < 0); whether the keys are compact, rid_bits, pos_bits, rank_bits + 64; the pass's list length and
+ * the list positions of 65, 129, 257, 513 anchors, of the block sorts' bound and of 2049, 4097 anchors and the device-wide sort's bound; then
+ * from the device: this pass's heap merges, merges made ahead, how many of them this pass took, fragments on the merge kernels' list (flag word 1); the
+ * heap merges by launch (each gets a counter word of its own in this tap): k_anchor_heap_lanes<2>, <1>, k_anchor_heap<0>, k_anchor_heap_wave,
+ * k_anchor_heap<48>, <96>; the sketch form the first pass's arguments select (1 d_sketch<11>, 2 d_sketch<0>, 3 d_sketch_wide) and its position bits + 64.
+ * Returns 0; -2: no first pass before the second, or a list out of order. */
+int  al_dbg_seed(al_ctx_t *ctx, const uint32_t *list, int n_list, uint64_t *counts);
 
 /* Self-test of the multi-lane output path (offset exchange + pwrite, or ordered turns) with synthetic blocks; needs no GPU. */
 int  al_dbg_ordered_out_selftest(const char *path, int n_lanes, int n_batches, int use_offsets);
