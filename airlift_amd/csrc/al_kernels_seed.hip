@@ -2511,14 +2511,15 @@ k_collect_flagged_blk(const uint32_t *__restrict__ list, int n, const uint32_t *
 	if (on) { uint32_t o = s_base; for (int i = 0; i < w; ++i) o += s_w[i]; out[o + (uint32_t)__popcll(m & ((1ULL << lane) - 1ULL))] = f; }
 }
 
-// list entries whose fragment is flagged, appended to out (any order)
+// list entries whose fragment is flagged, appended to out (any order); sum (may be null): += their anchor counts na[f]
 __global__ void __launch_bounds__(256)
-k_collect_flagged(const uint32_t *__restrict__ list, int n, const uint32_t *__restrict__ flag, uint32_t *__restrict__ out, uint32_t *__restrict__ cnt)
+k_collect_flagged(const uint32_t *__restrict__ list, int n, const uint32_t *__restrict__ flag, uint32_t *__restrict__ out, uint32_t *__restrict__ cnt,
+                  const uint32_t *__restrict__ na, unsigned long long *__restrict__ sum)
 {
 	const int t = blockIdx.x * blockDim.x + threadIdx.x;
 	if (t >= n) return;
 	const uint32_t f = list[t];
-	if (flag[f]) out[atomicAdd(cnt, 1u)] = f;
+	if (flag[f]) { out[atomicAdd(cnt, 1u)] = f; if (sum) atomicAdd(sum, (unsigned long long)na[f]); }
 }
 
 // lower bounds of up to 16 thresholds in an ascending key array (out[k] pre-set to n)

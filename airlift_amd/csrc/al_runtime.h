@@ -37,6 +37,31 @@ struct AlRegOut {            // per-read result header copied back to the host
 	uint32_t n_regs, reg_off;   // reg_off: index into the AlReg output array
 };
 
+// The scratch of one chaining round (al_runtime.hip: chain_tiles, chain_fallback, chain_by_segments, chain_legacy): every array those four write that is not
+// a fragment's result, the temporaries of the helpers they call, and the round's device counters.  The first round (everything but the equal-x fragments, on
+// main) uses the context's members of the same names; the second round (the equal-x fragments, beside the tile kernel on the side stream) has this set, so that
+// neither an array's contents nor a DevBuf::ensure of one round -- it frees the old range -- touches what the other round's kernels are using.
+struct AlChainScratch {
+	DevBuf<uint64_t> ws_u64, u_tmp, okey_tmp, seg_first, seg_first0, vs_off, vs_res, d_uslot, v_u, v_a_off, v_first64;
+	DevBuf<int32_t> ws_i32;
+	DevBuf<AlAnchor> chain_tmp, v_anchors, v_chained;
+	DevBuf<uint32_t> seg_cnt, seg_cnt0, seg_t1, seg_key, seg_idx, seg_ord, vs_na, vs_meta, vs_cls, d_rel, d_fragid, cmp_list, ctie, fb_list, fb2_list, fb3_list, fbk_list;
+	DevBuf<uint32_t> v_na, v_nseg, v_first, v_rd_len, v_order, v_nu, lb_buf;
+	DevBuf<uint8_t> scan_tmp;
+	DevBuf<uint32_t> cnt;                  // [0..1] hand-backs of k_seg_merge / k_chain_order, [4..7] the tile kernel's counts, [8] flagged fragments, [10..11] their anchors (64 bits)
+	void release()
+	{
+		ws_u64.release(); u_tmp.release(); okey_tmp.release(); seg_first.release(); seg_first0.release(); vs_off.release(); vs_res.release(); d_uslot.release(); v_u.release(); v_a_off.release(); v_first64.release();
+		ws_i32.release(); chain_tmp.release(); v_anchors.release(); v_chained.release();
+		seg_cnt.release(); seg_cnt0.release(); seg_t1.release(); seg_key.release(); seg_idx.release(); seg_ord.release(); vs_na.release(); vs_meta.release(); vs_cls.release(); d_rel.release(); d_fragid.release();
+		cmp_list.release(); ctie.release(); fb_list.release(); fb2_list.release(); fb3_list.release(); fbk_list.release();
+		v_na.release(); v_nseg.release(); v_first.release(); v_rd_len.release(); v_order.release(); v_nu.release(); lb_buf.release(); scan_tmp.release(); cnt.release();
+	}
+};
+
+// The batch arrays the segment-wise chaining kernels read and write: the context's own, or those of chain_fallback's virtual batch (al_runtime.hip)
+struct AlBatchPtrs { AlAnchor *anchors, *chained; uint64_t *a_off, *u; uint32_t *frag_na, *frag_first, *rd_len, *frag_nu; };
+
 #define AL_CHAIN_WHO_N 16                  // counters of al_ctx_s::chain_who (al_runtime.hip: CW_*)
 #define AL_SEED_WHO_N 32                   // counters of al_ctx_s::seed_who (al_runtime.hip: SW_*)
 struct al_ctx_s {
@@ -58,7 +83,7 @@ struct al_ctx_s {
 	int n_phys = 0;
 	hipStream_t stream = nullptr;         // == phys[0], the main role
 	hipStream_t on(int role) const { return phys[role_map[role]]; }   // the stream a role runs on
-	hipEvent_t ev_fj[2] = {};             // fork / join of the side stream inside a stage (chain_post classes, DP job classes)
+	hipEvent_t ev_fj[2] = {};             // fork / join of the side stream inside a stage (the second chaining round, chain_post classes, DP job classes)
 	hipEvent_t ev_aux[3] = {};            // join events of aux0-2
 	hipEvent_t ev_ovl[5] = {};            // fork and join events of ovl0-2
 	bool ovl_pending = false;             // chaining kernels in flight on ovl1: chain_tiles joins them before it reuses their scratch
@@ -98,6 +123,7 @@ struct al_ctx_s {
 	DevBuf<AlAnchor> chain_tmp; DevBuf<uint64_t> u_tmp, okey_tmp, seg_first, seg_first0, vs_off, big_off, big_toff;
 	DevBuf<uint64_t> vs_res;                 // two words per segment: ChainSeg::res
 	DevBuf<uint32_t> seg_cnt, seg_cnt0, seg_t1, vs_na, vs_meta, vs_cls, seg_key, seg_idx, seg_ord, fb_list, fb2_list, fb3_list, big_na, big_nt, big_tent, big_cuts, tie_frags, tie_sorted, heap_cnt;
+	AlChainScratch tie2;                   // the second chaining round's own scratch (the equal-x fragments, beside the first round's tile kernel)
 	uint64_t n_chain_fallback = 0;
 	uint64_t chain_who[AL_CHAIN_WHO_N] = {};          // which chaining kernels took how much of the last pass (al_runtime.hip: CW_*), for the al_dbg_chain tap
 	DevBuf<unsigned long long> seed_cnt;                 // the al_dbg_seed tap: a count per heap-merge launch of the pass (al_runtime.hip: HF_*), in the place of counters[0]

@@ -6,6 +6,9 @@
 #include <string.h>
 #include <cstring>
 #include <algorithm>
+#include <functional>
+#include <thread>
+#include <chrono>
 #include "al_internal.h"
 #include "al_device.h"
 #include <mutex>
@@ -62,7 +65,7 @@ template <int NW> __global__ void k_seg_scan(const AlAnchor *, const uint64_t *,
 template <int NW> __global__ void k_seg_merge(const uint32_t *, int, const uint64_t *, const uint64_t *, const uint4 *, const uint64_t *, const AlAnchor *, const uint64_t *, uint64_t *, AlAnchor *, uint32_t *, uint32_t *, uint32_t *, const uint32_t *, const uint64_t *, uint64_t *, int, int);
 template <int NWV> __global__ void k_chain_order_t(const uint32_t *, int, const uint64_t *, const uint32_t *, uint64_t *, AlAnchor *, const uint64_t *, uint64_t *, AlAnchor *, uint32_t *, uint32_t *, int32_t *, int, int);
 __global__ void k_lower_bounds(const uint32_t *, uint32_t, LbThr, uint32_t *);
-__global__ void k_collect_flagged(const uint32_t *, int, const uint32_t *, uint32_t *, uint32_t *);
+__global__ void k_collect_flagged(const uint32_t *, int, const uint32_t *, uint32_t *, uint32_t *, const uint32_t *, unsigned long long *);
 __global__ void k_collect_flagged_blk(const uint32_t *, int, const uint32_t *, uint32_t *, uint32_t *);
 
 static const char *g_stage_names[ST_N] = { "sketch", "seed_lookup", "scan", "size_order", "anchor_sort_small", "anchor_sort", "anchor_sort_blk", "anchor_sort_big", "anchor_heap",
@@ -194,7 +197,7 @@ static void ctx_release_buffers(al_ctx_t *c)
 	c->chained.release(); c->match.release(); c->counters.release(); c->scan_tmp.release(); c->regs0.release(); c->regs.release(); c->reg_cnt.release();
 	c->big_tmp.release(); c->chain_key.release(); c->chain_idx.release(); c->chain_idx2.release(); c->tie_list.release(); c->lb_buf.release(); c->tmp_u64b.release();
 	c->chain_tmp.release(); c->u_tmp.release(); c->okey_tmp.release(); c->fb2_list.release(); c->fb3_list.release(); c->seg_cnt.release(); c->seg_first.release(); c->seg_cnt0.release(); c->seg_first0.release(); c->seg_t1.release(); c->vs_off.release(); c->vs_na.release(); c->vs_meta.release(); c->vs_res.release(); c->vs_cls.release(); c->seg_key.release(); c->seg_idx.release(); c->seg_ord.release(); c->fb_list.release(); c->tie_frags.release(); c->heap_cnt.release(); c->tie_sorted.release(); c->big_na.release(); c->big_off.release();
-	c->uo.release(); c->big_k0.release(); c->big_k1.release(); c->v_anchors.release(); c->v_chained.release(); c->v_u.release(); c->v_a_off.release(); c->v_first64.release(); c->v_na.release(); c->v_nseg.release(); c->v_first.release(); c->v_rd_len.release(); c->v_order.release(); c->v_nu.release(); c->fbk_list.release(); c->d_uslot.release(); c->d_rel.release(); c->chain_cls.release(); c->d_fragid.release(); c->cmp_list.release(); c->ctie.release(); c->frag_meta.release();
+	c->uo.release(); c->big_k0.release(); c->big_k1.release(); c->v_anchors.release(); c->v_chained.release(); c->v_u.release(); c->v_a_off.release(); c->v_first64.release(); c->v_na.release(); c->v_nseg.release(); c->v_first.release(); c->v_rd_len.release(); c->v_order.release(); c->v_nu.release(); c->fbk_list.release(); c->d_uslot.release(); c->d_rel.release(); c->chain_cls.release(); c->d_fragid.release(); c->cmp_list.release(); c->ctie.release(); c->frag_meta.release(); c->tie2.release();
 	c->big_nt.release(); c->big_toff.release(); c->big_tent.release(); c->big_cuts.release();
 	c->a_off_p1.release(); c->frag_na_p1.release(); c->frag_rep_p1.release(); c->cigar.release(); c->reg_off.release(); c->cig_off.release(); c->align_ws.release(); c->seg_a.release(); c->seg_u.release();
 }
@@ -337,18 +340,6 @@ static int ensure_anchor_space(al_ctx_t *c, uint64_t total, bool keep)
 	return 0;
 }
 
-// first index with keys[i] >= thr[k] in an ascending device array, for up to 16 thresholds (one kernel, one copy back)
-static int lower_bounds(al_ctx_t *c, const uint32_t *keys, uint32_t n, const uint32_t *thr, int nt, uint32_t *out)
-{
-	if (c->lb_buf.ensure(16)) return -1;
-	uint32_t init[16]; LbThr T; T.n = nt;
-	for (int i = 0; i < 16; ++i) { init[i] = n; T.v[i] = i < nt ? thr[i] : 0xffffffffu; }
-	AL_HIP_CHECK(hipMemcpyAsync(c->lb_buf.p, init, 64, hipMemcpyHostToDevice, c->stream));
-	if (n > 0) hipLaunchKernelGGL(k_lower_bounds, dim3((n + 255) / 256), dim3(256), 0, c->stream, keys, n, T, c->lb_buf.p);
-	AL_HIP_CHECK(hipMemcpyAsync(out, c->lb_buf.p, 4 * nt, hipMemcpyDeviceToHost, c->stream));
-	AL_HIP_CHECK(hipStreamSynchronize(c->stream));
-	return 0;
-}
 static int sort_u32_pairs(al_ctx_t *c, const uint32_t *k_in, uint32_t *k_out, const uint32_t *v_in, uint32_t *v_out, int n)
 {
 	if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, k_in, k_out, v_in, v_out, n, 0, 32, c->stream); })) return -1;
@@ -366,7 +357,97 @@ enum { SW_SMALL, SW_REG0, SW_SORT1024 = SW_REG0 + 7, SW_MERGE_FRAGS, SW_MERGE_TI
 enum { HF_LANES2, HF_LANES1, HF_HEAP0, HF_WAVE, HF_HEAP48, HF_HEAP96, HF_N };   // the heap-merge launches: k_anchor_heap_lanes<2|1>, k_anchor_heap<0>, k_anchor_heap_wave, k_anchor_heap<48|96>
 static_assert(SW_N <= AL_SEED_WHO_N, "al_ctx_t::seed_who holds a counter per SW_* name");
 
-#define LCH(C, L, LO, AOFF, NA, CH, UO, NU, LIST, N, SEG, UOFF, WS, STRIDE) do { const int n__ = (N); if (n__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_lds<C, L>), dim3((n__ + L - 1) / L), dim3(64), 0, s, c->anchors.p, AOFF, NA, c->frag_first.p, c->rd_len.p, CH, UO, NU, WS, LIST, n__, LO, c->P, c->counters.p, SEG, UOFF, STRIDE); } while (0)
+#define LCH(C, L, LO, AOFF, NA, CH, UO, NU, LIST, N, SEG, UOFF, WS, STRIDE) do { const int n__ = (N); if (n__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_lds<C, L>), dim3((n__ + L - 1) / L), dim3(64), 0, s, B.anchors, AOFF, NA, B.frag_first, B.rd_len, CH, UO, NU, WS, LIST, n__, LO, c->P, c->counters.p, SEG, UOFF, STRIDE); } while (0)   // (B: the AlBatchPtrs in scope)
+
+// A chaining round: the stream its launches and host waits are on, and the scratch it works in (AlChainScratch, al_runtime.h).  round_main(): the main stream
+// and the context's own members -- the first round of a pass, and the second where it runs after the first.  round_beside(): the side stream and al_ctx_s::tie2
+// -- the second round of a pass beside the first round's tile kernel.  One host thread issues both; what the rounds share is read-only to both (the anchors, the
+// offsets, the options) or written at disjoint fragments' places (chained[], u[], uo[], frag_nu[]).
+static inline AlBatchPtrs batch_ptrs(const al_ctx_t *c) { return AlBatchPtrs{c->anchors.p, c->chained.p, c->a_off.p, c->u.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->frag_nu.p}; }   // the batch's own arrays
+
+// A host wait for a chaining round's stream: hipStreamSynchronize, or -- with `idle` -- a poll of the stream that lets the host serve the other round when that one's
+// turn comes first.  idle(): < 0 an error, 1 nothing more to do, 0 not yet.
+static int chain_wait(hipStream_t s, const std::function<int()> *idle)
+{
+	while (idle) {
+		const hipError_t q = hipStreamQuery(s);
+		if (q == hipSuccess) break;
+		if (q != hipErrorNotReady) { fprintf(stderr, "[airlift] HIP error %s while a chaining round waits for its stream\n", hipGetErrorName(q)); return -1; }
+		const int r = (*idle)();
+		if (r < 0) return -1;
+		if (r > 0) break;
+		std::this_thread::sleep_for(std::chrono::microseconds(20));
+	}
+	if (hipStreamSynchronize(s) != hipSuccess) { fprintf(stderr, "[airlift] HIP error while a chaining round waits for its stream\n"); return -1; }
+	return 0;
+}
+#define CHAIN_SCRATCH(X) X(ws_u64) X(u_tmp) X(okey_tmp) X(seg_first) X(seg_first0) X(vs_off) X(vs_res) X(d_uslot) X(v_u) X(v_a_off) X(v_first64) X(ws_i32) X(chain_tmp) X(v_anchors) X(v_chained) \
+	X(seg_cnt) X(seg_cnt0) X(seg_t1) X(seg_key) X(seg_idx) X(seg_ord) X(vs_na) X(vs_meta) X(vs_cls) X(d_rel) X(d_fragid) X(cmp_list) X(ctie) X(fb_list) X(fb2_list) X(fb3_list) X(fbk_list) \
+	X(v_na) X(v_nseg) X(v_first) X(v_rd_len) X(v_order) X(v_nu) X(lb_buf) X(scan_tmp)
+struct ChainRound {
+	hipStream_t s;
+	bool own;                             // the round has a scratch set to itself (and no part in the context's: ovl_pending, the two-stream rule of the deferred classes)
+	bool company;                         // kernels of the other round may be in flight beside this one's
+	const std::function<int()> *idle;     // (may be null) what the host has to do for the other round, asked while this one waits: < 0 an error, 1 nothing more, 0 not yet
+	uint32_t *fb_cnt, *cnts;              // two words: fragments k_seg_merge / k_chain_order hand back; four words: the tile kernel's counts (handed back, deferred segments, to compact)
+	uint64_t n_anchor; int n_frag_max;    // anchors of the round's fragments (bounds the deferred segments), fragments it can list
+	const char *tag() const { return own ? "beside" : "main"; }   // (AL_TRACE)
+#define X(n) decltype(AlChainScratch::n) &n;
+	CHAIN_SCRATCH(X)
+#undef X
+	// DevBuf::ensure for a scratch array of the round.  It frees the old range, and the allocator hands a freed range out again at once: beside the other round
+	// the stream is drained first, so that nothing of this round still uses what the other round's next ensure may be given.  (Grow-only arrays: the first batches.)
+	template <class T> int need(DevBuf<T> &b, size_t n, int line = __builtin_LINE()) const
+	{
+		if (n <= b.cap) return 0;
+		if (company && b.p && hipStreamSynchronize(s) != hipSuccess) return -1;
+		return b.ensure(n, false, s, line, __FILE__);
+	}
+	template <class F> int prim(F call, int line = __builtin_LINE()) const   // al_prim_run on the round's temporary
+	{
+		size_t bytes = 0;
+		if (company && call((void *)nullptr, bytes) == hipSuccess && need(scan_tmp, bytes + 16, line)) return AL_ERR_NOMEM;
+		return al_prim_run(scan_tmp, call, nullptr, line, __FILE__);
+	}
+	int wait() const { return chain_wait(s, idle); }   // a host wait of the round
+	// a count of the round copied back, waited for.  (The wait comes first: a copy to pageable host memory may hold the host until the stream reaches it.)
+	int fetch(void *dst, const void *src, size_t bytes) const
+	{
+		if (idle && wait()) return -1;
+		if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) { fprintf(stderr, "[airlift] HIP error while a chaining round copies a count back\n"); return -1; }
+		return 0;
+	}
+	int scan(const uint32_t *in, uint64_t *out, int n, int line = __builtin_LINE()) const   // scan_u32_to_u64 on the round's stream and temporary
+	{
+		auto it = rocprim::make_transform_iterator(in, AlCastU64());
+		return prim([&](void *t, size_t &b) { return rocprim::exclusive_scan(t, b, it, out, (uint64_t)0, (size_t)(n + 1), rocprim::plus<uint64_t>(), s); }, line) ? -1 : 0;
+	}
+};
+template <class S> static ChainRound chain_round(S &from, hipStream_t s, bool own, bool company, uint32_t *fb_cnt, uint32_t *cnts, uint64_t n_anchor, int n_frag_max)
+{
+	return ChainRound{s, own, company, nullptr, fb_cnt, cnts, n_anchor, n_frag_max,
+#define X(n) from.n,
+		CHAIN_SCRATCH(X)
+#undef X
+	};
+}
+static ChainRound round_main(al_ctx_t *c, bool company = false) { return chain_round(*c, c->stream, false, company, (uint32_t *)(c->counters.p + 15), (uint32_t *)(c->counters.p + 16), c->n_anchor_total, c->n_frag); }
+static ChainRound round_beside(al_ctx_t *c, uint64_t n_anchor, int n_frag_max) { AlChainScratch &T = c->tie2; return chain_round(T, c->on(AL_ROLE_SIDE), true, true, T.cnt.p, T.cnt.p + 4, n_anchor, n_frag_max); }
+
+// first index with keys[i] >= thr[k] in an ascending device array, for up to 16 thresholds (one kernel, one copy back); R: on that round's stream, with its buffer and its way to wait
+static int lower_bounds(al_ctx_t *c, const uint32_t *keys, uint32_t n, const uint32_t *thr, int nt, uint32_t *out, const ChainRound *R = nullptr)
+{
+	hipStream_t const s = R ? R->s : c->stream; DevBuf<uint32_t> &lb_buf = R ? R->lb_buf : c->lb_buf;
+	if (lb_buf.ensure(16)) return -1;
+	uint32_t init[16]; LbThr T; T.n = nt;
+	for (int i = 0; i < 16; ++i) { init[i] = n; T.v[i] = i < nt ? thr[i] : 0xffffffffu; }
+	AL_HIP_CHECK(hipMemcpyAsync(lb_buf.p, init, 64, hipMemcpyHostToDevice, s));
+	if (n > 0) hipLaunchKernelGGL(k_lower_bounds, dim3((n + 255) / 256), dim3(256), 0, s, keys, n, T, lb_buf.p);
+	if (R) return R->fetch(out, lb_buf.p, 4 * (size_t)nt);
+	AL_HIP_CHECK(hipMemcpyAsync(out, lb_buf.p, 4 * nt, hipMemcpyDeviceToHost, s));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	return 0;
+}
 
 // Chaining of the fragments order[0 .. n) (more than 128 anchors each, or any size when the compact LDS rows cannot hold the
 // options in force) through their segments: cut -> order the segments by length -> the lane-per-entry LDS kernels for segments
@@ -375,64 +456,62 @@ static_assert(SW_N <= AL_SEED_WHO_N, "al_ctx_t::seed_who holds a counter per SW_
 // with_keys: the per-chain processing keys (ChainSeg::okey) are written as well, and fragments whose chain starts tie get their order
 // from k_chain_order.  The hot call runs without them (8 scattered bytes per chain less to write and to read back) and hands the few
 // fragments that turn out to need them (ties among more than 64 chains) to a second call, on those fragments only, with keys.
-static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds_ok, bool first, const uint32_t *skip_flag, bool with_keys = false, int big_from = 0 /* entries before this one have too few anchors for AL_SEGM_BIG segments */, int big8_from = 0 /* ... at most AL_SEGS_BIG anchors */)
+static int chain_by_segments(al_ctx_t *c, const ChainRound &R, const AlBatchPtrs &B, const uint32_t *order, int n, bool lds_ok, bool first, const uint32_t *skip_flag, bool with_keys = false, int big_from = 0 /* entries before this one have too few anchors for AL_SEGM_BIG segments */, int big8_from = 0 /* ... at most AL_SEGS_BIG anchors */)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = R.s;
 	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
 	if (n <= 0) { if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS) || ev(ST_SEG_CHAIN_WAVE) || ev(ST_SEG_MERGE)) return -1; return 0; }
 	// a segment of fewer than lmin anchors cannot hold a chain: min_cnt anchors, and min_chain_score at <= k + 1 per anchor (chain.c:60-73,118-124)
 	int lmin = c->opt.min_cnt > 1 ? c->opt.min_cnt : 1;
 	{ const int per = c->mi->k + 1, need = (c->opt.min_chain_score + per - 1) / per; if (need > lmin) lmin = need; }
-	if (c->seg_cnt.ensure((size_t)n + 2) || c->seg_first.ensure((size_t)n + 2) || c->seg_cnt0.ensure((size_t)n + 2) || c->seg_first0.ensure((size_t)n + 2)) return -1;
+	if (R.need(R.seg_cnt, (size_t)n + 2) || R.need(R.seg_first, (size_t)n + 2) || R.need(R.seg_cnt0, (size_t)n + 2) || R.need(R.seg_first0, (size_t)n + 2)) return -1;
 	// (fragments of more than AL_SEGS_BIG anchors: eight wavefronts each, launched first; big8_from: the entries before it have at most 8192 anchors)
 	// (tests lower the two sizes so that ordinary fragments take the eight-wavefront forms; the list positions are then no bound any more)
 	const std::optional<int> &seg_big = al_env().test_seg_big;
 	const int segs_big = seg_big.value_or(8192), segm_big = seg_big ? std::max(1, *seg_big / 8) : 1024;
 	if (seg_big) { big_from = 0; big8_from = 0; c->chain_who[CW_SEG_BIG] += (uint64_t)n; }
 	if (big8_from < 0 || big8_from > n) big8_from = 0;
-	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order + big8_from, n - big8_from, c->P, lmin, 0,
-	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, c->seg_cnt.p + big8_from, c->seg_cnt0.p + big8_from, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
+	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, B.anchors, B.a_off, B.frag_na, B.frag_first, B.rd_len, order + big8_from, n - big8_from, c->P, lmin, 0,
+	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, R.seg_cnt.p + big8_from, R.seg_cnt0.p + big8_from, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
 	                   (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, big8_from, segs_big);
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<1>), dim3(n), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order, n, c->P, lmin, 0,
-	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, c->seg_cnt.p, c->seg_cnt0.p, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<1>), dim3(n), dim3(64), 0, s, B.anchors, B.a_off, B.frag_na, B.frag_first, B.rd_len, order, n, c->P, lmin, 0,
+	                   (const uint64_t *)nullptr, (const uint64_t *)nullptr, R.seg_cnt.p, R.seg_cnt0.p, (uint64_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, skip_flag,
 	                   (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr, big8_from, segs_big);
-	AL_HIP_CHECK(hipMemsetAsync(c->seg_cnt.p + n, 0, 4, s)); AL_HIP_CHECK(hipMemsetAsync(c->seg_cnt0.p + n, 0, 4, s));
-	if (scan_u32_to_u64(c, c->seg_cnt.p, c->seg_first.p, n) || scan_u32_to_u64(c, c->seg_cnt0.p, c->seg_first0.p, n)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(R.seg_cnt.p + n, 0, 4, s)); AL_HIP_CHECK(hipMemsetAsync(R.seg_cnt0.p + n, 0, 4, s));
+	if (R.scan(R.seg_cnt.p, R.seg_first.p, n) || R.scan(R.seg_cnt0.p, R.seg_first0.p, n)) return -1;
 	uint64_t ns64 = 0, ns0_64 = 0;
-	AL_HIP_CHECK(hipMemcpyAsync(&ns64, c->seg_first.p + n, 8, hipMemcpyDeviceToHost, s));
-	AL_HIP_CHECK(hipMemcpyAsync(&ns0_64, c->seg_first0.p + n, 8, hipMemcpyDeviceToHost, s));
-	AL_HIP_CHECK(hipStreamSynchronize(s));
+	if (R.fetch(&ns64, R.seg_first.p + n, 8) || R.fetch(&ns0_64, R.seg_first0.p + n, 8)) return -1;
 	if (ns64 >= (1ULL << 31)) { fprintf(stderr, "[airlift] %llu chaining segments in one batch: upload fewer fragments\n", (unsigned long long)ns64); al_nomem_flag() = true; return -1; }
 	// ns segments, ns0 of them of class 0 (at most 16 anchors: listed by the fill pass in memory order), n1 others (ordered by class below)
 	const int ns = (int)ns64, ns0 = (int)ns0_64, n1 = ns - ns0;
-	if (c->vs_off.ensure((size_t)ns + 1) || c->vs_na.ensure((size_t)ns + 1) || c->vs_meta.ensure((size_t)ns + 1) || c->vs_res.ensure(2 * ((size_t)ns + 1)) ||
-	    c->seg_idx.ensure((size_t)ns0 + 1) || c->vs_cls.ensure((size_t)n1 + 1) || c->seg_t1.ensure((size_t)n1 + 1) || c->seg_key.ensure((size_t)n1 + 1) || c->seg_ord.ensure((size_t)n1 + 1) || c->fb_list.ensure((size_t)n + 2)) return -1;
-	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order + big8_from, n - big8_from, c->P, lmin, 1,
-	                   (const uint64_t *)c->seg_first.p + big8_from, (const uint64_t *)c->seg_first0.p + big8_from, (uint32_t *)nullptr, (uint32_t *)nullptr, c->vs_off.p, c->vs_na.p, c->vs_meta.p, skip_flag,
-	                   c->seg_idx.p, c->seg_t1.p, c->vs_cls.p, big8_from, segs_big);
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<1>), dim3(n), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, order, n, c->P, lmin, 1,
-	                   (const uint64_t *)c->seg_first.p, (const uint64_t *)c->seg_first0.p, (uint32_t *)nullptr, (uint32_t *)nullptr, c->vs_off.p, c->vs_na.p, c->vs_meta.p, skip_flag,
-	                   c->seg_idx.p, c->seg_t1.p, c->vs_cls.p, big8_from, segs_big);
+	if (R.need(R.vs_off, (size_t)ns + 1) || R.need(R.vs_na, (size_t)ns + 1) || R.need(R.vs_meta, (size_t)ns + 1) || R.need(R.vs_res, 2 * ((size_t)ns + 1)) ||
+	    R.need(R.seg_idx, (size_t)ns0 + 1) || R.need(R.vs_cls, (size_t)n1 + 1) || R.need(R.seg_t1, (size_t)n1 + 1) || R.need(R.seg_key, (size_t)n1 + 1) || R.need(R.seg_ord, (size_t)n1 + 1) || R.need(R.fb_list, (size_t)n + 2)) return -1;
+	if (n > big8_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<8>), dim3(n - big8_from), dim3(512), 0, s, B.anchors, B.a_off, B.frag_na, B.frag_first, B.rd_len, order + big8_from, n - big8_from, c->P, lmin, 1,
+	                   (const uint64_t *)R.seg_first.p + big8_from, (const uint64_t *)R.seg_first0.p + big8_from, (uint32_t *)nullptr, (uint32_t *)nullptr, R.vs_off.p, R.vs_na.p, R.vs_meta.p, skip_flag,
+	                   R.seg_idx.p, R.seg_t1.p, R.vs_cls.p, big8_from, segs_big);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_scan<1>), dim3(n), dim3(64), 0, s, B.anchors, B.a_off, B.frag_na, B.frag_first, B.rd_len, order, n, c->P, lmin, 1,
+	                   (const uint64_t *)R.seg_first.p, (const uint64_t *)R.seg_first0.p, (uint32_t *)nullptr, (uint32_t *)nullptr, R.vs_off.p, R.vs_na.p, R.vs_meta.p, skip_flag,
+	                   R.seg_idx.p, R.seg_t1.p, R.vs_cls.p, big8_from, segs_big);
 	uint32_t lb[8] = {0, 0, 0, 0, 0, 0, 0, 0};                                // starts of classes 2 .. 9 in the class-ordered list of the n1 others
 	if (n1 > 0) {
 		{   // stable sort by size class only (4 bits: one radix pass)
-			if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, n1, 0, 4, s); })) return -1;
+			if (R.prim([&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)R.vs_cls.p, R.seg_key.p, (const uint32_t *)R.seg_t1.p, R.seg_ord.p, n1, 0, 4, s); })) return -1;
 		}
 		static const uint32_t thr[8] = {2, 3, 4, 5, 6, 7, 8, 9};
-		if (lower_bounds(c, c->seg_key.p, (uint32_t)n1, thr, 8, lb)) return -1;
+		if (lower_bounds(c, R.seg_key.p, (uint32_t)n1, thr, 8, lb, &R)) return -1;
 	}
 	if (al_env().trace && first) fprintf(stderr, "[airlift] trace: segments: %d in %d fragments; by size <=16:%d <=24:%u <=32:%u <=48:%u <=64:%u <=128:%u more:%u\n", ns, n,
 	                          ns0, lb[0], lb[1] - lb[0], lb[3] - lb[1], lb[4] - lb[3], lb[7] - lb[4], (uint32_t)n1 - lb[7]);
 	if (ev(ST_SEG_FIND)) return -1;
 	const bool keys_possible = c->opt.min_cnt >= 2;                           // a chain has >= 2 anchors: the keys of a segment fit half of its range
 	const bool keep_keys = with_keys && keys_possible;
-	const ChainSeg sg{c->vs_meta.p, (uint32_t *)c->vs_res.p, nullptr, 0, keep_keys ? c->okey_tmp.p : nullptr};
+	const ChainSeg sg{R.vs_meta.p, (uint32_t *)R.vs_res.p, nullptr, 0, keep_keys ? R.okey_tmp.p : nullptr};
 	bool thin[4] = {false, false, false, false};
 	const uint32_t wave_max = al_env().chain_wave_max;   // (tests: 0 = never, a large value = always)
 	if (ns > 0) {
-		const uint32_t *so0 = c->seg_idx.p, *so1 = c->seg_ord.p;
+		const uint32_t *so0 = R.seg_idx.p, *so1 = R.seg_ord.p;
 		if (lds_ok) {
-#define LSEG(C, L, LIST, A, B) LCH(C, L, -1, c->vs_off.p, c->vs_na.p, c->chain_tmp.p, c->u_tmp.p, (uint32_t *)nullptr, (LIST) + (A), (int)((B) - (A)), sg, (uint32_t *)nullptr, c->ws_u64.p, 0)
+#define LSEG(C, L, LIST, A, B) LCH(C, L, -1, R.vs_off.p, R.vs_na.p, R.chain_tmp.p, R.u_tmp.p, (uint32_t *)nullptr, (LIST) + (A), (int)((B) - (A)), sg, (uint32_t *)nullptr, R.ws_u64.p, 0)
 			LSEG(16, 64, so0, 0u, (uint32_t)ns0);
 			LSEG(24, 64, so1, 0u, lb[0]); LSEG(32, 64, so1, lb[0], lb[1]); LSEG(40, 64, so1, lb[1], lb[2]); LSEG(48, 64, so1, lb[2], lb[3]);
 			// A lane walks a 49 ... 128-anchor entry for 0.5 - 1.3 ms whatever the launch holds; the wavefront kernel takes ~1 us per anchor of an
@@ -446,8 +525,8 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 		}
 		if (ev(ST_SEG_CHAIN_LDS)) return -1;
 		// the wavefront kernel: segments of more than 128 anchors, or (options outside the compact rows' range) all of them
-#define LWAVE(LIST, N) do { const int nw__ = (N); if (nw__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(nw__), dim3(64), 0, s, c->anchors.p, c->vs_off.p, c->vs_na.p, c->frag_first.p, c->rd_len.p, c->chain_tmp.p, c->u_tmp.p, (uint32_t *)nullptr, \
-		                               c->ws_i32.p, c->ws_u64.p, (LIST), nw__, c->P, c->counters.p, sg); } while (0)
+#define LWAVE(LIST, N) do { const int nw__ = (N); if (nw__ > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(nw__), dim3(64), 0, s, B.anchors, R.vs_off.p, R.vs_na.p, B.frag_first, B.rd_len, R.chain_tmp.p, R.u_tmp.p, (uint32_t *)nullptr, \
+		                               R.ws_i32.p, R.ws_u64.p, (LIST), nw__, c->P, c->counters.p, sg); } while (0)
 		const int nw = lds_ok ? n1 - (int)lb[7] : ns;
 		c->chain_who[CW_WAVE_SEGS] += (uint64_t)nw; if (lds_ok) for (int k = 3; k < 7; ++k) if (thin[k - 3]) c->chain_who[CW_WAVE_SEGS] += lb[k + 1] - lb[k];
 		if (al_env().trace && nw > 0) fprintf(stderr, "[airlift] trace: %d segments to the wavefront kernel (of %d segments in %d fragments)\n", nw, ns, n);
@@ -455,26 +534,25 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 #undef LWAVE
 		if (ev(ST_SEG_CHAIN_WAVE)) return -1;
 	} else { if (ev(ST_SEG_CHAIN_LDS) || ev(ST_SEG_CHAIN_WAVE)) return -1; }
-	uint32_t *fb_cnt = (uint32_t *)(c->counters.p + 15);
+	uint32_t *fb_cnt = R.fb_cnt;
 	AL_HIP_CHECK(hipMemsetAsync(fb_cnt, 0, 8, s));
 	// (the fragments with many segments first: eight wavefronts each, next to the one-wavefront launch of the others)
 	if (big_from < 0 || big_from > n) big_from = 0;
-	if (n > big_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_merge<8>), dim3(n - big_from), dim3(512), 0, s, order + big_from, n - big_from, c->seg_first.p + big_from, c->vs_off.p, (const uint4 *)c->vs_res.p, c->u_tmp.p, c->chain_tmp.p, c->a_off.p,
-	                   c->u.p, c->chained.p, c->frag_nu.p, c->fb_list.p, fb_cnt, skip_flag, keep_keys ? (const uint64_t *)c->okey_tmp.p : nullptr, c->ws_u64.p, big_from, segm_big);
-	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_merge<1>), dim3(n), dim3(64), 0, s, order, n, c->seg_first.p, c->vs_off.p, (const uint4 *)c->vs_res.p, c->u_tmp.p, c->chain_tmp.p, c->a_off.p,
-	                   c->u.p, c->chained.p, c->frag_nu.p, c->fb_list.p, fb_cnt, skip_flag, keep_keys ? (const uint64_t *)c->okey_tmp.p : nullptr, c->ws_u64.p, big_from, segm_big);
+	if (n > big_from) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_merge<8>), dim3(n - big_from), dim3(512), 0, s, order + big_from, n - big_from, R.seg_first.p + big_from, R.vs_off.p, (const uint4 *)R.vs_res.p, R.u_tmp.p, R.chain_tmp.p, B.a_off,
+	                   B.u, B.chained, B.frag_nu, R.fb_list.p, fb_cnt, skip_flag, keep_keys ? (const uint64_t *)R.okey_tmp.p : nullptr, R.ws_u64.p, big_from, segm_big);
+	hipLaunchKernelGGL(HIP_KERNEL_NAME(k_seg_merge<1>), dim3(n), dim3(64), 0, s, order, n, R.seg_first.p, R.vs_off.p, (const uint4 *)R.vs_res.p, R.u_tmp.p, R.chain_tmp.p, B.a_off,
+	                   B.u, B.chained, B.frag_nu, R.fb_list.p, fb_cnt, skip_flag, keep_keys ? (const uint64_t *)R.okey_tmp.p : nullptr, R.ws_u64.p, big_from, segm_big);
 	uint32_t n_fb = 0;
-	AL_HIP_CHECK(hipMemcpyAsync(&n_fb, fb_cnt, 4, hipMemcpyDeviceToHost, s));
-	AL_HIP_CHECK(hipStreamSynchronize(s));
+	if (R.fetch(&n_fb, fb_cnt, 4)) return -1;
 	if (n_fb > 0 && keys_possible && !with_keys) {   // the same fragments once more, with keys (the segment arrays are free again; the list moves out of the way)
-		if (c->fb3_list.ensure((size_t)n_fb + 2)) return -1;
-		AL_HIP_CHECK(hipMemcpyAsync(c->fb3_list.p, c->fb_list.p, (size_t)n_fb * 4, hipMemcpyDeviceToDevice, s));
-		if (chain_by_segments(c, c->fb3_list.p, (int)n_fb, lds_ok, false, skip_flag, true)) return -1;
+		if (R.need(R.fb3_list, (size_t)n_fb + 2)) return -1;
+		AL_HIP_CHECK(hipMemcpyAsync(R.fb3_list.p, R.fb_list.p, (size_t)n_fb * 4, hipMemcpyDeviceToDevice, s));
+		if (chain_by_segments(c, R, B, R.fb3_list.p, (int)n_fb, lds_ok, false, skip_flag, true)) return -1;
 		if (ev(ST_SEG_MERGE)) return -1;
 		return 0;
 	}
 	c->n_chain_fallback += n_fb;
-	const uint32_t *fb = c->fb_list.p;
+	const uint32_t *fb = R.fb_list.p;
 	if (n_fb > 0 && keep_keys) {   // order restated from the merged chains and their processing keys; only what does not fit its tile is chained again
 		const size_t lds = (size_t)AL_ORD_CAP * (8 + 4 + 2) + 64, lds16 = (size_t)AL_ORD_CAP2 * (8 + 2) + 64;   // (lds16 >= lds: the block form keeps the one-wavefront layout up to AL_ORD_CAP chains)
 		const int nu_block = al_env().order_block;             // chains from which a block of 16 wavefronts takes the fragment
@@ -483,34 +561,34 @@ static int chain_by_segments(al_ctx_t *c, const uint32_t *order, int n, bool lds
 			AL_HIP_CHECK(hipFuncSetAttribute((const void *)k_chain_order_t<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds16));
 			c->attr_chain_order = true;
 		}
-		if (c->fb2_list.ensure((size_t)n_fb + 2)) return -1;
+		if (R.need(R.fb2_list, (size_t)n_fb + 2)) return -1;
 		c->chain_who[CW_ORDER_FRAGS] += n_fb;
+		if (al_env().trace) fprintf(stderr, "[airlift] trace: round %s: chain order kernels on %u fragments\n", R.tag(), n_fb);
 		AL_HIP_CHECK(hipMemsetAsync(fb_cnt, 0, 8, s));
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<16>), dim3(n_fb), dim3(1024), lds16, s, c->fb_list.p, (int)n_fb, c->a_off.p, c->frag_nu.p, c->u.p, c->chained.p, (const uint64_t *)c->ws_u64.p, c->u_tmp.p, c->chain_tmp.p, c->fb2_list.p, fb_cnt, c->ws_i32.p, nu_block, 1 << 30);
-		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<1>), dim3(n_fb), dim3(64), lds, s, c->fb_list.p, (int)n_fb, c->a_off.p, c->frag_nu.p, c->u.p, c->chained.p, (const uint64_t *)c->ws_u64.p, c->u_tmp.p, c->chain_tmp.p, c->fb2_list.p, fb_cnt, c->ws_i32.p, 0, nu_block);
-		AL_HIP_CHECK(hipMemcpyAsync(&n_fb, fb_cnt, 4, hipMemcpyDeviceToHost, s));
-		AL_HIP_CHECK(hipStreamSynchronize(s));
-		fb = c->fb2_list.p;
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<16>), dim3(n_fb), dim3(1024), lds16, s, R.fb_list.p, (int)n_fb, B.a_off, B.frag_nu, B.u, B.chained, (const uint64_t *)R.ws_u64.p, R.u_tmp.p, R.chain_tmp.p, R.fb2_list.p, fb_cnt, R.ws_i32.p, nu_block, 1 << 30);
+		hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_order_t<1>), dim3(n_fb), dim3(64), lds, s, R.fb_list.p, (int)n_fb, B.a_off, B.frag_nu, B.u, B.chained, (const uint64_t *)R.ws_u64.p, R.u_tmp.p, R.chain_tmp.p, R.fb2_list.p, fb_cnt, R.ws_i32.p, 0, nu_block);
+		if (R.fetch(&n_fb, fb_cnt, 4)) return -1;
+		fb = R.fb2_list.p;
 	}
 	const ChainSeg whole{nullptr, nullptr, nullptr, 0, nullptr};
 	if (al_env().trace) fprintf(stderr, "[airlift] trace: chain order: %llu fragments with tied chain starts among > 64 chains (%s keys), %u of them chained whole by the wavefront kernel\n", (unsigned long long)c->n_chain_fallback, keep_keys ? "with" : "without", n_fb);
-	if (n_fb > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(n_fb), dim3(64), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_first.p, c->rd_len.p, c->chained.p, c->u.p, c->frag_nu.p,
-	                                 c->ws_i32.p, c->ws_u64.p, fb, (int)n_fb, c->P, c->counters.p, whole);
+	if (n_fb > 0) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain<AL_CHAIN_CAP>), dim3(n_fb), dim3(64), 0, s, B.anchors, B.a_off, B.frag_na, B.frag_first, B.rd_len, B.chained, B.u, B.frag_nu,
+	                                 R.ws_i32.p, R.ws_u64.p, fb, (int)n_fb, c->P, c->counters.p, whole);
 	c->chain_who[CW_WHOLE_WAVE] += n_fb;
 	if (ev(ST_SEG_MERGE)) return -1;
 	return 0;
 }
 
 // The segment-wise kernels on fragments list[0 .. n) of the batch arrays (option values outside the tile kernel's range), then uo[].
-static int chain_legacy(al_ctx_t *c, const uint32_t *list, int n, bool lds_ok, const uint32_t *skip_flag)
+static int chain_legacy(al_ctx_t *c, const ChainRound &R, const uint32_t *list, int n, bool lds_ok, const uint32_t *skip_flag)
 {
 	if (n <= 0) return 0;
 	c->chain_who[CW_LEGACY_FRAGS] += (uint64_t)n;
-	const uint64_t total = c->n_anchor_total;
-	if (c->ws_i32.ensure(total * 4 + 4, false, c->stream) || c->ws_u64.ensure(total + 1, false, c->stream) ||
-	    c->chain_tmp.ensure(total + 1, false, c->stream) || c->u_tmp.ensure(total + 1, false, c->stream) || c->okey_tmp.ensure(total + 2, false, c->stream)) return -1;
-	if (chain_by_segments(c, list, n, lds_ok, false, skip_flag)) return -1;
-	hipLaunchKernelGGL(k_uo_fill, dim3(n), dim3(64), 0, c->stream, list, n, c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, skip_flag);
+	const uint64_t total = R.n_anchor;
+	if (R.need(R.ws_i32, total * 4 + 4) || R.need(R.ws_u64, total + 1) ||
+	    R.need(R.chain_tmp, total + 1) || R.need(R.u_tmp, total + 1) || R.need(R.okey_tmp, total + 2)) return -1;
+	if (chain_by_segments(c, R, batch_ptrs(c), list, n, lds_ok, false, skip_flag)) return -1;
+	hipLaunchKernelGGL(k_uo_fill, dim3(n), dim3(64), 0, R.s, list, n, c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, skip_flag);
 	return 0;
 }
 
@@ -518,76 +596,80 @@ static int chain_legacy(al_ctx_t *c, const uint32_t *list, int n, bool lds_ok, c
 // chain starts among more than 64 chains): a compact copy of their anchors becomes a small virtual batch -- fragment v of the list is
 // fragment v there -- which the segment-wise kernels chain (their per-anchor scratch is sized for this copy, not for the batch); the
 // results go back to the fragments' places with their uo[].
-static int chain_fallback(al_ctx_t *c, const uint32_t *fb, int n_fb, bool lds_ok)
+static int chain_fallback(al_ctx_t *c, const ChainRound &R, const uint32_t *fb, int n_fb, bool lds_ok)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = R.s;
 	if (n_fb <= 0) return 0;
 	c->chain_who[CW_FALLBACK_FRAGS] += (uint64_t)n_fb;
-	if (c->v_na.ensure((size_t)n_fb + 2) || c->v_nseg.ensure((size_t)n_fb + 2) || c->v_a_off.ensure((size_t)n_fb + 2) || c->v_first64.ensure((size_t)n_fb + 2) ||
-	    c->v_first.ensure((size_t)n_fb + 2) || c->v_rd_len.ensure(2 * (size_t)n_fb + 2) || c->v_order.ensure((size_t)n_fb + 2) || c->v_nu.ensure((size_t)n_fb + 2)) return -1;
-	hipLaunchKernelGGL(k_fb_meta, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_na.p, c->frag_first.p, c->v_na.p, c->v_nseg.p);
-	if (scan_u32_to_u64(c, c->v_na.p, c->v_a_off.p, n_fb) || scan_u32_to_u64(c, c->v_nseg.p, c->v_first64.p, n_fb)) return -1;
+	if (R.need(R.v_na, (size_t)n_fb + 2) || R.need(R.v_nseg, (size_t)n_fb + 2) || R.need(R.v_a_off, (size_t)n_fb + 2) || R.need(R.v_first64, (size_t)n_fb + 2) ||
+	    R.need(R.v_first, (size_t)n_fb + 2) || R.need(R.v_rd_len, 2 * (size_t)n_fb + 2) || R.need(R.v_order, (size_t)n_fb + 2) || R.need(R.v_nu, (size_t)n_fb + 2)) return -1;
+	hipLaunchKernelGGL(k_fb_meta, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_na.p, c->frag_first.p, R.v_na.p, R.v_nseg.p);
+	if (R.scan(R.v_na.p, R.v_a_off.p, n_fb) || R.scan(R.v_nseg.p, R.v_first64.p, n_fb)) return -1;
 	uint64_t vt = 0;
-	AL_HIP_CHECK(hipMemcpyAsync(&vt, c->v_a_off.p + n_fb, 8, hipMemcpyDeviceToHost, s));
-	AL_HIP_CHECK(hipStreamSynchronize(s));
+	if (R.fetch(&vt, R.v_a_off.p + n_fb, 8)) return -1;
 	if (al_env().trace) fprintf(stderr, "[airlift] trace: chain fallback: %d fragments, %llu anchors, through the segment-wise kernels\n", n_fb, (unsigned long long)vt);
-	if (c->v_anchors.ensure(vt + 1, false, s) || c->v_chained.ensure(vt + 1, false, s) || c->v_u.ensure(vt + (uint64_t)n_fb + 2, false, s) ||
-	    c->ws_i32.ensure(vt * 4 + 4, false, s) || c->ws_u64.ensure(vt + 1, false, s) || c->chain_tmp.ensure(vt + 1, false, s) || c->u_tmp.ensure(vt + 1, false, s) || c->okey_tmp.ensure(vt + 2, false, s)) return -1;
-	hipLaunchKernelGGL(k_fb_reads, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_first.p, c->rd_len.p, c->v_first64.p, c->v_first.p, c->v_rd_len.p, c->v_order.p);
-	hipLaunchKernelGGL(k_fb_copy_in, dim3(n_fb), dim3(64), 0, s, fb, n_fb, c->a_off.p, c->frag_na.p, c->anchors.p, c->v_a_off.p, c->v_anchors.p);
-	// the virtual batch stands in for the batch arrays while the segment-wise kernels run
-	AlAnchor *const sv_anchors = c->anchors.p, *const sv_chained = c->chained.p; uint64_t *const sv_a_off = c->a_off.p, *const sv_u = c->u.p;
-	uint32_t *const sv_na = c->frag_na.p, *const sv_first = c->frag_first.p, *const sv_rd_len = c->rd_len.p, *const sv_nu = c->frag_nu.p;
-	c->anchors.p = c->v_anchors.p; c->chained.p = c->v_chained.p; c->a_off.p = c->v_a_off.p; c->u.p = c->v_u.p;
-	c->frag_na.p = c->v_na.p; c->frag_first.p = c->v_first.p; c->rd_len.p = c->v_rd_len.p; c->frag_nu.p = c->v_nu.p;
-	const int rc = chain_by_segments(c, c->v_order.p, n_fb, lds_ok, false, nullptr, true);   // (with the processing keys at once: most of these fragments were handed back for tied chain starts, which need them -- one pass instead of two)
-	c->anchors.p = sv_anchors; c->chained.p = sv_chained; c->a_off.p = sv_a_off; c->u.p = sv_u;
-	c->frag_na.p = sv_na; c->frag_first.p = sv_first; c->rd_len.p = sv_rd_len; c->frag_nu.p = sv_nu;
+	if (R.need(R.v_anchors, vt + 1) || R.need(R.v_chained, vt + 1) || R.need(R.v_u, vt + (uint64_t)n_fb + 2) ||
+	    R.need(R.ws_i32, vt * 4 + 4) || R.need(R.ws_u64, vt + 1) || R.need(R.chain_tmp, vt + 1) || R.need(R.u_tmp, vt + 1) || R.need(R.okey_tmp, vt + 2)) return -1;
+	hipLaunchKernelGGL(k_fb_reads, dim3((n_fb + 256) / 256), dim3(256), 0, s, fb, n_fb, c->frag_first.p, c->rd_len.p, R.v_first64.p, R.v_first.p, R.v_rd_len.p, R.v_order.p);
+	hipLaunchKernelGGL(k_fb_copy_in, dim3(n_fb), dim3(64), 0, s, fb, n_fb, c->a_off.p, c->frag_na.p, c->anchors.p, R.v_a_off.p, R.v_anchors.p);
+	// the virtual batch stands in for the batch arrays while the segment-wise kernels run: they take the arrays as an argument, the context's own stay where they
+	// are (the host may issue launches of the other round inside a wait of this one: ChainRound::idle)
+	const AlBatchPtrs vb{R.v_anchors.p, R.v_chained.p, R.v_a_off.p, R.v_u.p, R.v_na.p, R.v_first.p, R.v_rd_len.p, R.v_nu.p};
+	const int rc = chain_by_segments(c, R, vb, R.v_order.p, n_fb, lds_ok, false, nullptr, true);   // (with the processing keys at once: most of these fragments were handed back for tied chain starts, which need them -- one pass instead of two)
 	if (rc) return -1;
-	hipLaunchKernelGGL(k_fb_copy_out, dim3(n_fb), dim3(64), 0, s, fb, n_fb, c->a_off.p, c->v_a_off.p, c->v_nu.p, c->v_u.p, c->v_chained.p, c->frag_nu.p, c->u.p, c->uo.p, c->chained.p);
+	hipLaunchKernelGGL(k_fb_copy_out, dim3(n_fb), dim3(64), 0, s, fb, n_fb, c->a_off.p, R.v_a_off.p, R.v_nu.p, R.v_u.p, R.v_chained.p, c->frag_nu.p, c->u.p, c->uo.p, c->chained.p);
 	return 0;
 }
 
 // The tile kernel over the items of S (list entries grouped by size class): it chains the segments of up to 8 anchors itself and defers the
 // longer ones, which the lane-per-segment kernels take by size class across all fragments (64 equally long segments per wavefront) and write
 // straight to the fragments' arrays; k_u_compact closes the unused reserve in the chain lists; then the fallback for what was handed back.
-static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, const uint32_t *skip_flag, int lmin, bool first, bool lds_ok)
+// beside: the caller's other round (the second round of the pass, on its stream), issued once the tile kernel is in flight, before this round's first host wait.
+// It gets a function to ask inside its own host waits (ChainRound::idle): once the tile kernel is over, the rest of this round -- everything from its first host
+// wait on -- is issued from there, so that neither round's kernels wait for a host that is blocked on the other round's stream.
+typedef std::function<int(const std::function<int()> *)> ChainBeside;
+static int chain_tiles(al_ctx_t *c, const ChainRound &R, const uint32_t *list, const TileSched &S, const uint32_t *skip_flag, int lmin, bool first, bool lds_ok, const ChainBeside *beside = nullptr)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = R.s; const AlBatchPtrs B = batch_ptrs(c);
 	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
-	uint32_t n_fb = 0;
+	uint32_t n_fb = 0, n_def_t = 0, n_cmp_t = 0; int n_cls_t = 0;   // (AL_TRACE: what the round reached)
+	uint32_t *const cnts = R.cnts;                                                // (the first round's: counters[16..17]) [0] handed back, [1] deferred segments, [2] fragments to compact
+	const size_t cap = (size_t)(R.n_anchor / 9) + 64;                            // a deferred segment has at least 9 anchors
 	if (S.n_items > 0) {
-		uint32_t *cnts = (uint32_t *)(c->counters.p + 16);                          // (counters[16..17]) [0] handed back, [1] deferred segments, [2] fragments to compact
 		const int force_fb = al_env().test_tile_fb ? 1 : 0;
-		const size_t cap = (size_t)(c->n_anchor_total / 9) + 64;                    // a deferred segment has at least 9 anchors
 		if (cap >= (1ULL << 31)) { fprintf(stderr, "[airlift] too many anchors in one batch for the deferred-segment list: upload fewer fragments\n"); al_nomem_flag() = true; return -1; }
-		if (c->vs_off.ensure(cap) || c->d_uslot.ensure(cap) || c->vs_na.ensure(cap) || c->vs_meta.ensure(cap) || c->d_rel.ensure(cap) || c->d_fragid.ensure(cap) || c->vs_cls.ensure(cap) ||
-		    c->cmp_list.ensure((size_t)c->n_frag + 2) || c->ctie.ensure((size_t)c->n_frag + 2)) return -1;
+		if (R.need(R.vs_off, cap) || R.need(R.d_uslot, cap) || R.need(R.vs_na, cap) || R.need(R.vs_meta, cap) || R.need(R.d_rel, cap) || R.need(R.d_fragid, cap) || R.need(R.vs_cls, cap) ||
+		    R.need(R.cmp_list, (size_t)R.n_frag_max + 2) || R.need(R.ctie, (size_t)c->n_frag + 2)) return -1;
 		AL_HIP_CHECK(hipMemsetAsync(cnts, 0, 16, s));
-		AL_HIP_CHECK(hipMemsetAsync(c->ctie.p, 0, ((size_t)c->n_frag + 1) * 4, s));
-		CtDefer D; D.off = c->vs_off.p; D.uslot = c->d_uslot.p; D.na = c->vs_na.p; D.meta = c->vs_meta.p; D.rel = c->d_rel.p; D.fragid = c->d_fragid.p; D.cls = c->vs_cls.p; D.cnt = cnts + 1; D.cap = (uint32_t)cap;
-		D.cmp_list = c->cmp_list.p; D.cmp_cnt = cnts + 2; D.ctie = c->ctie.p;
+		AL_HIP_CHECK(hipMemsetAsync(R.ctie.p, 0, ((size_t)c->n_frag + 1) * 4, s));
+		CtDefer D; D.off = R.vs_off.p; D.uslot = R.d_uslot.p; D.na = R.vs_na.p; D.meta = R.vs_meta.p; D.rel = R.d_rel.p; D.fragid = R.d_fragid.p; D.cls = R.vs_cls.p; D.cnt = cnts + 1; D.cap = (uint32_t)cap;
+		D.cmp_list = R.cmp_list.p; D.cmp_cnt = cnts + 2; D.ctie = R.ctie.p;
 		hipLaunchKernelGGL(k_chain_tile6, dim3(S.n_items), dim3(256), 0, s, c->anchors.p, c->a_off.p, c->frag_na.p, c->frag_meta.p, list, S, skip_flag,
-		                   c->chained.p, c->u.p, c->uo.p, c->frag_nu.p, c->fb_list.p, cnts, c->P, lmin, c->counters.p, force_fb, D);
+		                   c->chained.p, c->u.p, c->uo.p, c->frag_nu.p, R.fb_list.p, cnts, c->P, lmin, c->counters.p, force_fb, D);
 		if (ev(ST_SEG_FIND)) return -1;
-		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }   // the lane kernels of the small fragments (ovl1): done before their scratch is used again
+		if (c->ovl_pending && !R.own) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }   // the lane kernels of the small fragments (ovl1): done before their scratch is used again (the context's: a round with its own has no part in it)
+	} else if (ev(ST_SEG_FIND)) return -1;
+	if (beside) AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], s));                    // the tile kernel is over
+	// ---- from the first host wait on ----
+	auto finish = [&]() -> int {
+	if (S.n_items > 0) {
 		if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: tile kernel (%u items, first pass %d) -> %s\n", S.n_items, (int)first, hipGetErrorName(e)); }
 		uint32_t h[3] = {0, 0, 0};
-		AL_HIP_CHECK(hipMemcpyAsync(h, cnts, 12, hipMemcpyDeviceToHost, s));
-		AL_HIP_CHECK(hipStreamSynchronize(s));
-		const uint32_t n_def = h[1], n_cmp = h[2];
+		if (R.fetch(h, cnts, 12)) return -1;
+		const uint32_t n_def = h[1], n_cmp = h[2]; n_def_t = n_def; n_cmp_t = n_cmp;
 		c->chain_who[CW_TILE_ITEMS] += S.n_items; c->chain_who[CW_TILE_FRAGS] += S.ent[6] - S.ent[0]; c->chain_who[CW_DEFERRED] += n_def; c->chain_who[CW_COMPACTED] += n_cmp;
 		if (n_def > cap) { fprintf(stderr, "[airlift] deferred-segment list overflow (%u > %zu)\n", n_def, cap); return -1; }
 		if (n_def > 0) {
 			// the deferred segments by size class (stable: inside a class they keep the tiles' order, i.e. memory order inside a tile)
-			if (c->seg_key.ensure((size_t)n_def + 1) || c->seg_ord.ensure((size_t)n_def + 1) || c->seg_t1.ensure((size_t)n_def + 1)) return -1;
-			hipLaunchKernelGGL(k_iota_u32, dim3((n_def + 255) / 256), dim3(256), 0, s, c->seg_t1.p, n_def);
-			if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)c->vs_cls.p, c->seg_key.p, (const uint32_t *)c->seg_t1.p, c->seg_ord.p, (int)n_def, 0, 4, s); })) return -1;
+			if (R.need(R.seg_key, (size_t)n_def + 1) || R.need(R.seg_ord, (size_t)n_def + 1) || R.need(R.seg_t1, (size_t)n_def + 1)) return -1;
+			hipLaunchKernelGGL(k_iota_u32, dim3((n_def + 255) / 256), dim3(256), 0, s, R.seg_t1.p, n_def);
+			if (R.prim([&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint32_t *)R.vs_cls.p, R.seg_key.p, (const uint32_t *)R.seg_t1.p, R.seg_ord.p, (int)n_def, 0, 4, s); })) return -1;
 			static const uint32_t thr[8] = {1, 2, 3, 4, 5, 6, 7, 8};
 			uint32_t lb[8];
-			if (lower_bounds(c, c->seg_key.p, n_def, thr, 8, lb)) return -1;
+			if (lower_bounds(c, R.seg_key.p, n_def, thr, 8, lb, &R)) return -1;
 			const uint32_t cb[10] = {0, lb[0], lb[1], lb[2], lb[3], lb[4], lb[5], lb[6], lb[7], n_def};   // class k: entries [cb[k], cb[k + 1])
 			static const uint32_t capl0[9] = {16, 24, 32, 40, 48, 64, 80, 96, 128};
+			for (int k = 0; k < 9; ++k) n_cls_t += cb[k + 1] > cb[k];
 			// the long classes hold few segments, and a lane walks a 49 ... 128-anchor segment for half a millisecond whatever the launch holds: as long
 			// as they are thin they share ONE launch of the 128-anchor kernel (the list is ordered by class: their entries are one range)
 			// A class with many segments: the lane-per-segment kernel (64 equally long segments per wavefront, rows in LDS).  A lane walks a 17 ... 128-anchor
@@ -599,13 +681,13 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 			for (int k = 1; k < 9; ++k) thin[k] = coop_env == 1 || (coop_env != 0 && cb[k + 1] - cb[k] < 4096u);
 			uint32_t capl[9]; for (int k = 0; k < 9; ++k) capl[k] = thin[k] ? 0u : capl0[k];
 			size_t wsb[10]; wsb[0] = 0; for (int k = 0; k < 9; ++k) wsb[k + 1] = wsb[k] + (size_t)(cb[k + 1] - cb[k]) * capl[k];   // chain-end scratch: CAPL words per entry, by list position
-			if (c->ws_u64.ensure(wsb[9] + 64, false, s)) return -1;
+			if (R.need(R.ws_u64, wsb[9] + 64)) return -1;
 			if (al_env().trace && first) fprintf(stderr, "[airlift] trace: tile chaining: %u items, %u deferred segments (<=16:%u <=24:%u <=32:%u <=40:%u <=48:%u <=64:%u <=80:%u <=96:%u <=128:%u), %u fragments to compact\n", S.n_items, n_def,
 			                          cb[1] - cb[0], cb[2] - cb[1], cb[3] - cb[2], cb[4] - cb[3], cb[5] - cb[4], cb[6] - cb[5], cb[7] - cb[6], cb[8] - cb[7], cb[9] - cb[8], n_cmp);
-			ChainSeg sg{c->vs_meta.p, nullptr, nullptr, 0, nullptr, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p};
-#define LDEF(C, L, K) do { if (!thin[K]) LCH(C, L, -1, c->vs_off.p, c->vs_na.p, c->chained.p, c->u.p, (uint32_t *)nullptr, c->seg_ord.p + cb[K], (int)(cb[K + 1] - cb[K]), sg, c->uo.p, c->ws_u64.p + wsb[K], C); } while (0)
+			ChainSeg sg{R.vs_meta.p, nullptr, nullptr, 0, nullptr, R.d_uslot.p, R.d_rel.p, R.d_fragid.p, R.ctie.p};
+#define LDEF(C, L, K) do { if (!thin[K]) LCH(C, L, -1, R.vs_off.p, R.vs_na.p, c->chained.p, c->u.p, (uint32_t *)nullptr, R.seg_ord.p + cb[K], (int)(cb[K + 1] - cb[K]), sg, c->uo.p, R.ws_u64.p + wsb[K], C); } while (0)
 			// (round 5) the classes on two streams in turn, like the lane kernels of the small fragments (ovl2 is idle here: they were joined above); AL_CHAIN_OVL2=0: all on this one
-			const bool two = al_env().chain_ovl2 && c->n_frag < 400000;                          // (a 1 M-pair batch's classes fill the chip: no gain there, C5 slightly slower)
+			const bool two = al_env().chain_ovl2 && c->n_frag < 400000 && !R.own;                        // (a 1 M-pair batch's classes fill the chip: no gain there, C5 slightly slower)
 			hipStream_t const s_cls[2] = {s, two ? c->on(AL_ROLE_OVL2) : s};
 			if (two) { AL_HIP_CHECK(hipEventRecord(c->ev_ovl[4], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_OVL2), c->ev_ovl[4], 0)); }
 			{ int turn = 0;
@@ -620,31 +702,49 @@ static int chain_tiles(al_ctx_t *c, const uint32_t *list, const TileSched &S, co
 				const int nn = (int)(cb[k1 + 1] - cb[k]);
 				if (nn > 0) {
 					c->chain_who[CW_DEFERRED_COOP] += (uint64_t)nn;
-					if (k1 <= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<48>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, c->vs_off.p, c->vs_na.p, c->vs_meta.p, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p,
-					                                (const uint32_t *)c->seg_ord.p + cb[k], nn, c->P, c->counters.p);
-					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<128>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, c->vs_off.p, c->vs_na.p, c->vs_meta.p, c->d_uslot.p, c->d_rel.p, c->d_fragid.p, c->ctie.p,
-					                        (const uint32_t *)c->seg_ord.p + cb[k], nn, c->P, c->counters.p);
+					if (k1 <= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<48>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, R.vs_off.p, R.vs_na.p, R.vs_meta.p, R.d_uslot.p, R.d_rel.p, R.d_fragid.p, R.ctie.p,
+					                                (const uint32_t *)R.seg_ord.p + cb[k], nn, c->P, c->counters.p);
+					else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_chain_coop<128>), dim3((nn + 3) / 4), dim3(64), 0, s, c->anchors.p, c->chained.p, c->u.p, c->uo.p, R.vs_off.p, R.vs_na.p, R.vs_meta.p, R.d_uslot.p, R.d_rel.p, R.d_fragid.p, R.ctie.p,
+					                        (const uint32_t *)R.seg_ord.p + cb[k], nn, c->P, c->counters.p);
 				}
 				k = k1 + 1;
 			}
 			if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: deferred segments (%u, first pass %d) -> %s\n", n_def, (int)first, hipGetErrorName(e)); }
 #undef LDEF
 		}
-		if (n_cmp > 0) hipLaunchKernelGGL(k_u_compact, dim3(std::min<uint32_t>(n_cmp, 8192u)), dim3(64), 0, s, (const uint32_t *)c->cmp_list.p, (const uint32_t *)(cnts + 2), c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, (const uint32_t *)c->ctie.p, c->fb_list.p, cnts);
+		if (n_cmp > 0) hipLaunchKernelGGL(k_u_compact, dim3(std::min<uint32_t>(n_cmp, 8192u)), dim3(64), 0, s, (const uint32_t *)R.cmp_list.p, (const uint32_t *)(cnts + 2), c->a_off.p, c->frag_nu.p, c->u.p, c->uo.p, (const uint32_t *)R.ctie.p, R.fb_list.p, cnts);
 		if (ev(ST_SEG_CHAIN_LDS)) return -1;
 		if (al_env().trace) { const hipError_t e = hipStreamSynchronize(s); fprintf(stderr, "[airlift] trace: compact (%u fragments) -> %s\n", n_cmp, hipGetErrorName(e)); }
-		if (n_cmp > 0) { AL_HIP_CHECK(hipMemcpyAsync(&n_fb, cnts, 4, hipMemcpyDeviceToHost, s)); AL_HIP_CHECK(hipStreamSynchronize(s)); } else n_fb = h[0];
-	} else if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
-	if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
+		if (n_cmp > 0) { if (R.fetch(&n_fb, cnts, 4)) return -1; } else n_fb = h[0];
+	} else if (ev(ST_SEG_CHAIN_LDS)) return -1;
+	if (c->ovl_pending && !R.own) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
+	if (al_env().trace) fprintf(stderr, "[airlift] trace: round %s (first pass %d): tile kernel on %u items, %u deferred segments in %d lane classes, %u fragments to compact, %u handed back\n", R.tag(), (int)first, S.n_items, n_def_t, n_cls_t, n_cmp_t, n_fb);
 	if (n_fb > 0) {
 		c->n_chain_fallback += n_fb; c->chain_who[CW_HANDED_BACK] += n_fb;
 		// (the list the kernels appended to atomically, in ascending fragment order: the same virtual batch on every run)
-		if (c->fbk_list.ensure((size_t)n_fb + 2)) return -1;
-		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->fb_list.p, c->fbk_list.p, (int)n_fb, 0, 32, s); })) return -1;
-		if (chain_fallback(c, c->fbk_list.p, (int)n_fb, lds_ok)) return -1;
+		if (R.need(R.fbk_list, (size_t)n_fb + 2)) return -1;
+		if (R.prim([&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)R.fb_list.p, R.fbk_list.p, (int)n_fb, 0, 32, s); })) return -1;
+		if (chain_fallback(c, R, R.fbk_list.p, (int)n_fb, lds_ok)) return -1;
 	}
 	if (ev(ST_SEG_CHAIN_WAVE)) return -1;
 	return 0;
+	};
+	if (!beside) return finish();
+	int fin = 1; bool fin_nomem = false;                                          // 1: not run yet, else finish()'s result
+	const std::function<int()> idle = [&]() -> int {
+		if (fin != 1) return 1;
+		const hipError_t q = hipEventQuery(c->ev_fj[1]);
+		if (q == hipErrorNotReady) return 0;
+		if (q != hipSuccess) return -1;
+		const bool nomem0 = al_nomem_flag(); al_nomem_flag() = false;              // (an allocation finish() cannot make is this round's: the other round's own test of the flag must not take it for its own)
+		fin = finish();
+		fin_nomem = al_nomem_flag(); al_nomem_flag() = nomem0;
+		return 1;
+	};
+	const int rc = (*beside)(&idle);
+	if (fin_nomem) al_nomem_flag() = true;
+	if (rc) return -1;
+	return fin != 1 ? fin : finish();
 }
 
 // ---- the chaining half of a pass (run_seed_chain), in the pieces the al_dbg_chain tap runs too --------------------------------------------
@@ -712,7 +812,7 @@ static int chain_plan(al_ctx_t *c, const uint32_t *list, int nl, bool first, Cha
 // fragments of up to 128 anchors: the lane-per-fragment kernels
 static int chain_small(al_ctx_t *c, const ChainPlan &pl)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = c->stream; const AlBatchPtrs B = batch_ptrs(c);
 	const uint32_t *const order = pl.order; const bool lds_ok = pl.lds_ok;
 	const uint32_t lb65 = pl.lb65, lb81 = pl.lb81, lb97 = pl.lb97, lb129 = pl.lb129, tile_from = pl.tile_from;
 	const ChainSeg nosg{nullptr, nullptr, (const uint32_t *)c->tie_list.p, 1, nullptr};
@@ -759,9 +859,9 @@ static int chain_small(al_ctx_t *c, const ChainPlan &pl)
 }
 
 // everything else: the tile kernel, or (option values outside its range) the segment-wise kernels
-static int chain_large(al_ctx_t *c, const ChainPlan &pl)
+static int chain_large(al_ctx_t *c, const ChainPlan &pl, const ChainBeside *beside = nullptr /* chain_tiles: tiles_ok only */)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = c->stream; const ChainRound R = round_main(c, beside != nullptr);
 	const bool first = pl.first, lds_ok = pl.lds_ok, tiles_ok = pl.tiles_ok; const int nl = pl.nl, lmin = pl.lmin;
 	const uint32_t *const order = pl.order;
 	const uint32_t tile_from = pl.tile_from, lb33 = pl.lb33, lb65 = pl.lb65, lb129 = pl.lb129, lb257x = pl.lb257x, lb513x = pl.lb513x;
@@ -774,43 +874,89 @@ static int chain_large(al_ctx_t *c, const ChainPlan &pl)
 		for (int k = 0; k < 6; ++k) S.ent[k] = b[k]; S.ent[6] = (uint32_t)nl;
 		S.item[0] = 0; for (int k = 0; k < 6; ++k) { const uint32_t per = 32u >> k; S.item[k + 1] = S.item[k] + (S.ent[k + 1] - S.ent[k] + per - 1) / per; }
 		S.n_items = S.item[6];
-		if (chain_tiles(c, order, S, (const uint32_t *)c->tie_list.p, lmin, first, lds_ok)) return -1;
+		if (chain_tiles(c, R, order, S, (const uint32_t *)c->tie_list.p, lmin, first, lds_ok, beside)) return -1;
 	} else {
 		if (ev(ST_SEG_FIND) || ev(ST_SEG_CHAIN_LDS)) return -1;
 		if (c->ovl_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_ovl[3], 0)); c->ovl_pending = false; }
 		const uint32_t tail = lds_ok ? lb129 : 0u;
-		if (chain_legacy(c, order + tail, nl - (int)tail, lds_ok, (const uint32_t *)c->tie_list.p)) return -1;
+		if (chain_legacy(c, R, order + tail, nl - (int)tail, lds_ok, (const uint32_t *)c->tie_list.p)) return -1;
 		if (ev(ST_SEG_CHAIN_WAVE)) return -1;
 	}
 	return 0;
 }
 
-// second round: the flagged fragments (their anchors merged on the side stream), a fragment per item, any size
-static int chain_ties(al_ctx_t *c, const ChainPlan &pl)
+// second round: the flagged fragments (their anchors merged on the side stream), a fragment per item, any size.  beside: on the side stream -- behind the merges
+// in stream order -- with the scratch set al_ctx_s::tie2, while the first round's tile kernel runs on main; else on main with the context's scratch, the first
+// round being over.  Either way it writes only the flagged fragments' places of chained[], u[], uo[] and frag_nu[], which the first round skips.
+static int chain_ties(al_ctx_t *c, const ChainPlan &pl, bool beside, const char *why_after = "", const std::function<int()> *idle = nullptr)
 {
-	hipStream_t s = c->stream;
+	hipStream_t s = beside ? c->on(AL_ROLE_SIDE) : c->stream;
 	const bool first = pl.first, lds_ok = pl.lds_ok, tiles_ok = pl.tiles_ok; const int nl = pl.nl, lmin = pl.lmin;
 	const uint32_t *const order = pl.order;
-	auto ev = [&](int st) -> int { if (first) AL_HIP_CHECK(hipEventRecord(c->ev[st + 1], s)); return 0; };
 	if (c->tie_frags.ensure((size_t)nl + 2)) return -1;
-	uint32_t *cnt = (uint32_t *)(c->counters.p + 15);
-	AL_HIP_CHECK(hipMemsetAsync(cnt, 0, 8, s));
-	hipLaunchKernelGGL(k_collect_flagged, dim3((nl + 255) / 256), dim3(256), 0, s, order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, cnt);
-	uint32_t n_tie = 0, n_spec_used = 0;
-	AL_HIP_CHECK(hipMemcpyAsync(&n_tie, cnt, 4, hipMemcpyDeviceToHost, s));
+	// the fragments' count and, for a scratch set of the round's own, their anchors (its deferred-segment arrays are sized from them): one copy back
+	uint32_t *cnt = (uint32_t *)(c->counters.p + 15); unsigned long long *sum = nullptr;
+	if (beside) { if (c->tie2.cnt.ensure(16)) return -1; cnt = c->tie2.cnt.p + 8; sum = (unsigned long long *)(c->tie2.cnt.p + 10); }
+	AL_HIP_CHECK(hipMemsetAsync(cnt, 0, beside ? 16 : 8, s));
+	hipLaunchKernelGGL(k_collect_flagged, dim3((nl + 255) / 256), dim3(256), 0, s, order, nl, (const uint32_t *)c->tie_list.p, c->tie_frags.p, cnt, (const uint32_t *)c->frag_na.p, sum);
+	uint32_t h[4] = {0, 0, 0, 0}, n_spec_used = 0;
+	if (idle && chain_wait(s, idle)) return -1;                                  // (the merges may outlast the first round's tile kernel: its rest is issued from inside this wait then)
+	AL_HIP_CHECK(hipMemcpyAsync(h, cnt, beside ? 16 : 4, hipMemcpyDeviceToHost, s));
 	if (!first && c->n_spec > 0) AL_HIP_CHECK(hipMemcpyAsync(&n_spec_used, c->spec_cnt.p + 2, 4, hipMemcpyDeviceToHost, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
+	const uint32_t n_tie = h[0]; const uint64_t n_tie_anchor = (uint64_t)h[2] | (uint64_t)h[3] << 32;
 	if (!first && c->n_spec > 0) c->spec_idle = n_spec_used ? 0u : c->spec_idle + 1u;
 	c->chain_who[CW_TIE_ROUND] += n_tie;
+	if (al_env().trace) fprintf(stderr, "[airlift] trace: second round (first pass %d): %u equal-x fragments chained %s the first round%s\n", (int)first, n_tie, beside ? "beside" : "after", beside ? "" : why_after);
 	if (n_tie > 0) {
-		if (c->tie_sorted.ensure((size_t)n_tie + 2)) return -1;
-		if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s); })) return -1;   // ascending fragment ids: a deterministic order (the collection above appends atomically)
+		ChainRound R = beside ? round_beside(c, n_tie_anchor, (int)n_tie) : round_main(c);
+		R.idle = idle;
+		if (c->tie_sorted.ensure((size_t)n_tie + 2) || (beside && R.need(R.fb_list, (size_t)n_tie + 2))) return -1;
+		if (R.prim([&](void *t, size_t &b) { return rocprim::radix_sort_keys(t, b, (const uint32_t *)c->tie_frags.p, c->tie_sorted.p, (int)n_tie, 0, 32, s); })) return -1;   // ascending fragment ids: a deterministic order (the collection above appends atomically)
 		if (tiles_ok) {
 			TileSched S; for (int k = 0; k < 6; ++k) { S.ent[k] = 0; S.item[k] = 0; } S.ent[6] = n_tie; S.item[6] = n_tie; S.n_items = n_tie;   // a fragment per item, any size
-			if (chain_tiles(c, c->tie_sorted.p, S, nullptr, lmin, false, lds_ok)) return -1;
-		} else if (chain_legacy(c, c->tie_sorted.p, (int)n_tie, lds_ok, nullptr)) return -1;
+			if (chain_tiles(c, R, c->tie_sorted.p, S, nullptr, lmin, false, lds_ok)) return -1;
+		} else if (chain_legacy(c, R, c->tie_sorted.p, (int)n_tie, lds_ok, nullptr)) return -1;
 	}
-	if (ev(ST_SEG_MERGE)) return -1;
+	return 0;
+}
+
+// The two rounds of a pass after chain_small.  merged: recorded on the side stream when the equal-x fragments' anchors are in place (the heap merges; nullptr in
+// the al_dbg_chain tap, whose anchors are the caller's).  The second round needs nothing of the first, so where the side stream is a stream of its own it is issued
+// from inside the first round -- after the tile kernel's launch, before the first host wait on main -- and main joins the side stream at the end; the chain_ties
+// interval then holds that join alone.  AL_CHAIN_OVL=0, one physical stream, the segment-wise kernels in the first round's place (no tile kernel to hide behind), or
+// a scratch set that does not fit: the second round on main after the first, in the context's scratch.
+static int chain_rounds(al_ctx_t *c, const ChainPlan &pl, hipEvent_t merged)
+{
+	hipStream_t const s = c->stream, side = c->on(AL_ROLE_SIDE);
+	const bool first = pl.first;
+	const bool want_beside = al_env().chain_ovl && side != s && pl.tiles_ok;
+	bool done = false, no_room = false;
+	// (the tap: the list and the fragments' arrays were made on main; forked here, before the first round's launches, so that the second round starts at once)
+	if (want_beside && !merged) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(side, c->ev_fj[0], 0)); }
+	const ChainBeside beside = [&](const std::function<int()> *idle) -> int {
+		uint64_t who[CW_N]; for (int i = 0; i < CW_N; ++i) who[i] = c->chain_who[i];
+		const uint64_t fb0 = c->n_chain_fallback; const uint32_t idle0 = c->spec_idle; const bool nomem0 = al_nomem_flag();
+		if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(side, c->ev_spec[1], 0)); c->spec_pending = false; }     // the slots of the merges made ahead, copied in on their own stream
+		if (chain_ties(c, pl, true, "", idle) == 0) { done = true; return 0; }
+		if (!al_nomem_flag() || nomem0) return -1;
+		// the second set did not fit (a batch that fills the memory): not an out-of-memory batch -- the round runs after the first one, where the context's scratch is
+		// free again, and writes all of its fragments' results anew
+		(void)hipStreamSynchronize(side); (void)hipGetLastError();
+		c->tie2.release(); al_nomem_flag() = false; no_room = true;
+		for (int i = 0; i < CW_N; ++i) c->chain_who[i] = who[i];
+		c->n_chain_fallback = fb0; c->spec_idle = idle0;
+		if (al_env().trace) fprintf(stderr, "[airlift] trace: second round (first pass %d): no room for a scratch set of its own\n", (int)first);
+		return 0;
+	};
+	if (chain_large(c, pl, want_beside ? &beside : nullptr)) return -1;
+	if (done) { AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], side)); AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0)); }
+	else {
+		if (merged) AL_HIP_CHECK(hipStreamWaitEvent(s, merged, 0));
+		if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
+		if (chain_ties(c, pl, false, !al_env().chain_ovl ? " (AL_CHAIN_OVL=0)" : side == s ? " (one stream)" : !pl.tiles_ok ? " (no tile kernel to run beside)" : no_room ? " (no room for a scratch set of its own)" : "")) return -1;
+	}
+	if (first) AL_HIP_CHECK(hipEventRecord(c->ev[ST_SEG_MERGE + 1], s));
 	return 0;
 }
 
@@ -1056,11 +1202,12 @@ static int run_seed_chain(al_ctx_t *c, const uint32_t *list, int n_list, int max
 		AL_HIP_CHECK(hipEventRecord(evs[1], c->on(AL_ROLE_SIDE)));
 		if (ev(ST_ANCHOR_HEAP)) return -1;
 	}
-	if (chain && chain_large(c, pl)) return -1;
-	// second round: the fragments whose anchors the side stream merged, any size
-	AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_side[first ? 1 : 3], 0));
-	if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
-	if (chain && chain_ties(c, pl)) return -1;
+	// the first round, and the second: the fragments whose anchors the side stream merged, any size
+	if (chain) { if (chain_rounds(c, pl, c->ev_side[first ? 1 : 3])) return -1; }
+	else {
+		AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_side[first ? 1 : 3], 0));
+		if (!first && c->spec_pending) { AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_spec[1], 0)); c->spec_pending = false; }
+	}
 	AL_HIP_CHECK(hipGetLastError());
 	return 0;
 }
@@ -1236,7 +1383,7 @@ extern "C" int al_dbg_chain(al_ctx_t *c, const uint64_t *anchors_xy, const uint6
 	ChainPlan pl;
 	if (chain_plan(c, nullptr, nf, true, pl)) return -1;
 	AL_HIP_CHECK(hipEventRecord(c->ev_ovl[2], s));                           // what the lane kernels' streams wait for: here, the anchors in place
-	if (chain_small(c, pl) || chain_large(c, pl) || chain_ties(c, pl)) return -1;
+	if (chain_small(c, pl) || chain_rounds(c, pl, nullptr)) return -1;
 	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) AL_HIP_CHECK(hipStreamSynchronize(c->phys[p]));
 	AL_HIP_CHECK(hipStreamSynchronize(s));
 	AL_HIP_CHECK(hipGetLastError());
