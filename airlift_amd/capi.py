@@ -173,6 +173,12 @@ def load():
         L.al_map_tokens_chain_regions.argtypes = [vp, cs, ci, ci, ci, C.POINTER(MapOpt), ci, vp, vp, ci, vp, vp, vp]; L.al_map_tokens_chain_regions.restype = ci
         for f in (L.al_dbg_chainreg, L.al_dbg_chainreg_host):
             f.argtypes = [C.c_uint64, u32p, u32p, u32p, u32p, u32, u32p, u32p, u32, u32p, C.c_uint64, u32p, u32p, u32p, u32, u32p, u32p, ci, ci, u32p, u64p, u32p, u64p, u32p, u64p]; f.restype = ci
+    if hasattr(L, "al_chain_exact"):   # (chain-exact verify|build: the exact chain file, and its test taps)
+        u8p = C.POINTER(C.c_uint8); u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64); u32 = C.c_uint32; u64 = C.c_uint64
+        L.al_chain_exact.argtypes = [cs, cs, cs, ci, ci, vp, C.c_uint, ci]; L.al_chain_exact.restype = ci
+        for f in (L.al_dbg_chainexact, L.al_dbg_chainexact_host):
+            f.argtypes = [u8p, u64, u8p, u64, u64, u32p, u32p, u32p, u32p, u32p, u32, u64p, u64p, u32p, ci, ci, u32p, u32p, u64, u64p, u32p, u64, u64p, u32p, u64, u64p, u32p]; f.restype = ci
+        L.al_dbg_chainexact_tile.argtypes = []; L.al_dbg_chainexact_tile.restype = u32
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

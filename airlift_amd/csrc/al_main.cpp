@@ -20,6 +20,8 @@
 //                                                                   retired / constant regions come from the same process (get_retired_regions.py :68, get_constant_regions.py :79)
 //          airlift-align chain-beds --read-size R [--max-errors E] [--gaps-out FILE] [--constant-bed FILE] [--merged-in MERGED.bed --retired-bed FILE] [--host] [--device D] CHAIN
 //                                                                   the three scripts alone, file for file
+//          airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] OLD.fa NEW.fa CHAIN
+//                                                                   run/1_build_exact_chain_file.py: the exact chain file those scripts assume, verified or built on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -109,6 +111,8 @@ static int usage()
 	                "chain-beds: airlift-align chain-beds --read-size R [--max-errors E] [--gaps-out FILE] [--constant-bed FILE] [--merged-in MERGED.bed --retired-bed FILE] [--host]\n"
 	                "       [--device D] chain  (the three scripts alone; at least one output, '-' is stdout for one of them; --gaps-out needs --max-errors, --retired-bed needs\n"
 	                "       --merged-in; --host: the kernels' host twin, no device is opened; malformed input is refused as FILE:LINE: reason)\n"
+	                "chain-exact: airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] old.fa new.fa chain  (1_build_exact_chain_file.py: the two\n"
+	                "       references compared over every block of the chain file on the GPU; verify prints the mismatch lines or PASS VERIFICATION, build the exact chain file)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -172,6 +176,34 @@ int main(int argc, char **argv)
 			if ((o == stdout ? fflush(o) : fclose(o)) == EOF) rc2 = 1;
 		};
 		copy_out(tg, g_fn); copy_out(tc, c_fn); copy_out(tr, r_fn);
+		fflush(stderr);
+		_exit(rc2);
+	}
+	if (!strcmp(argv[1], "chain-exact")) {         // run/1_build_exact_chain_file.py verify|build old.fa new.fa chain
+		int M = 100, dev = -1; unsigned cf = 0; const char *o_fn = nullptr; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "--min-region") && j + 1 < argc) M = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "-o") && j + 1 < argc) o_fn = argv[++j];
+			else if (!strcmp(argv[j], "--host")) cf |= AL_CHAIN_HOST;
+			else p.push_back(argv[j]);
+		}
+		const int mode = p.size() == 4 && !strcmp(p[0], "verify") ? AL_CEX_VERIFY : p.size() == 4 && !strcmp(p[0], "build") ? AL_CEX_BUILD : -1;
+		if (mode < 0) { fprintf(stderr, "Usage: airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] old.fa new.fa chain\n"); return 1; }
+		if (M < 1) { fprintf(stderr, "[ERROR] chain-exact: --min-region must be positive\n"); return 1; }
+		// the output is buffered and opened only once the text exists: a refused input writes nothing
+		FILE *t = tmpfile();
+		if (!t) { perror("[ERROR] chain-exact: tmpfile"); return 1; }
+		int rc2 = al_chain_exact(p[1], p[2], p[3], mode, M, t, cf, dev) == 0 ? 0 : 1;
+		if (!rc2) {
+			FILE *o = o_fn && strcmp(o_fn, "-") ? fopen(o_fn, "wb") : stdout;
+			if (!o) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", o_fn); rc2 = 1; }
+			else {
+				char buf[1 << 16]; size_t k; rewind(t);
+				while ((k = fread(buf, 1, sizeof(buf), t)) > 0) if (fwrite(buf, 1, k, o) != k) { rc2 = 1; break; }
+				if ((o == stdout ? fflush(o) : fclose(o)) == EOF) rc2 = 1;
+			}
+		}
 		fflush(stderr);
 		_exit(rc2);
 	}

@@ -438,6 +438,33 @@ int  al_dbg_chainreg_host(uint64_t n, const uint32_t *chain, const uint32_t *siz
                           uint32_t n_slot, const uint32_t *L, uint64_t n_m, const uint32_t *m_slot, const uint32_t *m_start, const uint32_t *m_end, uint32_t n_rslot, const uint32_t *rslot_of, const uint32_t *RL,
                           int R, int E, uint32_t *o_gaps, uint64_t *n_gaps, uint32_t *o_constant, uint64_t *n_constant, uint32_t *o_retired, uint64_t *n_retired);
 
+/* ---- the exact chain file (chain-exact verify|build): run/1_build_exact_chain_file.py ----
+ * The old reference (the headers' tName .. tEnd) and the new one (qName .. qEnd) are compared base by base over every block of `chain_fn` on `device` (-1:
+ * the default device), or with AL_CHAIN_HOST in `flags` by the kernels' host twin, which opens no device.  `out` receives the bytes the script prints:
+ *   AL_CEX_VERIFY  a line "mismatch: E errors in SIZE blocktarget: QNAME header: ..." per block with mismatches, or "PASS VERIFICATION"
+ *   AL_CEX_BUILD   the chain file rebuilt: every block cut at its mismatches, stretches shorter than `min_region` (the script: 100) folded into the gaps,
+ *                  heads and tails moved into the headers; chains in the script's order (first appearance of tName, of qName, of tStart)
+ * Refused as FILE:LINE: reason with -1: what al_chain_beds refuses of a chain file (qStrand may be '-'), a header number that is none, a chain whose last
+ * line is not 1-field, two headers with the same (tName, qName, tStart), a contig name twice in a FASTA, a 'U' or 'u' among the bases, on a '-' chain a
+ * block that leaves the new contig or a new-side byte other than acgtnACGTN, and in build a name the FASTA lacks or a block that ends beyond its contig
+ * (there the script prints a one-line message and no chain). */
+#define AL_CEX_VERIFY 0
+#define AL_CEX_BUILD 1
+int  al_chain_exact(const char *old_fa, const char *new_fa, const char *chain_fn, int mode, int min_region, FILE *out, unsigned flags, int device);
+/* Test taps of the comparison on two texts and a block table: blocks {chain, size, dt, dq, three} in output order, chains {c_old0, c_new0: the text
+ * offsets of the first block's first base (c_new0: its last on the new side where c_dir is 1), c_dir}.  Through the kernels on the current device
+ * (al_dbg_chainexact) or their host twin (al_dbg_chainexact_host).  o_cnt[n]: mismatches per block; *o_flag: 1 when a '-' block meets a new-side byte
+ * other than acgtn -- then nothing else is said.  With `build`: the positions as pairs block, idx (room for cap_pos pairs), the lines after pass 1 and
+ * after pass 2 as chain, size, dt, dq, three (room for cap_l1 / cap_l2 lines).  -1: arguments, or a table that breaks what the table builder
+ * guarantees; -4: an output has too little room.  al_dbg_chainexact_tile: the bases of a block that one wavefront compares. */
+int  al_dbg_chainexact(const uint8_t *old_text, uint64_t n_old, const uint8_t *new_text, uint64_t n_new, uint64_t n, const uint32_t *chain, const uint32_t *size, const uint32_t *dt, const uint32_t *dq,
+                       const uint32_t *three, uint32_t n_chain, const uint64_t *c_old0, const uint64_t *c_new0, const uint32_t *c_dir, int build, int min_region, uint32_t *o_cnt, uint32_t *o_pos,
+                       uint64_t cap_pos, uint64_t *n_pos, uint32_t *o_l1, uint64_t cap_l1, uint64_t *n_l1, uint32_t *o_l2, uint64_t cap_l2, uint64_t *n_l2, uint32_t *o_flag);
+int  al_dbg_chainexact_host(const uint8_t *old_text, uint64_t n_old, const uint8_t *new_text, uint64_t n_new, uint64_t n, const uint32_t *chain, const uint32_t *size, const uint32_t *dt, const uint32_t *dq,
+                            const uint32_t *three, uint32_t n_chain, const uint64_t *c_old0, const uint64_t *c_new0, const uint32_t *c_dir, int build, int min_region, uint32_t *o_cnt, uint32_t *o_pos,
+                            uint64_t cap_pos, uint64_t *n_pos, uint32_t *o_l1, uint64_t cap_l1, uint64_t *n_l1, uint32_t *o_l2, uint64_t cap_l2, uint64_t *n_l2, uint32_t *o_flag);
+uint32_t al_dbg_chainexact_tile(void);
+
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
 	uint64_t n_frag, n_reads, n_bases;
