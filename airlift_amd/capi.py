@@ -83,6 +83,26 @@ class BatchStat(C.Structure):
                 ("dp_jobs", C.c_uint64 * 10), ("dp_target_bases", C.c_uint64 * 10)]
 
 
+class LiftStat(C.Structure):
+    """AlLiftStat of al_lift_bam."""
+    _fields_ = [("kept", C.c_uint64), ("unlifted", C.c_uint64), ("unmapped_kept", C.c_uint64), ("pieces", C.c_uint64), ("bytes_in", C.c_uint64), ("held", C.c_uint64),
+                ("read_s", C.c_double), ("up_s", C.c_double), ("inflate_s", C.c_double), ("walk_s", C.c_double), ("lift_s", C.c_double), ("down_s", C.c_double),
+                ("deflate_s", C.c_double), ("wall_s", C.c_double), ("on_device", C.c_int)]
+
+
+LIFT_HOST = 1                 # AL_LIFT_HOST of include/airlift.h
+LIFT_GPU_DEFLATE = 2          # AL_LIFT_GPU_DEFLATE
+
+
+def lift_bam(bam_in, chain, bam_out, bed_out, flags=0, device=-1, n_threads=3, level=5, piece_bytes=0):
+    """al_lift_bam: the constant-region reads of `bam_in` moved across `chain` into `bam_out`, the reads that do not lift as rows of `bed_out`.  Returns the LiftStat."""
+    st = LiftStat()
+    rc = load().al_lift_bam(os.fsencode(bam_in), os.fsencode(chain), os.fsencode(bam_out), os.fsencode(bed_out), flags, device, n_threads, level, piece_bytes, C.byref(st))
+    if rc != 0:
+        raise AirliftError("al_lift_bam failed: %d" % rc)
+    return st
+
+
 _lib = None
 
 
@@ -179,6 +199,12 @@ def load():
         for f in (L.al_dbg_chainexact, L.al_dbg_chainexact_host):
             f.argtypes = [u8p, u64, u8p, u64, u64, u32p, u32p, u32p, u32p, u32p, u32, u64p, u64p, u32p, ci, ci, u32p, u32p, u64, u64p, u32p, u64, u64p, u32p, u64, u64p, u32p]; f.restype = ci
         L.al_dbg_chainexact_tile.argtypes = []; L.al_dbg_chainexact_tile.restype = u32
+    if hasattr(L, "al_lift_bam"):   # (lift: the constant-region reads of a BAM across the chain file, and its test taps)
+        szp = C.POINTER(C.c_size_t); u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64)
+        L.al_lift_bam.argtypes = [cs, cs, cs, cs, C.c_uint, ci, ci, ci, C.c_size_t, C.POINTER(LiftStat)]; L.al_lift_bam.restype = ci
+        L.al_dbg_lift_host.argtypes = [vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp]; L.al_dbg_lift_host.restype = ci
+        L.al_dbg_lift.argtypes = [ci, vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp, szp]; L.al_dbg_lift.restype = ci
+        L.al_dbg_lift_window.argtypes = []; L.al_dbg_lift_window.restype = C.c_uint32
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

@@ -8,7 +8,11 @@
 // no whole member left, or one launch's limits (staging bytes, members) are reached.  What it lists is taken: the window's front moves behind it.
 #pragma once
 #include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
+#include <unistd.h>
+#include <algorithm>
 #include <vector>
 #include "al_dev_inflate.h"
 
@@ -65,3 +69,62 @@ static inline double al_bgzf_ratio(const AlBgzfFeed &f)
 	}
 	return in && out ? (double)out / (double)in : 1.0;
 }
+
+// Where the pieces of a driver that walks a BGZF file come from (al_select.h, al_lift.h): compressed pieces by pread into the feed's window, whole members
+// taken off its front and inflated into a slot's text by the driver's backend.  Backend: append_bgzf(), host_buffer(), host_buffer_free(); Source: the
+// driver's source interface (read / push / pending, read_s, Timer).  tag: the option or command the messages name.  open(): the piece of compressed bytes,
+// and where the first member lies in the file and in the inflated stream.
+template <class Backend, class Source> struct AlBgzfPieceSource : Source {
+	int fd = -1; uint64_t fpos = 0; Backend *B = nullptr; const char *tag = ""; AlBgzfFeed feed; size_t piece = 0, want_out[2] = {0, 0}; bool eof_file = false, own = false; const char *fn = "";
+	size_t max_in = 0, max_mem = 0; std::vector<AlInfMember> mem;
+	~AlBgzfPieceSource() { if (feed.buf) { if (own) free(feed.buf); else B->host_buffer_free(feed.buf); } }
+	int open(size_t piece_bytes, uint64_t file_off = 0, uint64_t out_off = 0)
+	{
+		piece = piece_bytes; feed.cap = 2 * piece + 65536; fpos = file_off; feed.file_off = file_off; feed.out_off = out_off;
+		feed.buf = (uint8_t *)B->host_buffer(feed.cap);
+		if (!feed.buf) { feed.buf = (uint8_t *)malloc(feed.cap); own = true; }
+		if (!feed.buf) { fprintf(stderr, "[ERROR] airlift: %s: no host memory for the BGZF window of '%s'\n", tag, fn); return -1; }
+		max_in = feed.cap; max_mem = feed.cap / 28 + 16;           // (a member is at least 28 bytes)
+		return 0;
+	}
+	int read_piece()
+	{
+		size_t room = 0; uint8_t *dst = al_bgzf_feed_room(feed, &room);
+		size_t want = std::min(piece, room);
+		typename Source::Timer tm(this->read_s);
+		while (want) {
+			const ssize_t g = pread(fd, dst, want, (off_t)fpos);
+			if (g < 0) { fprintf(stderr, "[ERROR] airlift: %s: reading '%s' failed\n", tag, fn); return -1; }
+			if (g == 0) { eof_file = true; break; }
+			al_bgzf_feed_add(feed, (size_t)g); dst += g; fpos += (uint64_t)g; want -= (size_t)g;
+		}
+		return 0;
+	}
+	int read(int slot, size_t want) override { want_out[slot] = want; return 0; }
+	size_t pending(int slot) const override { return want_out[slot] + 65536; }
+	int push(Backend &Bk, int slot, bool *eof) override
+	{
+		uint64_t got = 0; *eof = false;
+		while (got < want_out[slot]) {
+			const uint8_t *bytes = nullptr; uint64_t n_in = 0, n_out = 0, at = 0;
+			const int r = al_bgzf_take(feed, want_out[slot] - got, max_in, max_mem, mem, &bytes, &n_in, &n_out, &at);
+			if (!mem.empty()) {
+				size_t bad = 0; uint32_t bst = 0;
+				const int ar = Bk.append_bgzf(slot, bytes, (size_t)n_in, mem.data(), mem.size(), n_out, &bad, &bst);
+				if (ar > 0) fprintf(stderr, "[ERROR] airlift: %s: '%s': BGZF member at file offset %llu: status %u (%s)\n", tag, fn, (unsigned long long)(at + mem[bad].in_off), bst, al_inf_strerror((int)bst));
+				if (ar) return -1;
+				got += n_out;
+			}
+			if (r == AL_BGZF_BROKEN) { fprintf(stderr, "[ERROR] airlift: %s: '%s': no BGZF member at file offset %llu\n", tag, fn, (unsigned long long)feed.file_off); return -1; }
+			if (r == AL_BGZF_MORE) {
+				if (eof_file) {
+					if (al_bgzf_feed_left(feed)) { fprintf(stderr, "[ERROR] airlift: %s: '%s': truncated BGZF member at file offset %llu\n", tag, fn, (unsigned long long)feed.file_off); return -1; }
+					*eof = true; break;
+				}
+				if (read_piece()) return -1;
+			}
+		}
+		return 0;
+	}
+};
+

@@ -189,6 +189,10 @@ struct AlChnTab {
 	std::vector<AlChnLine> line;
 	uint64_t n_three = 0;
 	std::unordered_map<std::string, uint32_t> by_name;
+	// the q side, kept only when keep_q is set before al_chn_parse (lift, al_dev_lift.h): per chain qName, qSize, qStart, qStrand == '-' and the line of its
+	// header; per alignment line dq (0 on a 1-field line)
+	bool keep_q = false;
+	std::vector<std::string> c_qname; std::vector<uint64_t> c_qsize, c_qstart; std::vector<uint8_t> c_minus; std::vector<unsigned long long> c_line; std::vector<uint32_t> dq;
 	AlChnIn in() const
 	{
 		AlChnIn x; x.n = line.size(); x.line = line.data(); x.n_chain = (uint32_t)c_slot.size(); x.c_slot = c_slot.data(); x.c_tstart = c_tstart.data();
@@ -249,6 +253,14 @@ static inline int al_chn_parse(const char *fn, AlChnTab &t, std::string &err)
 			else slot = it->second;                                          // (a later header's tSize changes nothing, as in the scripts)
 			if (tstart > t.L[slot]) return fail("tStart lies beyond tSize");
 			if (t.c_slot.size() >= 0xfffffffeu) return fail("more chains than a run takes");
+			if (t.keep_q) {
+				uint64_t qsize, qstart;
+				if (!al_chn_num(l + f[8].first, f[8].second, &qsize)) return fail("qSize is not a number");
+				if (!al_chn_num(l + f[10].first, f[10].second, &qstart)) return fail("qStart is not a number");
+				if (f[9].second != 1 || (l[f[9].first] != '+' && l[f[9].first] != '-')) return fail("qStrand is neither '+' nor '-'");
+				t.c_qname.push_back(std::string(l + f[7].first, f[7].second)); t.c_qsize.push_back(qsize); t.c_qstart.push_back(qstart);
+				t.c_minus.push_back(l[f[9].first] == '-'); t.c_line.push_back(rd.n_line);
+			}
 			t.c_slot.push_back(slot); t.c_tstart.push_back((uint32_t)tstart);
 			pos = tstart; have = true; closed = false;
 			continue;
@@ -262,6 +274,7 @@ static inline int al_chn_parse(const char *fn, AlChnTab &t, std::string &err)
 		if (pos + v[0] > t.L[slot]) return fail("the block ends beyond tSize");
 		if (pos + v[0] + v[1] > t.L[slot]) return fail("the gap ends beyond tSize");
 		if (t.line.size() >= 0x7ffffff0u) return fail("more alignment lines than a run takes");
+		if (t.keep_q) { if (v[2] >= (1ull << 31)) return fail("dq is 2^31 or more"); t.dq.push_back((uint32_t)v[2]); }
 		t.line.push_back(AlChnLine{(uint32_t)t.c_slot.size() - 1, (uint32_t)v[0], (uint32_t)v[1], f.size() == 3 ? 1u : 0u});
 		pos += v[0] + v[1];
 		if (f.size() == 3) ++t.n_three; else closed = true;

@@ -1,0 +1,460 @@
+// al_lift.hip -- `lift`: the constant-region reads of a BAM moved across the chain file on the GPU (the function: al_dev_lift.h; the driver: al_lift.h).
+//
+//   k_bam_walk      one wavefront per text: the record offsets along the chain of block_size fields.  The 64 lanes stage the text in windows of AL_LIFT_W
+//                   bytes into LDS with 16-byte loads; the hop through the window is uniform (two LDS words broadcast to every lane, the size field made
+//                   scalar) and runs while the next window is already on its way in registers.  The two windows form a ring, so a block_size field cut
+//                   by a window's edge is read once the next window is in; a record that ends beyond the next window is skipped by arithmetic and the
+//                   window it ends in is loaded afresh.  Lane i & 63 keeps the offset of record i: 64 offsets leave with one store.
+//   k_lift          lane per record: the fixed fields and the CIGAR read byte-wise (records are not aligned), at most two binary searches in the block
+//                   table, the kept record patched in place; verdict, kept length, arena share
+//   (scan)          al_stream_scan_excl_u64 over the kept lengths and over the arena shares
+//   k_lift_gather   16 lanes per record: a kept record to the packed output, an unlifted record's descriptor, name and CIGAR words to the arena
+// A backend slot is an input-only AlStreamSlot (text, stream, inflater staging), as in al_select.hip.
+#include <hip/hip_runtime.h>
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <atomic>
+#include <memory>
+#include "al_internal.h"
+#include "al_device.h"
+#include "al_runtime.h"
+#include "al_stream.h"
+#include "al_dev_inflate.h"
+#include "al_bam.h"
+#include "al_lift.h"
+#include "../../include/airlift.h"
+
+#define AL_LIFT_W 8192u                       // bytes of a window (a power of two, a multiple of 64 x 16)
+#define AL_LIFT_V (AL_LIFT_W / 16 / 64)       // 16-byte loads per lane and window
+
+// window w of the text into a lane's registers; lim: the bytes of the text's buffer that may be read.  A window that lies whole below lim -- every window
+// of a text whose buffer has the room begin() asks for -- is loaded without a branch per load, so that the loads stay in flight while the lanes go on.
+typedef uint32_t al_u32x4 __attribute__((ext_vector_type(4)));
+struct AlWalkRegs { al_u32x4 v[AL_LIFT_V]; };
+__device__ __forceinline__ void walk_load(AlWalkRegs &R, const uint8_t *__restrict__ t, uint32_t w, uint32_t lim, uint32_t l)
+{
+	const al_u32x4 zero = {0, 0, 0, 0};
+	if ((uint64_t)(w + 1) * AL_LIFT_W <= lim) {
+		_Pragma("unroll")
+		for (uint32_t j = 0; j < AL_LIFT_V; ++j) R.v[j] = *(const al_u32x4 *)(t + (size_t)w * AL_LIFT_W + (l + 64 * j) * 16); }
+	else {
+		_Pragma("unroll")
+		for (uint32_t j = 0; j < AL_LIFT_V; ++j) { const uint64_t off = (uint64_t)w * AL_LIFT_W + (l + 64 * j) * 16; R.v[j] = off + 16 <= lim ? *(const al_u32x4 *)(t + off) : zero; }
+	}
+}
+// The hop is uniform: every lane reads the same two LDS words (a broadcast), the size field is taken out of them with one funnel shift and made scalar, so
+// the loop's compares and branches are scalar; lane i & 63 keeps the offset of record i and the 64 offsets leave with one store.
+__global__ void __launch_bounds__(64)
+k_bam_walk(const uint8_t *__restrict__ t, uint32_t n, uint32_t lim, uint32_t start, uint32_t *__restrict__ rec_off, uint32_t *__restrict__ res)
+{
+	__shared__ al_u32x4 ring4[2 * AL_LIFT_W / 16];
+	const uint32_t *ring32 = (const uint32_t *)ring4;
+	const uint32_t l = threadIdx.x;
+	uint32_t p = start, n_rec = 0, mine = 0, state = p + 4 > n ? 1u : 0u;   // state 1: the walk has ended; 2: at a block_size out of range
+	uint32_t k = p / AL_LIFT_W;
+	AlWalkRegs R = {};
+	if (state == 0) {
+		walk_load(R, t, k, lim, l);
+		_Pragma("unroll")
+		for (uint32_t j = 0; j < AL_LIFT_V; ++j) ring4[(k & 1) * (AL_LIFT_W / 16) + l + 64 * j] = R.v[j];
+	}
+	__syncthreads();
+	while (state == 0) {
+		const bool pre = (uint64_t)(k + 1) * AL_LIFT_W < n;
+		if (pre) walk_load(R, t, k + 1, lim, l);
+		const uint32_t wend = pre ? (k + 1) * AL_LIFT_W : n;
+		while (p + 4 <= wend) {
+			const uint32_t a = (p & (2 * AL_LIFT_W - 1)) >> 2;
+			const uint32_t lo = ring32[a], hi = ring32[(a + 1) & (2 * AL_LIFT_W / 4 - 1)];
+			const uint32_t bs = __builtin_amdgcn_readfirstlane(__funnelshift_r(lo, hi, (p & 3) * 8));
+			if (bs < 32 || bs > AL_LIFT_MAX_BS) { state = 2; break; }
+			if (p + 4 + bs > n) { state = 1; break; }
+			if (l == (n_rec & 63)) mine = p;
+			++n_rec;
+			if ((n_rec & 63) == 0) rec_off[n_rec - 64 + l] = mine;
+			p += 4 + bs;
+		}
+		if (state == 0 && p + 4 > n) state = 1;
+		if (state) break;
+		const uint32_t k2 = p / AL_LIFT_W;
+		__syncthreads();
+		if (k2 <= k + 1) ++k;                                              // (p + 4 lies beyond window k and inside the text: window k + 1 exists and is on its way)
+		else { k = k2; walk_load(R, t, k, lim, l); }                       // a record that ends beyond the next window: skipped, the window of p loaded afresh
+		_Pragma("unroll")
+		for (uint32_t j = 0; j < AL_LIFT_V; ++j) ring4[(k & 1) * (AL_LIFT_W / 16) + l + 64 * j] = R.v[j];
+		__syncthreads();
+	}
+	if (l < (n_rec & 63)) rec_off[(n_rec & ~63u) + l] = mine;
+	if (l == 0) { res[0] = n_rec; res[1] = p; res[2] = state == 2 ? 1u : 0u; }
+}
+
+__global__ void __launch_bounds__(256)
+k_lift(uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_off, uint32_t n_rec, AlLiftTab T, uint32_t *__restrict__ verdict, uint32_t *__restrict__ keep_len, uint32_t *__restrict__ arena_len,
+       unsigned long long *__restrict__ first_bad, unsigned long long *__restrict__ cnt)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	uint32_t v = 0xffu;
+	if (r < n_rec) {
+		const AlLiftOut o = al_lift_record(T, t + rec_off[r]);
+		verdict[r] = v = o.verdict; keep_len[r] = o.keep_len; arena_len[r] = o.arena_len;
+		if (v >= AL_LIFT_BAD_FIT) atomicMin(first_bad, (unsigned long long)r);
+	} else if (r == n_rec) { keep_len[r] = 0; arena_len[r] = 0; }          // (the scans' last element: their totals)
+	for (uint32_t c = 0; c < 3; ++c) {
+		const unsigned long long m = __ballot(v == c);
+		if ((threadIdx.x & 63) == 0 && m) atomicAdd(cnt + c, (unsigned long long)__popcll(m));
+	}
+}
+
+__global__ void __launch_bounds__(256)
+k_lift_gather(const uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_off, uint32_t n_rec, const uint32_t *__restrict__ verdict, const uint32_t *__restrict__ keep_len,
+              const uint64_t *__restrict__ keep_off, const uint64_t *__restrict__ arena_off, uint8_t *__restrict__ packed, uint8_t *__restrict__ arena)
+{
+	const uint32_t r = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
+	if (r >= n_rec) return;
+	const uint8_t *src = t + rec_off[r];
+	const uint32_t v = verdict[r];
+	if (v == AL_LIFT_UNLIFTED) al_lift_arena_put(src, arena + arena_off[r], l, 16);
+	else if (v == AL_LIFT_KEPT || v == AL_LIFT_UNMAPPED) {
+		const uint32_t len = keep_len[r];
+		uint8_t *o = packed + keep_off[r];
+		for (uint32_t j = l; j < len; j += 16) o[j] = src[j];
+	}
+}
+
+namespace {
+
+#define LIFT_CHECK(x) AL_HIP_CHECK_AS("lift", x)
+
+struct AlLiftDevBackend : AlLiftBackend {
+	int device = 0; bool open_ok = false;
+	std::atomic<size_t> own_acct{0}, *acct = &own_acct, *acct_before = nullptr;     // the account every device range of the backend is booked on
+	AlStreamSlot S[2];
+	AlLiftBlock *d_blk = nullptr; uint32_t *d_pmax = nullptr, *d_first = nullptr; int32_t *d_ref = nullptr; AlLiftTab T{nullptr, nullptr, nullptr, nullptr, 0, 0};
+	DevBuf<uint32_t> rec_off[2], verdict[2], keep_len[2], arena_len[2]; DevBuf<uint64_t> keep_off[2], arena_off[2]; DevBuf<uint8_t> packed[2], arena[2];
+	DevBuf<unsigned long long> cnt[2];                                  // first_bad, kept, unlifted, unmapped; the walk's three words behind them
+	PinnedVec<uint8_t> h_packed[2], h_arena[2];
+	unsigned long long *h_cnt = nullptr;                                // page-locked, 16 words per slot
+	hipEvent_t ev[2][6] = {};                                          // per slot: walk from / to, lift to, gather from / to, copy down to
+	bool gathered[2] = {false, false}; uint32_t n_rec[2] = {0, 0};
+	double up_s = 0, walk_s = 0, lift_s = 0, down_s = 0;
+
+	const char *name() const override { return "k_lift"; }
+	// 0, or 1 when there is no usable device or it refuses the memory (nothing is left allocated after the destructor)
+	int open(int dev, const AlLiftChain &C, size_t piece, size_t cap_in, size_t cap_mem)
+	{
+		int n_dev = 0;
+		if (hipGetDeviceCount(&n_dev) != hipSuccess || n_dev < 1) { (void)hipGetLastError(); return 1; }
+		device = dev < 0 ? 0 : dev;
+		if (device >= n_dev || hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return 1; }
+		acct_before = al_acct(); al_acct() = acct; open_ok = true;
+		for (int i = 0; i < 2; ++i) {
+			if (al_stream_slot_init(S[i], nullptr, device, 1)) return 1;
+			for (hipEvent_t &e : ev[i]) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return 1; }
+			if (al_stream_begin_text(S[i], 0, 2 * piece + 65536) || cnt[i].ensure(8)) return 1;
+			if (cap_in && al_stream_bgzf_init(S[i], cap_in, cap_mem)) return 1;
+		}
+		if (hipHostMalloc((void **)&h_cnt, 32 * 8, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); h_cnt = nullptr; return 1; }
+		const size_t nb = C.blk.size(), nr = C.ref_slot.size();
+		if (al_dev_malloc((void **)&d_blk, (nb + 1) * sizeof(AlLiftBlock)) != hipSuccess || al_dev_malloc((void **)&d_pmax, (nb + 1) * 4) != hipSuccess ||
+		    al_dev_malloc((void **)&d_first, C.first.size() * 4) != hipSuccess || al_dev_malloc((void **)&d_ref, (nr + 1) * 4) != hipSuccess) { (void)hipGetLastError(); return 1; }
+		if ((nb && (hipMemcpy(d_blk, C.blk.data(), nb * sizeof(AlLiftBlock), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d_pmax, C.pmax.data(), nb * 4, hipMemcpyHostToDevice) != hipSuccess)) ||
+		    hipMemcpy(d_first, C.first.data(), C.first.size() * 4, hipMemcpyHostToDevice) != hipSuccess || (nr && hipMemcpy(d_ref, C.ref_slot.data(), nr * 4, hipMemcpyHostToDevice) != hipSuccess)) { (void)hipGetLastError(); return 1; }
+		T = AlLiftTab{d_blk, d_pmax, d_first, d_ref, (uint32_t)C.tname.size(), (uint32_t)nr};
+		return 0;
+	}
+	~AlLiftDevBackend() override
+	{
+		if (!open_ok) return;
+		(void)hipSetDevice(device);
+		for (int i = 0; i < 2; ++i) {
+			if (S[i].io) (void)hipStreamSynchronize(S[i].io);
+			rec_off[i].release(); verdict[i].release(); keep_len[i].release(); arena_len[i].release(); keep_off[i].release(); arena_off[i].release(); packed[i].release(); arena[i].release(); cnt[i].release();
+			al_stream_slot_destroy(S[i]);
+			for (hipEvent_t &e : ev[i]) if (e) (void)hipEventDestroy(e);
+		}
+		if (d_blk) al_dev_free(d_blk); if (d_pmax) al_dev_free(d_pmax); if (d_first) al_dev_free(d_first); if (d_ref) al_dev_free(d_ref);
+		if (h_cnt) (void)hipHostFree(h_cnt);
+		al_acct() = acct_before;
+	}
+	size_t held() const override { return acct->load(); }
+
+	int begin(int s, size_t cap) override { if (al_stream_begin_text(S[s], 0, cap + 2 * AL_LIFT_W)) return -1; gathered[s] = false; return 0; }   // (room for k_bam_walk to load whole windows)
+	int room(int s, uint64_t n) const { if (S[s].txt_n[0] + n + 16 > S[s].txt[0].cap) { fprintf(stderr, "[airlift] lift: text buffer too small\n"); return -1; } return 0; }
+	int carry(int s, int from, uint64_t off, uint64_t n) override
+	{
+		if (n == 0) return 0;
+		if (room(s, n) || off + n > S[from].txt_n[0]) return -1;
+		LIFT_CHECK(hipMemcpyAsync(S[s].txt[0].p + S[s].txt_n[0], S[from].txt[0].p + off, n, hipMemcpyDeviceToDevice, S[s].io));
+		S[s].txt_n[0] += n;
+		return 0;
+	}
+	int append(int s, const uint8_t *p, size_t n) override
+	{
+		if (n == 0) return 0;
+		if (room(s, n)) return -1;
+		LIFT_CHECK(hipMemcpyAsync(S[s].txt[0].p + S[s].txt_n[0], p, n, hipMemcpyHostToDevice, S[s].io));
+		LIFT_CHECK(hipStreamSynchronize(S[s].io));
+		S[s].txt_n[0] += n;
+		return 0;
+	}
+	int append_bgzf(int s, const uint8_t *b, size_t n_in, const AlInfMember *mem, size_t n_mem, uint64_t n_out, size_t *bad, uint32_t *bad_status) override
+	{
+		const auto t0 = std::chrono::steady_clock::now(); const double k0 = S[s].bz.kernel_s;
+		const int r = al_stream_append_bgzf(S[s], 0, b, n_in, mem, n_mem, n_out, bad, bad_status);
+		up_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - (S[s].bz.kernel_s - k0);
+		return r;
+	}
+	uint64_t text_bytes(int s) const override { return S[s].txt_n[0]; }
+	int run(int s, uint64_t start, AlLiftPiece *r) override
+	{
+		AlStreamSlot &X = S[s]; hipStream_t st = X.io;
+		LIFT_CHECK(hipSetDevice(device));
+		*r = AlLiftPiece();
+		const uint64_t n = X.txt_n[0];
+		if (n >= (1ull << 31) || start > n) { fprintf(stderr, "[airlift] lift: a text of %llu bytes\n", (unsigned long long)n); return -1; }
+		const size_t cap = (size_t)(n / 36) + 64;                       // (a record takes at least 36 bytes)
+		if (rec_off[s].ensure(cap)) return -1;
+		unsigned long long *h = h_cnt + 16 * s; uint32_t *hw = (uint32_t *)(h + 4);
+		h[0] = ~0ull; h[1] = h[2] = h[3] = 0;
+		LIFT_CHECK(hipMemcpyAsync(cnt[s].p, h, 32, hipMemcpyHostToDevice, st));
+		LIFT_CHECK(hipEventRecord(ev[s][0], st));
+		hipLaunchKernelGGL(k_bam_walk, dim3(1), dim3(64), 0, st, X.txt[0].p, (uint32_t)n, (uint32_t)std::min<size_t>(X.txt[0].cap, 0xfffffff0u), (uint32_t)start, rec_off[s].p, (uint32_t *)(cnt[s].p + 4));
+		LIFT_CHECK(hipEventRecord(ev[s][1], st));
+		LIFT_CHECK(hipMemcpyAsync(hw, cnt[s].p + 4, 12, hipMemcpyDeviceToHost, st));
+		LIFT_CHECK(hipStreamSynchronize(st));
+		LIFT_CHECK(hipGetLastError());
+		const uint32_t nr = hw[0];
+		r->n_rec = nr; r->consumed = hw[1]; r->walk_bad = hw[2]; n_rec[s] = nr;
+		if (verdict[s].ensure((size_t)nr + 2) || keep_len[s].ensure((size_t)nr + 2) || arena_len[s].ensure((size_t)nr + 2) || keep_off[s].ensure((size_t)nr + 2) || arena_off[s].ensure((size_t)nr + 2)) return -1;
+		hipLaunchKernelGGL(k_lift, dim3((nr + 256) / 256), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, nr, T, verdict[s].p, keep_len[s].p, arena_len[s].p, cnt[s].p, cnt[s].p + 1);
+		if (al_stream_scan_excl_u64(X, keep_len[s].p, keep_off[s].p, (size_t)nr + 1, st) || al_stream_scan_excl_u64(X, arena_len[s].p, arena_off[s].p, (size_t)nr + 1, st)) return -1;
+		LIFT_CHECK(hipEventRecord(ev[s][2], st));
+		LIFT_CHECK(hipMemcpyAsync(h, cnt[s].p, 32, hipMemcpyDeviceToHost, st));
+		LIFT_CHECK(hipMemcpyAsync(h + 6, keep_off[s].p + nr, 8, hipMemcpyDeviceToHost, st));
+		LIFT_CHECK(hipMemcpyAsync(h + 7, arena_off[s].p + nr, 8, hipMemcpyDeviceToHost, st));
+		LIFT_CHECK(hipStreamSynchronize(st));
+		LIFT_CHECK(hipGetLastError());
+		r->first_bad = h[0]; r->n_kept = h[1]; r->n_unlifted = h[2]; r->n_unmapped = h[3]; r->kept_bytes = h[6]; r->arena_bytes = h[7];
+		if (r->first_bad != ~0ull) {
+			uint32_t two[2] = {0, 0};
+			LIFT_CHECK(hipMemcpy(&two[0], rec_off[s].p + r->first_bad, 4, hipMemcpyDeviceToHost)); LIFT_CHECK(hipMemcpy(&two[1], verdict[s].p + r->first_bad, 4, hipMemcpyDeviceToHost));
+			r->bad_off = two[0]; r->bad_code = two[1];
+		}
+		float ms[2] = {0, 0};
+		if (hipEventElapsedTime(&ms[0], ev[s][0], ev[s][1]) == hipSuccess && hipEventElapsedTime(&ms[1], ev[s][1], ev[s][2]) == hipSuccess) { walk_s += ms[0] * 1e-3; lift_s += ms[1] * 1e-3; } else (void)hipGetLastError();
+		return 0;
+	}
+	int gather(int s, const AlLiftPiece &r, bool packed_down) override
+	{
+		AlStreamSlot &X = S[s]; hipStream_t st = X.io;
+		if (packed[s].ensure((size_t)r.kept_bytes + 16) || arena[s].ensure((size_t)r.arena_bytes + 16) || h_arena[s].resize((size_t)r.arena_bytes + 1) || (packed_down && h_packed[s].resize((size_t)r.kept_bytes + 1))) return -1;
+		LIFT_CHECK(hipEventRecord(ev[s][3], st));
+		if (r.n_rec) hipLaunchKernelGGL(k_lift_gather, dim3((unsigned)((r.n_rec + 15) / 16)), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, (uint32_t)r.n_rec, verdict[s].p, keep_len[s].p, keep_off[s].p, arena_off[s].p, packed[s].p, arena[s].p);
+		LIFT_CHECK(hipEventRecord(ev[s][4], st));
+		if (r.arena_bytes) LIFT_CHECK(hipMemcpyAsync(h_arena[s].data(), arena[s].p, (size_t)r.arena_bytes, hipMemcpyDeviceToHost, st));
+		if (packed_down && r.kept_bytes) LIFT_CHECK(hipMemcpyAsync(h_packed[s].data(), packed[s].p, (size_t)r.kept_bytes, hipMemcpyDeviceToHost, st));
+		LIFT_CHECK(hipEventRecord(ev[s][5], st));
+		LIFT_CHECK(hipGetLastError());
+		gathered[s] = true;
+		return 0;
+	}
+	int finish(int s, const uint8_t **p, const uint8_t **a) override
+	{
+		LIFT_CHECK(hipStreamSynchronize(S[s].io));
+		LIFT_CHECK(hipGetLastError());
+		*p = h_packed[s].data(); *a = h_arena[s].data();
+		if (gathered[s]) {
+			float ms[2] = {0, 0};
+			if (hipEventElapsedTime(&ms[0], ev[s][3], ev[s][4]) == hipSuccess && hipEventElapsedTime(&ms[1], ev[s][4], ev[s][5]) == hipSuccess) { lift_s += ms[0] * 1e-3; down_s += ms[1] * 1e-3; } else (void)hipGetLastError();
+			gathered[s] = false;
+		}
+		return 0;
+	}
+	// the packed records of a slot after finish(), for a slot whose bytes did not come down with the gather
+	int fetch_packed(int s, const AlLiftPiece &r, const uint8_t **p)
+	{
+		if (h_packed[s].resize((size_t)r.kept_bytes + 1)) return -1;
+		const auto t0 = std::chrono::steady_clock::now();
+		if (r.kept_bytes) LIFT_CHECK(hipMemcpy(h_packed[s].data(), packed[s].p, (size_t)r.kept_bytes, hipMemcpyDeviceToHost));
+		down_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+		*p = h_packed[s].data();
+		return 0;
+	}
+	void *host_buffer(size_t n) override { void *p = nullptr; if (hipHostMalloc(&p, n, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return nullptr; } return p; }
+	void host_buffer_free(void *p) override { (void)hipHostFree(p); }
+	int fetch_records(int s, uint32_t *ro, uint32_t *v, size_t n) override
+	{
+		if (n) { LIFT_CHECK(hipMemcpy(ro, rec_off[s].p, n * 4, hipMemcpyDeviceToHost)); LIFT_CHECK(hipMemcpy(v, verdict[s].p, n * 4, hipMemcpyDeviceToHost)); }
+		return 0;
+	}
+	void stat(AlLiftRun &st) override { st.up_s += up_s; st.inflate_s += S[0].bz.kernel_s + S[1].bz.kernel_s; st.walk_s += walk_s; st.lift_s += lift_s; st.down_s += down_s; }
+};
+
+// The BAM header of a BGZF file: leading members inflated on the host until it is complete.  *file_off / *out_off: file and stream offset of the member
+// that holds the first record's first byte, *start that byte's offset in the member.  0; -1 with a message printed.
+int lift_read_header(int fd, const char *fn, AlLiftHeader &H, uint64_t *file_off, uint64_t *out_off, uint64_t *start)
+{
+	std::vector<uint8_t> in, out; std::vector<uint64_t> m_file, m_out; uint64_t fpos = 0, ipos = 0; bool eof = false;
+	for (;;) {
+		uint32_t msize = 0, hd = 0; int r = -1;
+		if (in.size() - ipos >= 18) r = al_inf_parse_header(in.data() + ipos, in.size() - ipos, &msize, &hd);
+		if (r > 0 || (eof && fpos == 0 && in.size() < 28)) { fprintf(stderr, "[ERROR] airlift: lift: '%s' is not a BGZF file (lift reads a BAM by its BGZF members; there is no one-stream reader here)\n", fn); return -1; }
+		if (r < 0 || msize > in.size() - ipos) {
+			if (eof) { fprintf(stderr, "ERROR: '%s': the file ends inside the BAM header\n", fn); return -2; }
+			const size_t at = in.size(); in.resize(at + (1 << 16));
+			const ssize_t g = pread(fd, in.data() + at, 1 << 16, (off_t)fpos);
+			if (g < 0) { fprintf(stderr, "[ERROR] airlift: lift: reading '%s' failed\n", fn); return -1; }
+			in.resize(at + (size_t)g); fpos += (uint64_t)g; if (g == 0) eof = true;
+			continue;
+		}
+		const uint32_t isize = al_inf_le32(in.data() + ipos + msize - 4);
+		if (isize > AL_INF_MAX_ISIZE) { fprintf(stderr, "[ERROR] airlift: lift: '%s': no BGZF member at file offset %llu\n", fn, (unsigned long long)ipos); return -1; }
+		const size_t at = out.size(); out.resize(at + isize);
+		const int stt = al_inflate_member_host(in.data() + ipos, msize, out.data() + at);
+		if (stt) { fprintf(stderr, "[ERROR] airlift: lift: '%s': BGZF member at file offset %llu: status %d (%s)\n", fn, (unsigned long long)ipos, stt, al_inf_strerror(stt)); return -1; }
+		m_file.push_back(ipos); m_out.push_back(at); ipos += msize;
+		size_t used = 0; std::string err;
+		const int hr = al_lift_header_parse(out.data(), out.size(), H, &used, err);
+		if (hr < 0) { fprintf(stderr, "ERROR: '%s': %s\n", fn, err.c_str()); return -2; }
+		if (hr > 0) continue;
+		size_t m = m_out.size();
+		while (m > 0 && m_out[m - 1] > used) --m;                         // the last member that starts at or before the first record
+		if (used == out.size()) { *file_off = ipos; *out_off = out.size(); *start = 0; }
+		else { *file_off = m_file[m - 1]; *out_off = m_out[m - 1]; *start = used - m_out[m - 1]; }
+		return 0;
+	}
+}
+
+} // namespace
+
+extern "C" uint32_t al_dbg_lift_window(void) { return AL_LIFT_W; }
+
+extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char *bam_out, const char *bed_out, unsigned flags, int device, int n_threads, int level, size_t piece_bytes, AlLiftStat *stat)
+{
+	const auto t_wall = std::chrono::steady_clock::now();
+	if (stat) memset(stat, 0, sizeof(*stat));
+	AlLiftChain C; std::string err;
+	if (al_lift_build(chain_fn, C, err)) { fprintf(stderr, "[ERROR] airlift: %s\n", err.c_str()); return -1; }
+	const int fd = open(bam_in, O_RDONLY);
+	if (fd < 0) { fprintf(stderr, "ERROR: failed to open file '%s'\n", bam_in); return -1; }
+	AlLiftHeader H; uint64_t file_off = 0, out_off = 0, start = 0;
+	int rc = lift_read_header(fd, bam_in, H, &file_off, &out_off, &start);
+	if (rc == 0 && al_lift_bind(C, H, err)) { fprintf(stderr, "[ERROR] airlift: lift: '%s': %s\n", bam_in, err.c_str()); rc = -1; }
+	if (rc) { close(fd); return rc; }
+	FILE *fo = fopen(bam_out, "wb"), *fb = fo ? fopen(bed_out, "wb") : nullptr;
+	if (!fo || !fb) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fo ? bed_out : bam_out); if (fo) { fclose(fo); unlink(bam_out); } close(fd); return -1; }
+	const bool host_backend = (flags & AL_LIFT_HOST) != 0, gpu_deflate = (flags & AL_LIFT_GPU_DEFLATE) != 0 && !host_backend;
+	const size_t zpiece = (size_t)al_env().inflate_piece_kb << 10, zcap = 2 * zpiece + 65536, zmem = zcap / 64 + 1024;
+	if (piece_bytes == 0) piece_bytes = std::max((size_t)8 << 20, 4 * zpiece);
+	if (piece_bytes >= ((size_t)1 << 29)) piece_bytes = (size_t)1 << 29;
+	std::atomic<size_t> acct{0}; AlLiftRun run; const char *backend = ""; double deflate_s = 0; rc = -1;
+	{
+		std::unique_ptr<AlLiftBackend> B; AlLiftDevBackend *D = nullptr;
+		if (!host_backend) {
+			std::unique_ptr<AlLiftDevBackend> d(new AlLiftDevBackend()); d->acct = &acct;
+			if (d->open(device, C, piece_bytes, zcap, zmem) == 0) { D = d.get(); B = std::move(d); }
+			else fprintf(stderr, "[airlift] lift: no usable device, or no device memory for the lift's buffers; the host twin lifts the reads\n");
+		}
+		if (!B) B.reset(new AlLiftHostBackend(C.tab(), n_threads));
+		backend = B->name();
+		{
+			AlBgzf z(fo, (level & 0xff) | (gpu_deflate && D ? 0x100 : 0), n_threads, D ? D->device : -1);
+			const size_t CH = (size_t)al_env().out_piece_mb << 20; char *ring[2] = {nullptr, nullptr};
+			bool ok = true;
+			if (z.dev_on) for (int i = 0; i < 2; ++i) if (hipHostMalloc((void **)&ring[i], CH, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ring[i] = nullptr; ok = false; }
+			if (!ok) fprintf(stderr, "[ERROR] airlift: lift: no page-locked memory for the BAM output\n");
+			std::vector<uint8_t> hdr; al_lift_header_write(H, C, hdr);
+			std::string rows;
+			if (ok && z.write((const char *)hdr.data(), hdr.size()) == 0) {
+				AlLiftBgzfSource src; src.fd = fd; src.B = B.get(); src.fn = bam_in;
+				if (src.open(zpiece, file_off, out_off) == 0) {
+					src.max_in = zcap; src.max_mem = zmem;
+					rc = al_lift_stream(*B, src, piece_bytes, start, out_off, bam_in, !z.dev_on, [&](int slot, const AlLiftPiece &r) -> int {
+						const uint8_t *packed = nullptr, *arena = nullptr;
+						if (B->finish(slot, &packed, &arena)) return -1;
+						if (z.dev_on) {
+							const int wd = z.write_device((const char *)D->packed[slot].p, (size_t)r.kept_bytes, D->S[slot].io, ring, CH, D->S[slot].ev_out);
+							if (wd < 0) return -1;
+							if (wd > 0 && (D->fetch_packed(slot, r, &packed) || z.write((const char *)packed, (size_t)r.kept_bytes))) return -1;
+						} else if (z.write((const char *)packed, (size_t)r.kept_bytes)) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out); return -1; }
+						rows.clear(); al_lift_rows(arena, (size_t)r.arena_bytes, H, rows);
+						if (fwrite(rows.data(), 1, rows.size(), fb) != rows.size()) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bed_out); return -1; }
+						return 0;
+					}, run);
+				}
+				if (rc == 0 && z.finish()) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out); rc = -1; }
+			} else if (ok) fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out);
+			deflate_s = z.t_deflate;
+			if (rc == 0 && z.dev_on && al_env().timing) z.timing_line(stderr, "lift");
+			for (int i = 0; i < 2; ++i) if (ring[i]) (void)hipHostFree(ring[i]);
+		}                                                               // (the compressor's device ranges go back before the backend's account is read)
+		B->stat(run);
+		B.reset();                                                      // every device range goes back here
+	}
+	close(fd);
+	if (fclose(fo) == EOF && rc == 0) rc = -1;
+	if (fclose(fb) == EOF && rc == 0) rc = -1;
+	if (rc) { unlink(bam_out); unlink(bed_out); }
+	const double wall = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_wall).count();
+	if (stat) {
+		stat->kept = run.kept; stat->unlifted = run.unlifted; stat->unmapped_kept = run.unmapped_kept; stat->pieces = run.pieces; stat->bytes_in = run.bytes_in;
+		stat->read_s = run.read_s; stat->up_s = run.up_s; stat->inflate_s = run.inflate_s; stat->walk_s = run.walk_s; stat->lift_s = run.lift_s; stat->down_s = run.down_s; stat->deflate_s = deflate_s; stat->wall_s = wall;
+		stat->held = acct.load(); stat->on_device = strcmp(backend, "host twin") != 0;
+	}
+	if (rc == 0 && al_env().timing)
+		fprintf(stderr, "[airlift] lift: '%s' (%s): %llu pieces, %llu bytes in, %llu kept, %llu unlifted, %llu unmapped kept; file read %.3f s, copy up %.3f s, inflate %.3f s, walk %.3f s, lift and gather %.3f s, copy down %.3f s, deflate %.3f s, wall %.3f s; device bytes held at return: %zu\n",
+		        bam_in, backend, (unsigned long long)run.pieces, (unsigned long long)run.bytes_in, (unsigned long long)run.kept, (unsigned long long)run.unlifted, (unsigned long long)run.unmapped_kept,
+		        run.read_s, run.up_s, run.inflate_s, run.walk_s, run.lift_s, run.down_s, deflate_s, wall, acct.load());
+	return rc;
+}
+
+// ---- test taps (airlift_amd/capi.py) ------------------------------------------------------------------------------------------------------------------------------
+// One uncompressed BAM stream (header and records) and a chain file through ONE pass of a backend: the text is the stream as given, the walk starts behind the
+// header.  0; -1 a device failure; -3 room (the counts are set); -4 the chain file or the header is refused (its message printed).
+static int lift_tap_prepare(const void *bam, size_t n, const char *chain_fn, AlLiftChain &C, AlLiftHeader &H, size_t *start)
+{
+	std::string err;
+	if (al_lift_build(chain_fn, C, err)) { fprintf(stderr, "[ERROR] airlift: %s\n", err.c_str()); return -4; }
+	if (al_lift_header_parse((const uint8_t *)bam, n, H, start, err) != 0) { fprintf(stderr, "ERROR: the header is cut or malformed: %s\n", err.c_str()); return -4; }
+	if (al_lift_bind(C, H, err)) { fprintf(stderr, "[ERROR] airlift: lift: %s\n", err.c_str()); return -4; }
+	return 0;
+}
+static int lift_tap(AlLiftBackend &B, const void *bam, size_t n, size_t start, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n)
+{
+	AlLiftPiece r; const uint8_t *p = nullptr, *a = nullptr;
+	if (B.begin(0, n + 1) || B.append(0, (const uint8_t *)bam, n) || B.run(0, start, &r)) return -1;
+	out4[0] = r.n_rec; out4[1] = r.consumed; out4[2] = r.first_bad != ~0ull ? r.first_bad : r.walk_bad ? r.n_rec : ~0ull; out4[3] = r.first_bad != ~0ull ? r.bad_code : r.walk_bad ? AL_LIFT_BAD_SIZE : 0;
+	*packed_n = (size_t)r.kept_bytes; *arena_n = (size_t)r.arena_bytes;
+	if (r.n_rec > rec_cap || r.kept_bytes > packed_cap || r.arena_bytes > arena_cap) return -3;
+	if (B.fetch_records(0, rec_off, verdict, (size_t)r.n_rec)) return -1;
+	if (r.first_bad != ~0ull) { *packed_n = *arena_n = 0; return 0; }
+	if (B.gather(0, r, true) || B.finish(0, &p, &a)) return -1;
+	if (r.kept_bytes) memcpy(packed, p, (size_t)r.kept_bytes);
+	if (r.arena_bytes) memcpy(arena, a, (size_t)r.arena_bytes);
+	return 0;
+}
+extern "C" int al_dbg_lift_host(const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n)
+{
+	AlLiftChain C; AlLiftHeader H; size_t start = 0;
+	if (const int r = lift_tap_prepare(bam, n, chain_fn, C, H, &start)) return r;
+	AlLiftHostBackend B(C.tab());
+	return lift_tap(B, bam, n, start, rec_off, verdict, rec_cap, out4, packed, packed_cap, packed_n, arena, arena_cap, arena_n);
+}
+extern "C" int al_dbg_lift(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n, size_t *held)
+{
+	AlLiftChain C; AlLiftHeader H; size_t start = 0;
+	*held = 0;
+	if (const int r = lift_tap_prepare(bam, n, chain_fn, C, H, &start)) return r;
+	if (n >= ((size_t)1 << 31) - 65536) return -3;
+	std::atomic<size_t> acct{0}; int rc;
+	{
+		AlLiftDevBackend B; B.acct = &acct;
+		if (B.open(device, C, n / 2 + 1, 0, 0)) return -1;
+		rc = lift_tap(B, bam, n, start, rec_off, verdict, rec_cap, out4, packed, packed_cap, packed_n, arena, arena_cap, arena_n);
+	}
+	*held = acct.load();
+	return rc;
+}

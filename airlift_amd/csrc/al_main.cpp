@@ -22,6 +22,8 @@
 //                                                                   the three scripts alone, file for file
 //          airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] OLD.fa NEW.fa CHAIN
 //                                                                   run/1_build_exact_chain_file.py: the exact chain file those scripts assume, verified or built on the GPU
+//          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
+//                                                                   run_pipeline.sh:92-95 (FastRemap): the constant-region reads moved across the chain file on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -113,6 +115,8 @@ static int usage()
 	                "       --merged-in; --host: the kernels' host twin, no device is opened; malformed input is refused as FILE:LINE: reason)\n"
 	                "chain-exact: airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] old.fa new.fa chain  (1_build_exact_chain_file.py: the two\n"
 	                "       references compared over every block of the chain file on the GPU; verify prints the mismatch lines or PASS VERIFICATION, build the exact chain file)\n"
+	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+	                "       (the reads in constant regions moved across the chain file on the GPU; the reads that do not lift leave as the rows extract-reads writes)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -141,10 +145,37 @@ int main(int argc, char **argv)
 			return 1;
 		}
 	for (int j = 2; j < argc; ++j)
-		if (!strcmp(argv[j], "--chain") && strcmp(argv[1], "tokens") != 0) {
+		if (!strcmp(argv[j], "--chain") && strcmp(argv[1], "tokens") != 0 && strcmp(argv[1], "lift") != 0) {
 			fprintf(stderr, "[ERROR] --chain names the chain file of a tokens run (airlift-align tokens --read-size R --skip S --chain CHAIN --max-errors E ref.fa; the scripts alone: airlift-align chain-beds): it cannot be combined with another mode\n");
 			return 1;
 		}
+	if (!strcmp(argv[1], "lift")) {                // run_pipeline.sh:92-95 (FastRemap): the constant-region reads moved across the chain file, the rest to a BED
+		int dev = -1, nt = 3, level = 5; unsigned lf = 0; size_t piece = 0; const char *c_fn = nullptr, *o_fn = nullptr, *b_fn = nullptr; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "--chain") && j + 1 < argc) c_fn = argv[++j];
+			else if (!strcmp(argv[j], "-o") && j + 1 < argc) o_fn = argv[++j];
+			else if (!strcmp(argv[j], "--unmapped-bed") && j + 1 < argc) b_fn = argv[++j];
+			else if (!strcmp(argv[j], "--host")) lf |= AL_LIFT_HOST;
+			else if (!strcmp(argv[j], "--gpu-deflate")) lf |= AL_LIFT_GPU_DEFLATE;
+			else if (!strcmp(argv[j], "-l") && j + 1 < argc) level = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--piece") && j + 1 < argc) piece = (size_t)strtoull(argv[++j], nullptr, 10);
+			else p.push_back(argv[j]);
+		}
+		if (p.size() != 1 || !c_fn || !o_fn || !b_fn || level < 0 || level > 9) {
+			fprintf(stderr, "Usage: airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+			                "       (every record of in.bam, a BGZF file, through the chain file on the GPU: a mapped read that lies wholly and uniquely inside one block of a '+' chain\n"
+			                "       gets its new contig, position and bin and stays in OUT.bam, in input order and unsorted; one that does not becomes a row of FILE -- chrom start end\n"
+			                "       name[.1|.2] MAPQ CIGAR, what extract-reads writes -- and is re-aligned; unmapped reads are kept; --host: the kernels' host twin, no device is opened;\n"
+			                "       --gpu-deflate: OUT.bam's blocks are deflated on the GPU; -t: host threads of the compressor; --piece: inflated bytes per piece)\n");
+			return 1;
+		}
+		if ((lf & AL_LIFT_HOST) && (lf & AL_LIFT_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] lift: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }
+		const int rc2 = al_lift_bam(p[0], c_fn, o_fn, b_fn, lf, dev, nt, level, piece, nullptr) == 0 ? 0 : 1;
+		fflush(stderr);
+		_exit(rc2);
+	}
 	if (!strcmp(argv[1], "chain-beds")) {          // 2_get_updated_regions_bed.py + get_constant_regions.py + get_retired_regions.py
 		int R = 0, E = -1, dev = -1; unsigned cf = 0; const char *g_fn = nullptr, *c_fn = nullptr, *r_fn = nullptr, *m_fn = nullptr; std::vector<const char *> p;
 		for (int j = 2; j < argc; ++j) {

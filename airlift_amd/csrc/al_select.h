@@ -81,60 +81,8 @@ struct AlSelPlainSource : AlSelSource {
 	size_t pending(int slot) const override { return n[slot]; }
 };
 
-// BGZF file (--gpu-inflate as well): compressed pieces into the feed's window, whole members taken off its front and inflated into the text
-struct AlSelBgzfSource : AlSelSource {
-	int fd = -1; uint64_t fpos = 0; AlSelBackend *B = nullptr; AlBgzfFeed feed; size_t piece = 0, want_out[2] = {0, 0}; bool eof_file = false, own = false; const char *fn = "";
-	size_t max_in = 0, max_mem = 0; std::vector<AlInfMember> mem;
-	~AlSelBgzfSource() { if (feed.buf) { if (own) free(feed.buf); else B->host_buffer_free(feed.buf); } }
-	int open(size_t piece_bytes)
-	{
-		piece = piece_bytes; feed.cap = 2 * piece + 65536;
-		feed.buf = (uint8_t *)B->host_buffer(feed.cap);
-		if (!feed.buf) { feed.buf = (uint8_t *)malloc(feed.cap); own = true; }
-		if (!feed.buf) { fprintf(stderr, "[ERROR] airlift: --gpu-select: no host memory for the BGZF window of '%s'\n", fn); return -1; }
-		max_in = feed.cap; max_mem = feed.cap / 28 + 16;           // (a member is at least 28 bytes)
-		return 0;
-	}
-	int read_piece()
-	{
-		size_t room = 0; uint8_t *dst = al_bgzf_feed_room(feed, &room);
-		size_t want = std::min(piece, room);
-		Timer tm(read_s);
-		while (want) {
-			const ssize_t g = pread(fd, dst, want, (off_t)fpos);
-			if (g < 0) { fprintf(stderr, "[ERROR] airlift: --gpu-select: reading '%s' failed\n", fn); return -1; }
-			if (g == 0) { eof_file = true; break; }
-			al_bgzf_feed_add(feed, (size_t)g); dst += g; fpos += (uint64_t)g; want -= (size_t)g;
-		}
-		return 0;
-	}
-	int read(int slot, size_t want) override { want_out[slot] = want; return 0; }
-	size_t pending(int slot) const override { return want_out[slot] + 65536; }
-	int push(AlSelBackend &Bk, int slot, bool *eof) override
-	{
-		uint64_t got = 0; *eof = false;
-		while (got < want_out[slot]) {
-			const uint8_t *bytes = nullptr; uint64_t n_in = 0, n_out = 0, at = 0;
-			const int r = al_bgzf_take(feed, want_out[slot] - got, max_in, max_mem, mem, &bytes, &n_in, &n_out, &at);
-			if (!mem.empty()) {
-				size_t bad = 0; uint32_t bst = 0;
-				const int ar = Bk.append_bgzf(slot, bytes, (size_t)n_in, mem.data(), mem.size(), n_out, &bad, &bst);
-				if (ar > 0) fprintf(stderr, "[ERROR] airlift: --gpu-select: '%s': BGZF member at file offset %llu: status %u (%s)\n", fn, (unsigned long long)(at + mem[bad].in_off), bst, al_inf_strerror((int)bst));
-				if (ar) return -1;
-				got += n_out;
-			}
-			if (r == AL_BGZF_BROKEN) { fprintf(stderr, "[ERROR] airlift: --gpu-select: '%s': no BGZF member at file offset %llu\n", fn, (unsigned long long)feed.file_off); return -1; }
-			if (r == AL_BGZF_MORE) {
-				if (eof_file) {
-					if (al_bgzf_feed_left(feed)) { fprintf(stderr, "[ERROR] airlift: --gpu-select: '%s': truncated BGZF member at file offset %llu\n", fn, (unsigned long long)feed.file_off); return -1; }
-					*eof = true; break;
-				}
-				if (read_piece()) return -1;
-			}
-		}
-		return 0;
-	}
-};
+// BGZF file (--gpu-inflate as well): AlBgzfPieceSource of al_bgzf_take.h over this driver's backend
+struct AlSelBgzfSource : AlBgzfPieceSource<AlSelBackend, AlSelSource> { AlSelBgzfSource() { tag = "--gpu-select"; } };
 
 // One file through the backend.  emit(arena, desc, n): the selected records of one piece, in file order.  *handover: ~0, or the stream offset the default
 // reader continues at.  0, or -1 with a message printed.

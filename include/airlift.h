@@ -465,6 +465,38 @@ int  al_dbg_chainexact_host(const uint8_t *old_text, uint64_t n_old, const uint8
                             uint64_t cap_pos, uint64_t *n_pos, uint32_t *o_l1, uint64_t cap_l1, uint64_t *n_l1, uint32_t *o_l2, uint64_t cap_l2, uint64_t *n_l2, uint32_t *o_flag);
 uint32_t al_dbg_chainexact_tile(void);
 
+/* ---- lift: the constant-region reads of a BAM moved across the chain file (run_pipeline.sh:92-95, FastRemap) ----
+ * Every record of `bam_in` (a BGZF file) goes through the block table of `chain_fn` on `device` (-1: the default device): a mapped record that lies wholly
+ * and uniquely inside one block of a '+' chain gets the new refID, pos and bin, its mate fields are lifted as a point, and it is written to `bam_out` in
+ * input order; a mapped record that does not lift leaves the BAM and becomes a row "chrom s e name[.1|.2] MAPQ CIGAR" of `bed_out` (the six columns
+ * extract-reads writes); an unmapped record is always kept.  The header's @SQ lines and reference list become the chain's qNames, an SO: value becomes
+ * unsorted.  The function is stated in full in airlift_amd/csrc/al_dev_lift.h.  flags: AL_LIFT_HOST -- the kernels' host twin, no device is opened (it also
+ * takes over, with a notice, where the device or its memory is refused); AL_LIFT_GPU_DEFLATE -- the packed records are deflated where they lie.
+ * level: the BGZF level; n_threads: host threads of the compressor and of the twin's inflater; piece_bytes: inflated bytes per piece (0: the default).
+ * 0; -1 with a message (a chain file refused as FILE:LINE: reason, a file that is no BGZF file, the wrong reference, I/O); -2 malformed BAM input, the
+ * message names the record's offset in the inflated stream.  On an error the two output files are removed.  All device memory is released before the
+ * return (stat->held == 0). */
+#define AL_LIFT_HOST 1u
+#define AL_LIFT_GPU_DEFLATE 2u
+typedef struct {
+	uint64_t kept, unlifted, unmapped_kept;   /* records: lifted and kept, gone to the BED, unmapped and kept */
+	uint64_t pieces, bytes_in, held;          /* pieces walked, inflated bytes, device bytes of the call's account at return */
+	double   read_s, up_s, inflate_s, walk_s, lift_s, down_s, deflate_s, wall_s;   /* file read, copy up, inflate, walk, lift + gather, copy down, deflate, wall */
+	int      on_device;                       /* 1: the kernels ran; 0: the host twin */
+} AlLiftStat;
+int  al_lift_bam(const char *bam_in, const char *chain_fn, const char *bam_out, const char *bed_out, unsigned flags, int device, int n_threads, int level, size_t piece_bytes, AlLiftStat *stat);
+/* Test taps: one uncompressed BAM stream (header and records) and a chain file through ONE pass of the kernels (al_dbg_lift) or of their host twin
+ * (al_dbg_lift_host).  The text is the stream as given and the walk starts behind the header.  rec_off / verdict[0, out4[0]): offset and verdict (0 kept,
+ * 1 unlifted, 2 unmapped and kept, 3.. refused) of every complete record; out4: records, offset of the first incomplete record, first refused record
+ * (~0: none) and its code; packed: the kept records one behind the other; arena: per unlifted record a descriptor {name_len, n_cigar, MAPQ | flag << 8,
+ * refID, s, 0, e (64 bits)}, the name and the CIGAR words, padded to 8 bytes.  0; -1: the device failed; -3: an array is too small (the counts are set);
+ * -4: the chain file or the header is refused.  al_dbg_lift_window: the bytes of text k_bam_walk stages at a time. */
+int  al_dbg_lift_host(const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
+                      void *arena, size_t arena_cap, size_t *arena_n);
+int  al_dbg_lift(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
+                 void *arena, size_t arena_cap, size_t *arena_n, size_t *held);
+uint32_t al_dbg_lift_window(void);
+
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
 	uint64_t n_frag, n_reads, n_bases;
