@@ -211,6 +211,9 @@ def load():
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci
     if hasattr(L, "al_dbg_chain"):
         L.al_dbg_chain.argtypes = [vp] * 9; L.al_dbg_chain.restype = ci
+    if hasattr(L, "al_dbg_regs"):
+        L.al_dbg_regs.argtypes = [vp] * 13; L.al_dbg_regs.restype = ci
+        L.al_dbg_regs_fetch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]; L.al_dbg_regs_fetch.restype = ci
     if hasattr(L, "al_dbg_seed"):
         L.al_dbg_seed.argtypes = [vp, vp, ci, vp]; L.al_dbg_seed.restype = ci
     L.al_version.restype = cs
@@ -391,6 +394,32 @@ class Context:
         if rc != 0:
             raise AirliftError("al_dbg_chain failed: %d" % rc)
         return nu, u, uo, ch[:tot], dict(zip(self.CHAIN_COUNTS, (int(x) for x in cnt)))
+
+    REGS_COUNTS = ("lb5", "lb65", "lb1025", "lb8193", "lb2049", "lb4097", "lb257", "heavy12", "heavy24", "heavy48", "heavy72", "heavy200", "log_miss", "sort_ties", "select_ran",
+                   "map_only_wave", "log_n")
+
+    def regs(self, nu, u, uo, chained, a_off, frag_rep):
+        """al_dbg_regs + al_dbg_regs_fetch: the stage between chaining and extension on caller-supplied chains (what chain() returns, and the
+        fragments' rep_len) for the uploaded batch (not run).  Returns a dict: reg_cnt, seg_na (per read), regs_n0, frag_hash (per fragment), regs (the
+        per-mate hits, (n, 28) uint32 device records, read after read), seg_a ((n, 2) uint64), dense (the map-only output, or None), counts by name."""
+        nf, nr = self.n_frag, self.n_reads
+        a_off = np.ascontiguousarray(a_off, dtype=np.uint64); tot = int(a_off[-1])
+        nu = np.ascontiguousarray(nu, dtype=np.uint32); u = np.ascontiguousarray(u, dtype=np.uint64); uo = np.ascontiguousarray(uo, dtype=np.uint32)
+        chained = np.ascontiguousarray(chained, dtype=np.uint64).reshape(-1, 2); frag_rep = np.ascontiguousarray(frag_rep, dtype=np.int32)
+        if len(a_off) != nf + 1 or len(nu) != nf or len(frag_rep) != nf or len(u) != tot + nf + 1 or len(uo) != tot + nf + 1 or len(chained) != tot:
+            raise AirliftError("al_dbg_regs: arrays do not fit the uploaded batch")
+        rc_, sna = np.zeros(nr, dtype=np.uint32), np.zeros(nr, dtype=np.uint32); n0, fh = np.zeros(nf, dtype=np.uint32), np.zeros(nf, dtype=np.uint32)
+        cnt = np.zeros(17, dtype=np.uint64); sizes = np.zeros(2, dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = load().al_dbg_regs(self.h, p(nu), p(u), p(uo), p(chained), p(a_off), p(frag_rep), p(rc_), p(sna), p(n0), p(fh), p(cnt), p(sizes))
+        if rc != 0:
+            raise AirliftError("al_dbg_regs failed: %d" % rc)
+        regs = np.zeros((int(sizes[0]) + 1, 28), dtype=np.uint32); seg_a = np.zeros((tot + 1, 2), dtype=np.uint64); dense = np.zeros((int(sizes[1]) + 1, 28), dtype=np.uint32)
+        rc = load().al_dbg_regs_fetch(self.h, p(regs), int(sizes[0]), p(seg_a), p(dense), int(sizes[1]))
+        if rc != 0:
+            raise AirliftError("al_dbg_regs_fetch failed: %d" % rc)
+        return {"reg_cnt": rc_, "seg_na": sna, "regs_n0": n0, "frag_hash": fh, "regs": regs[:-1], "seg_a": seg_a[:tot], "dense": dense[:-1] if self.idx.mo.flag & AL_F_OUT_PAF and not self.idx.mo.flag & AL_F_CIGAR else None,
+                "counts": dict(zip(self.REGS_COUNTS, (int(x) for x in cnt)))}
 
     SEED_COUNTS = ("small", "reg_2_1_128", "reg_4_1_256", "reg_8_1_512", "reg_16_1_512", "reg_8_4_1024", "reg_16_4_1024", "reg_16_8_1024", "sort1024", "merge_frags", "merge_tiles", "merge_passes",
                    "radix_frags", "radix_chunks", "flag_all", "compact", "rid_bits", "pos_bits", "rank_bits", "nl", "lb65", "lb129", "lb257", "lb513", "lb1025", "lb2049", "lb4097", "lb_big",

@@ -1171,7 +1171,7 @@ k_regs_select(const AlAnchor *__restrict__ chained, const uint64_t *__restrict__
 				if (!(P.pri_ratio > 0.0f)) return true;                          // selection switched off: everything is kept
 				if (n_segs <= 1) {                                              // mm_select_sub
 					if ((float)score >= __fmul_rn((float)psc, P.pri_ratio) || score + min_diff >= psc)
-						return !(qs == pqs && qe == pqe && (rid << 1 | rev) == pridrev && rs == prs && re == pre);
+						return !(qs == pqs && qe == pqe && rid == (pridrev >> 1) && rs == prs && re == pre);   // (hit.c:247 does not look at the strand: a hit with its parent's coordinates on the other strand is dropped too)
 					return false;
 				}
 				if (score + min_diff >= psc) return true;                       // mm_select_sub_multi
@@ -2890,6 +2890,10 @@ struct AlignState {            // lives in al_ctx_s::align_state (opaque there)
 	uint64_t out_total = 0;
 	AlTagBufs tags, eqx;                         // --MD / --cs tags, --eqx CIGARs (al_kernels_tags.hip); untouched without them
 	bool eqx_on = false;                         // the last run's records point into eqx.arena instead of arena
+	// the al_dbg_regs tap: stop after the ST_REGS event (a map-only run goes on: it has no extension stage); what the last run's host code decided
+	bool regs_only = false;
+	uint32_t tap_lb[7] = {}, tap_hv[5] = {};     // the chain-count class bounds in the order of k_lower_bounds' thresholds, fragments per k_regs_heavy tile
+	bool tap_select = false;                     // the selection kernels ran (regs_n0 is the last run's)
 };
 static std::map<al_ctx_t *, AlignState *> g_states;
 static std::mutex g_states_mtx;
@@ -3065,9 +3069,22 @@ int al_run_align_stage(al_ctx_t *c)
 	const bool map_only = al_map_only(c->opt.flag);
 	A->eqx_on = false;
 	if (nf == 0) { for (int i = ST_REGS; i < ST_COMPACT; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); return 0; }
-	// logf table from the HOST libm (the reference's logf is glibc's): logf((float)k / a) and logf((float)k)
+	// workspace sizes from the number of chains; the most chains a fragment has, for the logf table (behind the sums, in the slot the scan leaves free)
+	if (A->nu_off.ensure(nf + 2)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(c->frag_nu.p + nf, 0, 4, s));
+	if (scan32(c, c->frag_nu.p, A->nu_off.p, nf)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(A->nu_off.p + nf + 1, 0, 8, s));
+	if (al_prim_run(c->scan_tmp, [&](void *t, size_t &b) { return rocprim::reduce(t, b, (const uint32_t *)c->frag_nu.p, (uint32_t *)(A->nu_off.p + nf + 1), 0u, (size_t)nf, rocprim::maximum<uint32_t>(), s); })) return -1;
+	uint64_t nu_tail[2] = {0, 0};
+	AL_HIP_CHECK(hipMemcpyAsync(nu_tail, A->nu_off.p + nf, 16, hipMemcpyDeviceToHost, s));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	const uint64_t nu_total = nu_tail[0];
+	// logf table from the HOST libm (the reference's logf is glibc's): logf((float)k / a) and logf((float)k).  Its arguments: dp_max and chain scores, at most
+	// match_sc * read length, and n_sub + 1, at most the hits of a mate: a fragment's chains, four times that and four after the z-drop splits (a read inside
+	// a repeat has more chains than it has bases)
 	const int Lmax0 = c->max_rd_len;
-	const int log_n = std::max(AL_LOGTAB_N, (std::max(c->opt.a, 1) * 2 * Lmax0 + 1024 + 4095) / 4096 * 4096);   // dp_max <= match_sc * read length; room to spare
+	const uint64_t log_need = std::max<uint64_t>((uint64_t)std::max(c->opt.a, 1) * 2 * (uint64_t)Lmax0 + 1024, 4 * (nu_tail[1] & 0xffffffffu) + 8);
+	const int log_n = (int)std::max<uint64_t>(AL_LOGTAB_N, (log_need + 4095) / 4096 * 4096);   // room to spare
 	if (A->logtab_a != c->opt.a || A->logtab_n < log_n) {
 		std::vector<float> h(2 * (size_t)log_n);
 		for (int k = 0; k < log_n; ++k) { h[k] = logf((float)k / c->opt.a); h[log_n + k] = logf((float)k); }
@@ -3076,13 +3093,6 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipStreamSynchronize(s));
 		A->logtab_a = c->opt.a; A->logtab_n = log_n;
 	}
-	// workspace sizes from the number of chains
-	if (A->nu_off.ensure(nf + 2)) return -1;
-	AL_HIP_CHECK(hipMemsetAsync(c->frag_nu.p + nf, 0, 4, s));
-	if (scan32(c, c->frag_nu.p, A->nu_off.p, nf)) return -1;
-	uint64_t nu_total = 0;
-	AL_HIP_CHECK(hipMemcpyAsync(&nu_total, A->nu_off.p + nf, 8, hipMemcpyDeviceToHost, s));
-	AL_HIP_CHECK(hipStreamSynchronize(s));
 	const uint64_t Btot = 4 * nu_total + 4ULL * nf + 8;
 	if ((!c->no_taps && c->seg_a.ensure(c->n_anchor_total + 1)) || A->regs0.ensure(nu_total + 1) || A->aux128.ensure(Btot) || A->aux64.ensure(Btot) || A->auxi.ensure(2 * Btot) ||
 	    A->seg_u.ensure(2 * nu_total + 2) || A->reg_cnt.ensure(nr + 1) || A->seg_na.ensure(nr + 1) || A->out_off.ensure(nr + 2) || A->seg_fast.ensure(nr + 1) || A->cap2.ensure(nf + 2) || A->b2_off.ensure(nf + 2)) return -1;
@@ -3102,6 +3112,8 @@ int al_run_align_stage(al_ctx_t *c)
 	W.nu_off = A->nu_off.p; W.frag_nu = c->frag_nu.p; W.a_off = c->a_off.p; W.reg_cnt = A->reg_cnt.p; W.seg_na = A->seg_na.p; W.seg_fast = A->seg_fast.p; W.cap2 = nullptr; W.b2_off = nullptr; W.mregs = nullptr; W.rtmp = nullptr; W.rext = nullptr;
 	// fragments with many chains: chain_post by a wavefront each (k_regs_select), by chain-count class
 	uint32_t *regs_n0 = nullptr; uint32_t heavy_from = 0, heavy_n = 0; uint64_t Btot2 = 0;
+	for (int i = 0; i < 7; ++i) A->tap_lb[i] = 0;
+	A->tap_select = false;
 	if (!((c->P.dbg >> 19) & 1)) {
 		if (A->regs_n0.ensure(nf + 1) || c->chain_key.ensure(nf + 1) || c->chain_idx.ensure(nf + 1) || c->chain_idx2.ensure(nf + 1) || c->lb_buf.ensure(16)) return -1;
 		regs_n0 = A->regs_n0.p;
@@ -3115,6 +3127,8 @@ int al_run_align_stage(al_ctx_t *c)
 		AL_HIP_CHECK(hipMemcpyAsync(lb, c->lb_buf.p, 28, hipMemcpyDeviceToHost, s));
 		AL_HIP_CHECK(hipStreamSynchronize(s));
 		const uint32_t *ord = c->chain_idx2.p;
+		for (int i = 0; i < 7; ++i) A->tap_lb[i] = lb[i];
+		A->tap_select = true;
 		T.n = 1; T.v[0] = 9;      // fragments with at least nine chains may keep at least nine hits: candidates of k_regs_heavy
 		{ uint32_t i9 = (uint32_t)nf; AL_HIP_CHECK(hipMemcpyAsync(c->lb_buf.p, &i9, 4, hipMemcpyHostToDevice, s)); hipLaunchKernelGGL(k_lower_bounds, dim3((nf + 255) / 256), dim3(256), 0, s, (const uint32_t *)c->chain_key.p, (uint32_t)nf, T, c->lb_buf.p);
 		  AL_HIP_CHECK(hipMemcpyAsync(&i9, c->lb_buf.p, 4, hipMemcpyDeviceToHost, s)); AL_HIP_CHECK(hipStreamSynchronize(s)); heavy_from = i9; heavy_n = (uint32_t)nf - i9; }
@@ -3221,6 +3235,8 @@ int al_run_align_stage(al_ctx_t *c)
 		        (unsigned long long)n_done, (unsigned long long)n_set, mx_set, mx_set_nu, (unsigned long long)n_unset, mx_unset);
 	}
 	AL_HIP_CHECK(hipEventRecord(c->ev[ST_REGS + 1], s));
+	for (int i = 0; i < 5; ++i) A->tap_hv[i] = hv_cnt[i];
+	if (A->regs_only && !map_only) { AL_HIP_CHECK(hipStreamSynchronize(s)); AL_HIP_CHECK(hipGetLastError()); return 0; }   // (the al_dbg_regs tap: the stage product is in place)
 	if (map_only) {   // no extension stage: no jobs, no DP, no CIGAR arena, no traceback areas -- MAPQ of the chain-level hits and the dense output in one step
 		for (int i = ST_EXT_PREP; i <= ST_EXT_FINISH; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s));        // (empty intervals)
 		AL_HIP_CHECK(hipMemsetAsync(A->reg_cnt.p + nr, 0, 4, s));
@@ -3502,6 +3518,109 @@ extern "C" int al_dbg_ext_dp(al_ctx_t *c, int n, const int64_t *jobs8 /* read, r
 	if (rc) (void)hipDeviceSynchronize();
 	(void)hipFree(d_in); (void)hipFree(d_out); (void)hipFree(d_cig);
 	return rc;
+}
+
+// Tap (parity tests): the stage between chaining and extension on caller-supplied chains -- see include/airlift.h.  The batch's fragments, read lengths
+// and name hashes are the uploaded ones; the chain lists take the place of what the chain stage would have left.  al_run_align_stage itself runs, up to the
+// ST_REGS event (a map-only context: to its end), so the class bounds, the launches and their streams are the stage's own.
+static_assert(sizeof(AlReg) == 112, "al_dbg_regs_fetch hands AlReg records out as 28 words each");
+extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep,
+                           uint32_t *reg_cnt, uint32_t *seg_na, uint32_t *regs_n0, uint32_t *frag_hash, uint64_t *counts, uint64_t *sizes)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || (int)c->h_rd_len.size() < c->n_reads || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_regs: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	const int nf = c->n_frag, nr = c->n_reads;
+	// every chain inside its fragment's range and every anchor inside its read: the kernels index their tables by both
+	if (a_off[0] != 0) return -2;
+	for (int f = 0; f < nf; ++f) {
+		if (a_off[f + 1] < a_off[f] || a_off[f + 1] - a_off[f] > 0x7fffffffu) return -2;
+		const uint64_t na = a_off[f + 1] - a_off[f], base = a_off[f] + (uint64_t)f; uint64_t sum = 0;
+		const uint32_t r0 = c->h_frag_first[f], n_segs = c->h_frag_first[f + 1] - r0;
+		if (n_segs < 1 || n_segs > 2 || nu[f] > na) return -2;
+		const int64_t ql0 = c->h_rd_len[r0], ql1 = n_segs > 1 ? c->h_rd_len[r0 + 1] : 0;
+		for (uint32_t i = 0; i < nu[f]; ++i) {
+			const uint64_t cnt = (uint32_t)u[base + i];
+			if (cnt == 0 || cnt > 0x7fffffffu || (uint64_t)uo[base + i] + cnt > na) return -2;
+			sum += cnt;
+			for (uint64_t j = 0; j < cnt; ++j) {
+				const uint64_t x = chained_xy[2 * (a_off[f] + uo[base + i] + j)], y = chained_xy[2 * (a_off[f] + uo[base + i] + j) + 1];
+				const int64_t sid = (int64_t)((y & AL_SEED_SEG_MASK) >> AL_SEED_SEG_SHIFT), span = (int64_t)(y >> 32 & 0xff), q = (int32_t)y;
+				if (sid >= (int64_t)n_segs || span < 1 || (y >> 56) != 0 || (int32_t)x < 0) return -2;
+				const int64_t qls = sid ? ql1 : ql0, acc = sid ? ql0 : 0, q1 = q - ((x >> 63) ? (ql0 + ql1) - (qls + acc) : acc);   // the position inside its mate (hit.c:397)
+				if (q1 + 1 - span < 0 || q1 >= qls) return -2;
+			}
+		}
+		if (sum > na) return -2;
+	}
+	const uint64_t total = a_off[nf];
+	AL_HIP_CHECK(hipSetDevice(c->device));
+	al_nomem_flag() = false;
+	hipStream_t s = c->stream;
+	AlignState *A = get_state(c);
+	c->n_anchor_pass1 = total; c->n_anchor_total = total; c->n_rechain = 0; c->ran = false;
+	if (c->anchors.ensure(total + 1) || c->chained.ensure(total + 1) || c->u.ensure(total + nf + 2) || c->uo.ensure(total + nf + 2)) return -1;
+	AL_HIP_CHECK(hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), s));
+	if (total) AL_HIP_CHECK(hipMemcpyAsync(c->chained.p, chained_xy, (size_t)total * 16, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->u.p, u, (size_t)(total + nf + 1) * 8, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->uo.p, uo, (size_t)(total + nf + 1) * 4, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->a_off.p, a_off, ((size_t)nf + 1) * 8, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->frag_nu.p, nu, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipMemcpyAsync(c->frag_rep.p, frag_rep, (size_t)nf * 4, hipMemcpyHostToDevice, s));
+	AL_HIP_CHECK(hipStreamSynchronize(s));                                   // (the host arrays are the caller's)
+	A->regs_only = true;
+	const int rc = al_run_align_stage(c);
+	A->regs_only = false;
+	if (rc) { (void)hipDeviceSynchronize(); return rc; }
+	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) AL_HIP_CHECK(hipStreamSynchronize(c->phys[p]));
+	AL_HIP_CHECK(hipStreamSynchronize(s));
+	AL_HIP_CHECK(hipGetLastError());
+	AL_HIP_CHECK(hipMemcpy(reg_cnt, A->reg_cnt.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+	AL_HIP_CHECK(hipMemcpy(seg_na, A->seg_na.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+	if (A->tap_select) AL_HIP_CHECK(hipMemcpy(regs_n0, A->regs_n0.p, (size_t)nf * 4, hipMemcpyDeviceToHost));
+	else for (int f = 0; f < nf; ++f) regs_n0[f] = AL_REGS_UNSET;
+	for (int f = 0; f < nf; ++f) frag_hash[f] = c->h_frag_hash[f];
+	unsigned long long cn[16] = {};
+	AL_HIP_CHECK(hipMemcpy(cn, c->counters.p, sizeof(cn), hipMemcpyDeviceToHost));
+	for (int i = 0; i < 7; ++i) counts[i] = A->tap_lb[i];
+	for (int i = 0; i < 5; ++i) counts[7 + i] = A->tap_hv[i];
+	counts[12] = cn[8]; counts[13] = cn[10]; counts[14] = A->tap_select ? 1 : 0; counts[15] = al_map_only(c->opt.flag) ? (uint32_t)cn[14] : 0; counts[16] = (uint64_t)A->logtab_n;
+	uint64_t n_regs = 0; for (int r = 0; r < nr; ++r) n_regs += reg_cnt[r];
+	sizes[0] = n_regs; sizes[1] = al_map_only(c->opt.flag) ? A->out_total : 0;
+	return 0;
+}
+
+// ... and what it left on the device: every read's hits (AlReg records, read after read, reg_cnt[r] each) from the per-mate arrays, the per-mate anchor
+// array (a_off[n_frag] anchors, laid out as the context's: mate 0's anchors of fragment f from a_off[f], mate 1's seg_na of mate 0 further on), and in a
+// map-only context the dense output k_map_only / k_map_only_wave wrote (the same hits with their MAPQ)
+extern "C" int al_dbg_regs_fetch(al_ctx_t *c, void *regs_out, uint64_t n_regs, uint64_t *seg_a_xy, void *dense_out, uint64_t n_dense)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1) return -1;
+	AlignState *A = get_state(c);
+	const int nf = c->n_frag, nr = c->n_reads;
+	if (!A->cap2.p || !A->b2_off.p || !A->mregs.p || !A->reg_cnt.p) return -1;
+	AL_HIP_CHECK(hipSetDevice(c->device));
+	std::vector<uint32_t> cap2((size_t)nf + 1), rc((size_t)nr + 1); std::vector<uint64_t> b2((size_t)nf + 1);
+	AL_HIP_CHECK(hipMemcpy(cap2.data(), A->cap2.p, ((size_t)nf + 1) * 4, hipMemcpyDeviceToHost));
+	AL_HIP_CHECK(hipMemcpy(b2.data(), A->b2_off.p, ((size_t)nf + 1) * 8, hipMemcpyDeviceToHost));
+	AL_HIP_CHECK(hipMemcpy(rc.data(), A->reg_cnt.p, (size_t)nr * 4, hipMemcpyDeviceToHost));
+	if (2 * b2[nf] > A->mregs.cap) return -1;
+	std::vector<AlReg> all((size_t)(2 * b2[nf] + 1));
+	if (b2[nf]) AL_HIP_CHECK(hipMemcpy(all.data(), A->mregs.p, (size_t)(2 * b2[nf]) * sizeof(AlReg), hipMemcpyDeviceToHost));
+	AlReg *out = (AlReg *)regs_out; uint64_t k = 0;
+	for (int f = 0; f < nf; ++f) {
+		const uint32_t r0 = c->h_frag_first[f], n_segs = c->h_frag_first[f + 1] - r0;
+		for (uint32_t m = 0; m < n_segs; ++m) {
+			if (rc[r0 + m] > cap2[f] || k + rc[r0 + m] > n_regs) return -2;
+			for (uint32_t i = 0; i < rc[r0 + m]; ++i) out[k++] = all[(size_t)(2 * b2[f] + (uint64_t)m * cap2[f] + i)];
+		}
+	}
+	if (k != n_regs) return -2;
+	const AlAnchor *sa = c->no_taps ? c->anchors.p : c->seg_a.p;
+	if (c->n_anchor_total) AL_HIP_CHECK(hipMemcpy(seg_a_xy, sa, (size_t)c->n_anchor_total * 16, hipMemcpyDeviceToHost));
+	if (n_dense) {
+		if (!al_map_only(c->opt.flag) || n_dense != A->out_total) return -2;
+		AL_HIP_CHECK(hipMemcpy(dense_out, A->out.p, (size_t)n_dense * sizeof(AlReg), hipMemcpyDeviceToHost));
+	}
+	return 0;
 }
 
 int al_run_tags(al_ctx_t *c)

@@ -295,6 +295,24 @@ int  al_dbg_ext_dp(al_ctx_t *ctx, int n, const int64_t *jobs8, int32_t *out9, ui
  * fragments chained whole after them, size of the second round, fragments under AL_TEST_SEG_BIG, fragments of the fallback's virtual batches,
  * n_chain_fallback, lds_ok, tiles_ok, tile_from, the list positions of 1, 65 and 129 anchors, lmin.  Returns 0; -2: offsets out of order. */
 int  al_dbg_chain(al_ctx_t *ctx, const uint64_t *anchors_xy, const uint64_t *a_off, const uint32_t *tie_flag, uint32_t *nu_out, uint64_t *u_out, uint32_t *uo_out, uint64_t *chained_xy, uint64_t *counts);
+/* Tap (parity tests): the stage between chaining and extension -- a fragment's chains to its per-mate hits (mm_gen_regs, mm_set_parent,
+ * mm_select_sub(_multi), mm_seg_gen, the per-mate mm_set_parent and the squeeze) -- on caller-supplied chains, through the host code the stage runs
+ * for a batch: the chain-count classes and their k_regs_select launches, k_regs_heavy_classify and the k_regs_heavy tiles, k_regs_cap2 and the parts
+ * of k_regs, on their streams, up to the stage's ST_REGS event; in a map-only context (AL_F_OUT_PAF without AL_F_CIGAR) on through k_map_only and
+ * k_map_only_wave.  Needs a batch uploaded with al_batch_upload and NOT run (dummy reads of the wanted lengths and names will do).  In: what
+ * al_dbg_chain puts out (nu, u, uo, chained_xy over a_off) and frag_rep[n_frag], the fragments' rep_len.  Out: reg_cnt / seg_na[n_reads]; regs_n0 and
+ * frag_hash[n_frag] (regs_n0: kept hits, 0xfffffffe = finished by k_regs_heavy, 0xffffffff = left to k_regs, 0xfffffff1 ... 3 = the selection gave
+ * up; all 0xffffffff when the selection kernels did not run); counts[17]: the list positions of 5, 65, 1025, 8193, 2049, 4097 and 257 chains, the
+ * fragments per k_regs_heavy tile (12, 24, 48, 72, 200 hits), log-table misses, sort ties seen, whether the selection kernels ran, mates given to
+ * k_map_only_wave, entries of the log table; sizes[2]: hits of all reads, records of the dense map-only output.  Returns 0; -2: a chain outside its
+ * fragment's anchors or an anchor outside its read (nothing ran).
+ * al_dbg_regs_fetch, after it: regs_out[n_regs] = the per-mate hits as 112-byte device records (id cnt rid score | qs qe rs re | parent subsc as mlen |
+ * blen n_sub score0 hash | mapq flags ...; flags = split | rev << 2 | inv << 3 | sam_pri << 4 | proper << 5 | pe_thru << 6 | seg_split << 7 |
+ * seg_id << 8 | split_inv << 16 | has_p << 17), read after read; seg_a_xy: the per-mate anchors, a_off[n_frag] of them (mate 0's of fragment f from
+ * a_off[f], mate 1's seg_na[mate 0] further on; a hit's are [as, as + cnt) of its mate's); dense_out[n_dense]: the map-only output, same order. */
+int  al_dbg_regs(al_ctx_t *ctx, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep,
+                 uint32_t *reg_cnt, uint32_t *seg_na, uint32_t *regs_n0, uint32_t *frag_hash, uint64_t *counts, uint64_t *sizes);
+int  al_dbg_regs_fetch(al_ctx_t *ctx, void *regs_out, uint64_t n_regs, uint64_t *seg_a_xy, void *dense_out, uint64_t n_dense);
 /* Tap (parity tests): the seed stage of a pass as a batch run launches it -- sketch, seed lookup, anchor collection, the sorts and the merges of the
  * flagged fragments, on their streams and in their order -- without the chaining.  Needs a batch uploaded with al_batch_upload.  list == NULL: the
  * first pass (mid_occ) on every fragment.  list[n_list], ascending fragment ids: the re-chain pass of those fragments with max_occ, in the place of

@@ -1436,6 +1436,70 @@ static oreg_t *align_regs(const oopt_t *opt, const oidx_t *mi, int qlen, const c
 	return regs;
 }
 
+/* ---------------------------------------------------------------- stage-level entry: chains in, per-mate hits out (ref: map.c:379-403 without align_regs)
+ * The hit-stage tests compare this, fragment by fragment, with oracle/hitref_shim.c's hitref_frag() over the reference's own functions; arguments,
+ * results and the layout of a hit (O_HIT_NF words) are the shim's. */
+#define O_HIT_NF 22
+static void hit_put(int32_t *o, const oreg_t *r)
+{
+	o[0] = r->id; o[1] = r->parent; o[2] = r->score; o[3] = r->score0; o[4] = r->cnt; o[5] = r->rid; o[6] = r->qs; o[7] = r->qe; o[8] = r->rs; o[9] = r->re;
+	o[10] = r->subsc; o[11] = r->n_sub; o[12] = (int32_t)r->hash; o[13] = r->mlen; o[14] = r->blen; o[15] = r->rev; o[16] = r->sam_pri; o[17] = r->seg_split;
+	o[18] = r->seg_id; o[19] = r->mapq; o[20] = r->split | r->inv << 2 | r->proper_frag << 3 | r->pe_thru << 4 | r->split_inv << 5 | (r->p != 0) << 6; o[21] = r->as;
+}
+
+static int64_t hit_mate(int n, oreg_t *r, o128_t *a, int min_chain_sc, int match_sc, int rep_len, int32_t *B, int32_t *C, uint64_t *anch)
+{
+	int i, j; int64_t k = 0;
+	squeeze_a(n, r, a);
+	for (i = 0; i < n; ++i) {
+		hit_put(B + (size_t)i * O_HIT_NF, &r[i]);
+		for (j = 0; j < r[i].cnt; ++j, ++k) anch[2 * k] = a[r[i].as + j].x, anch[2 * k + 1] = a[r[i].as + j].y;
+	}
+	set_mapq(n, r, min_chain_sc, match_sc, rep_len);
+	for (i = 0; i < n; ++i) hit_put(C + (size_t)i * O_HIT_NF, &r[i]);
+	return k;
+}
+
+int o_frag_hits(int n_u, const uint64_t *u_in, const uint64_t *a_xy, int64_t n_a, uint32_t hash, int n_segs, const int *qlens, int rep_len,
+                float mask_level, float pri_ratio, int best_n, int min_diff, int max_gap_ref, int sub_diff, int min_chain_sc, int match_sc,
+                int32_t *pre, int32_t *nA, int32_t *A, int32_t *nB, int32_t *B, int32_t *C, uint64_t *anch, int64_t *n_anch)
+{
+	int i, s, qlen_sum = 0, n_regs0 = n_u, n_regs[2] = {0, 0}; int64_t j;
+	uint64_t *u; o128_t *a; oreg_t *regs0, *regs[2] = {0, 0};
+	if (n_segs < 1 || n_segs > 2) return -1;
+	for (i = 0; i < n_segs; ++i) qlen_sum += qlens[i];
+	u = (uint64_t*)malloc((n_u > 0? n_u : 1) * 8); a = (o128_t*)malloc((n_a > 0? n_a : 1) * 16);
+	for (i = 0; i < n_u; ++i) u[i] = u_in[i];
+	for (j = 0; j < n_a; ++j) a[j].x = a_xy[2 * j], a[j].y = a_xy[2 * j + 1];
+	nB[0] = nB[1] = 0; n_anch[0] = n_anch[1] = 0;
+	regs0 = gen_regs(hash, qlen_sum, n_u, u, a);
+	set_parent(mask_level, n_regs0, regs0, sub_diff);
+	for (i = 0; i < n_regs0; ++i) pre[2 * i] = regs0[i].parent, pre[2 * i + 1] = regs0[i].as;
+	if (n_segs <= 1) select_sub(pri_ratio, min_diff, best_n, &n_regs0, regs0);
+	else select_sub_multi(pri_ratio, 0.2f, 0.7f, max_gap_ref, min_diff, best_n, n_segs, qlens, &n_regs0, regs0);
+	*nA = n_regs0;
+	for (i = 0; i < n_regs0; ++i) hit_put(A + (size_t)i * O_HIT_NF, &regs0[i]);
+	if (n_segs == 1) {
+		nB[0] = n_regs0;
+		n_anch[0] = hit_mate(n_regs0, regs0, a, min_chain_sc, match_sc, rep_len, B, C, anch);
+		free(regs0);
+	} else {
+		oseg_t *seg = seg_gen(hash, n_segs, qlens, n_regs0, regs0, n_regs, regs, a); int64_t k = 0;
+		free(regs0);
+		for (s = 0; s < n_segs; ++s) {
+			set_parent(mask_level, n_regs[s], regs[s], sub_diff);
+			nB[s] = n_regs[s];
+			n_anch[s] = hit_mate(n_regs[s], regs[s], seg[s].a, min_chain_sc, match_sc, rep_len, B + (size_t)s * n_u * O_HIT_NF, C + (size_t)s * n_u * O_HIT_NF, anch + 2 * k);
+			k += n_anch[s];
+			free(regs[s]);
+		}
+		for (s = 0; s < n_segs; ++s) free(seg[s].u), free(seg[s].a);
+		free(seg);
+	}
+	free(u); free(a);
+	return 0;
+}
+
 void o_map_frag(const oidx_t *mi, const oopt_t *opt, int n_segs, const int *qlens, const char **seqs,
                 int *n_regs, oreg_t **regs, const char *qname, int *rep_len_, ostat_t *st)
 {

@@ -106,6 +106,10 @@ void    o_ksw_extd2(int qlen, const uint8_t *query, int tlen, const uint8_t *tar
 o128_t *o_chain_dp(int max_dist_x, int max_dist_y, int bw, int max_skip, int max_iter, int min_cnt, int min_sc,
                    int n_segs, int64_t n, o128_t *a, int *n_u_, uint64_t **_u);
 o128_t *o_collect_seeds(const oidx_t *mi, int max_occ, const o128_t *mv, size_t n_mv, int qlen, int64_t *n_a, int *rep_len);
+/* a fragment's chains to its per-mate hits (map.c:379-403 without align_regs): see al_oracle.c and oracle/hitref_shim.c */
+int     o_frag_hits(int n_u, const uint64_t *u, const uint64_t *a_xy, int64_t n_a, uint32_t hash, int n_segs, const int *qlens, int rep_len,
+                    float mask_level, float pri_ratio, int best_n, int min_diff, int max_gap_ref, int sub_diff, int min_chain_sc, int match_sc,
+                    int32_t *pre, int32_t *nA, int32_t *A, int32_t *nB, int32_t *B, int32_t *C, uint64_t *anch, int64_t *n_anch);
 void    o_radix_sort_128x(o128_t *beg, o128_t *end);
 void    o_radix_sort_64(uint64_t *beg, uint64_t *end);
 
