@@ -92,6 +92,7 @@ class LiftStat(C.Structure):
 
 LIFT_HOST = 1                 # AL_LIFT_HOST of include/airlift.h
 LIFT_GPU_DEFLATE = 2          # AL_LIFT_GPU_DEFLATE
+LIFT_SORTED = 4               # AL_LIFT_SORTED: the lifted BAM in coordinate order
 
 
 def lift_bam(bam_in, chain, bam_out, bed_out, flags=0, device=-1, n_threads=3, level=5, piece_bytes=0):
@@ -205,6 +206,10 @@ def load():
         L.al_dbg_lift_host.argtypes = [vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp]; L.al_dbg_lift_host.restype = ci
         L.al_dbg_lift.argtypes = [ci, vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp, szp]; L.al_dbg_lift.restype = ci
         L.al_dbg_lift_window.argtypes = []; L.al_dbg_lift_window.restype = C.c_uint32
+    if hasattr(L, "al_dbg_lift_sorted"):   # (lift --sorted: the taps of the sorted form)
+        szp = C.POINTER(C.c_size_t); u32p = C.POINTER(C.c_uint32); u64p = C.POINTER(C.c_uint64)
+        L.al_dbg_lift_sorted_host.argtypes = [vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp, u32p, u64p]; L.al_dbg_lift_sorted_host.restype = ci
+        L.al_dbg_lift_sorted.argtypes = [ci, vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp, u32p, u64p, C.c_uint, szp]; L.al_dbg_lift_sorted.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)

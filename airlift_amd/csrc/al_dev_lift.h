@@ -29,6 +29,13 @@
 //
 // WALK (al_lift_walk_host, k_bam_walk).  From `start`, records follow each other by block_size; block_size < 32 or > 2^28 is malformed; the walk ends at
 // the first record that is not complete within the text (`consumed` = its offset).
+//
+// ORDER (lift --sorted; al_lift_key, k_lift_compact / k_lift_descents / k_lift_gather_sorted, the twin's sort).  The key of a kept record, taken AFTER the lift: ~0
+// (64 bits) when refID < 0, otherwise (uint64)refID << 32 | (uint32)pos -- the key of --sorted-bam (al_dev_bam.h).  Unmapped records are not dropped: a placed one
+// sorts at its lifted position, one without a position sorts last.  The sorted output holds exactly the records the unsorted output holds, byte for byte, in
+// non-decreasing key order; equal keys leave in input order (stable).  The rows of the unlifted records are not touched.  Per piece the kept records are compacted
+// to (key, record index), the descents -- positions i of the compacted list with key[i] < key[i - 1] -- are counted, and only a piece with a descent is sorted; the
+// pieces, each in order, are merged on the host (al_run_store.h).  The tie rule is this project's, as for --sorted-bam: the order is defined, not pinned to a tool.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -78,6 +85,8 @@ AL_DHD bool al_lift_iv(const AlLiftTab &T, int32_t ref, int64_t s, int64_t e, in
 	*q = (int32_t)B.qSlot; *d = (int64_t)B.qStart - (int64_t)B.tStart;
 	return true;
 }
+// the sort key of a kept record at r (its block_size field), after al_lift_record has patched it
+AL_DHD uint64_t al_lift_key(const uint8_t *r) { const uint32_t ref = al_lift_u32(r + 4); return (int32_t)ref < 0 ? ~0ull : (uint64_t)ref << 32 | al_lift_u32(r + 8); }
 // the reference bases the n_cig CIGAR words at c cover (c is not aligned)
 AL_DHD int64_t al_lift_reflen(const uint8_t *c, uint32_t n_cig)
 {
@@ -239,8 +248,9 @@ static inline int al_lift_bind(AlLiftChain &C, const AlLiftHeader &H, std::strin
 	return 0;
 }
 // The header of the lifted BAM: @SQ lines replaced by one per q-slot where the first old @SQ stood (without any: after a leading @HD, else first), an SO:
-// value of @HD becomes unsorted, other lines are kept; the binary reference list is the q-slots.
-static inline void al_lift_header_write(const AlLiftHeader &H, const AlLiftChain &C, std::vector<uint8_t> &out)
+// value of @HD becomes unsorted, other lines are kept; the binary reference list is the q-slots.  sorted (lift --sorted): the SO: value becomes coordinate, and
+// a text without an @HD line gets "@HD\tVN:1.6\tSO:coordinate" as its first line (the line al_bam_header writes for --sorted-bam), an @HD line without SO: gets one.
+static inline void al_lift_header_write(const AlLiftHeader &H, const AlLiftChain &C, std::vector<uint8_t> &out, bool sorted = false)
 {
 	std::string text = H.text, tail;
 	{ const size_t z = text.find('\0'); if (z != std::string::npos) { tail = text.substr(z); text.resize(z); } }   // (NUL padding stays behind the text)
@@ -251,14 +261,17 @@ static inline void al_lift_header_write(const AlLiftHeader &H, const AlLiftChain
 	auto is = [](const std::string &l, const char *tag) { return l.compare(0, 3, tag) == 0 && (l.size() == 3 || l[3] == '\t'); };
 	bool any_sq = false;
 	for (const std::string &l : lines) if (is(l, "@SQ")) any_sq = true;
-	std::string o; bool put = false;
+	std::string o; bool put = false, any_hd = false;
+	for (const std::string &l : lines) if (is(l, "@HD")) any_hd = true;
+	if (sorted && !any_hd) o += "@HD\tVN:1.6\tSO:coordinate\n";
 	if (!any_sq && (lines.empty() || !is(lines[0], "@HD"))) { o += sq; put = true; }
 	for (size_t i = 0; i < lines.size(); ++i) {
 		std::string l = lines[i];
 		if (is(l, "@SQ")) { if (!put) { o += sq; put = true; } continue; }
 		if (is(l, "@HD")) {
 			std::string m; size_t p = 0;
-			while (p <= l.size()) { size_t q = l.find('\t', p); if (q == std::string::npos) q = l.size(); std::string f = l.substr(p, q - p); if (f.compare(0, 3, "SO:") == 0) f = "SO:unsorted"; if (p) m += '\t'; m += f; p = q + 1; }
+			while (p <= l.size()) { size_t q = l.find('\t', p); if (q == std::string::npos) q = l.size(); std::string f = l.substr(p, q - p); if (f.compare(0, 3, "SO:") == 0) f = sorted ? "SO:coordinate" : "SO:unsorted"; if (p) m += '\t'; m += f; p = q + 1; }
+			if (sorted && m.find("\tSO:") == std::string::npos) m += "\tSO:coordinate";   // (an @HD line that names no order)
 			l = m;
 		}
 		o += l; o += '\n';

@@ -7,6 +7,10 @@
 // the other, and an arena with what the rows of the unlifted records need.  While one slot's gather and copy down run, the other slot takes its carry and its
 // piece.  A piece that holds no complete record doubles the next one.  Malformed input ends the walk with error -2 and a message that names the offset of the
 // record in the inflated stream.
+//
+// lift --sorted (set_sorted(true) before the first run()): run() also compacts the kept records to (key, record index) and counts the descents of the compacted
+// keys; gather() sorts the pairs when there is a descent (a stable sort) and packs the kept records in that order; sorted_out() gives the keys and the lengths
+// of the packed records, what AlRunStore::add_run (al_run_store.h) takes.  The arena is filled as without it.
 #pragma once
 #include <stdint.h>
 #include <stdio.h>
@@ -23,8 +27,11 @@ struct AlLiftPiece {
 	uint64_t n_rec = 0, consumed = 0; uint32_t walk_bad = 0;          // complete records from the start offset on, offset of the first incomplete one, its block_size is out of range
 	uint64_t first_bad = ~0ull; uint32_t bad_code = 0; uint64_t bad_off = 0;   // the first record al_lift_record refuses: its number, verdict and offset
 	uint64_t kept_bytes = 0, arena_bytes = 0, n_kept = 0, n_unlifted = 0, n_unmapped = 0;
+	uint64_t descents = 0;                                            // sorted: positions i of the compacted kept records with key[i] < key[i - 1]
+	uint64_t n_packed() const { return n_kept + n_unmapped; }
 };
-struct AlLiftRun { uint64_t pieces = 0, bytes_in = 0, kept = 0, unlifted = 0, unmapped_kept = 0; double read_s = 0, up_s = 0, inflate_s = 0, walk_s = 0, lift_s = 0, down_s = 0; };
+struct AlLiftRun { uint64_t pieces = 0, bytes_in = 0, kept = 0, unlifted = 0, unmapped_kept = 0; double read_s = 0, up_s = 0, inflate_s = 0, walk_s = 0, lift_s = 0, down_s = 0;
+	uint64_t in_order = 0, sorted_pieces = 0; double sort_s = 0, sgather_s = 0; };      // lift --sorted: pieces without / with a descent, seconds of the sorts and of the permuted gathers
 
 struct AlLiftBackend {
 	virtual ~AlLiftBackend() {}
@@ -42,6 +49,12 @@ struct AlLiftBackend {
 	virtual int fetch_records(int slot, uint32_t *rec_off, uint32_t *verdict, size_t n) = 0;   // of the slot's last run() (the taps)
 	virtual void stat(AlLiftRun &) {}                                                     // adds the backend's seconds
 	virtual size_t held() const { return 0; }                                             // device bytes of the backend's account
+	// lift --sorted
+	bool sorted = false;
+	void set_sorted(bool on) { sorted = on; }
+	virtual int sorted_out(int slot, const uint64_t **keys, const uint32_t **lens) = 0;   // after finish(): key and length of every packed record, in packed order
+	virtual int fetch_perm(int slot, uint32_t *perm, size_t n) = 0;                       // after finish(): the record index of every packed record (the taps)
+	virtual bool sort_launched(int slot) const = 0;                                       // the slot's last gather() launched a sort (the twin: ran std::stable_sort)
 };
 
 struct AlLiftSource {
@@ -101,7 +114,9 @@ template <class Emit> static inline int al_lift_stream(AlLiftBackend &B, AlLiftS
 // ---- the host backend: the twin (al_dev_lift.h) behind the same calls -----------------------------------------------------------------------------------------
 struct AlLiftHostBackend : AlLiftBackend {
 	AlLiftTab T; int n_threads; std::vector<uint8_t> txt[2], packed[2], arena[2]; std::vector<uint32_t> rec_off[2], verdict[2], keep_len[2], arena_len[2];
-	double inflate_s = 0, walk_s = 0, lift_s = 0;
+	std::vector<uint64_t> key[2], key_s[2]; std::vector<uint32_t> ridx[2], len_s[2];   // sorted: the compacted keys and record indices (ridx: in packed order after gather()), keys and lengths in packed order
+	bool did_sort[2] = {false, false};
+	double inflate_s = 0, walk_s = 0, lift_s = 0, sort_s = 0, sgather_s = 0;
 	typedef AlLiftSource::Timer Timer;
 	explicit AlLiftHostBackend(const AlLiftTab &t, int nt = 1) : T(t), n_threads(nt > 1 ? nt : 1) {}
 	const char *name() const override { return "host twin"; }
@@ -135,6 +150,11 @@ struct AlLiftHostBackend : AlLiftBackend {
 			if (o.verdict == AL_LIFT_KEPT) ++r->n_kept; else if (o.verdict == AL_LIFT_UNLIFTED) ++r->n_unlifted; else if (o.verdict == AL_LIFT_UNMAPPED) ++r->n_unmapped;
 			else if (r->first_bad == ~0ull) { r->first_bad = k; r->bad_code = o.verdict; r->bad_off = rec_off[s][k]; }
 		}
+		if (sorted) {
+			key[s].clear(); ridx[s].clear();
+			for (size_t k = 0; k < n; ++k) if (verdict[s][k] == AL_LIFT_KEPT || verdict[s][k] == AL_LIFT_UNMAPPED) { key[s].push_back(al_lift_key(txt[s].data() + rec_off[s][k])); ridx[s].push_back((uint32_t)k); }
+			for (size_t i = 1; i < key[s].size(); ++i) if (key[s][i] < key[s][i - 1]) ++r->descents;
+		}
 		return 0;
 	}
 	int gather(int s, const AlLiftPiece &r, bool) override
@@ -145,13 +165,34 @@ struct AlLiftHostBackend : AlLiftBackend {
 		for (size_t k = 0; k < (size_t)r.n_rec; ++k) {
 			const uint8_t *src = txt[s].data() + rec_off[s][k];
 			if (verdict[s][k] == AL_LIFT_UNLIFTED) { al_lift_arena_put(src, arena[s].data() + ao, 0, 1); ao += arena_len[s][k]; }
-			else if (keep_len[s][k]) { memcpy(packed[s].data() + po, src, keep_len[s][k]); po += keep_len[s][k]; }
+			else if (!sorted && keep_len[s][k]) { memcpy(packed[s].data() + po, src, keep_len[s][k]); po += keep_len[s][k]; }
+		}
+		if (sorted) {
+			const size_t nk = ridx[s].size();
+			did_sort[s] = r.descents != 0;
+			if (r.descents) {
+				Timer ts(sort_s);
+				std::vector<uint32_t> perm(nk); for (size_t i = 0; i < nk; ++i) perm[i] = (uint32_t)i;
+				std::stable_sort(perm.begin(), perm.end(), [&](uint32_t x, uint32_t y) { return key[s][x] < key[s][y]; });
+				for (size_t i = 0; i < nk; ++i) perm[i] = ridx[s][perm[i]];
+				ridx[s].swap(perm);
+			}
+			Timer tg(sgather_s);
+			key_s[s].resize(nk); len_s[s].resize(nk);
+			for (size_t i = 0; i < nk; ++i) {
+				const uint32_t k = ridx[s][i]; const uint8_t *src = txt[s].data() + rec_off[s][k];
+				key_s[s][i] = al_lift_key(src); len_s[s][i] = keep_len[s][k];
+				memcpy(packed[s].data() + po, src, keep_len[s][k]); po += keep_len[s][k];
+			}
 		}
 		return 0;
 	}
+	int sorted_out(int s, const uint64_t **k, const uint32_t **l) override { *k = key_s[s].data(); *l = len_s[s].data(); return 0; }
+	int fetch_perm(int s, uint32_t *perm, size_t n) override { if (n > ridx[s].size()) return -1; if (n) memcpy(perm, ridx[s].data(), n * 4); return 0; }
+	bool sort_launched(int s) const override { return did_sort[s]; }
 	int finish(int s, const uint8_t **p, const uint8_t **a) override { *p = packed[s].data(); *a = arena[s].data(); return 0; }
 	void *host_buffer(size_t) override { return nullptr; }
 	void host_buffer_free(void *) override {}
 	int fetch_records(int s, uint32_t *ro, uint32_t *v, size_t n) override { if (n) { memcpy(ro, rec_off[s].data(), n * 4); memcpy(v, verdict[s].data(), n * 4); } return 0; }
-	void stat(AlLiftRun &st) override { st.inflate_s += inflate_s; st.walk_s += walk_s; st.lift_s += lift_s; }
+	void stat(AlLiftRun &st) override { st.inflate_s += inflate_s; st.walk_s += walk_s; st.lift_s += lift_s; st.sort_s += sort_s; st.sgather_s += sgather_s; }
 };

@@ -9,6 +9,14 @@
 //                   table, the kept record patched in place; verdict, kept length, arena share
 //   (scan)          al_stream_scan_excl_u64 over the kept lengths and over the arena shares
 //   k_lift_gather   16 lanes per record: a kept record to the packed output, an unlifted record's descriptor, name and CIGAR words to the arena
+// lift --sorted only (the function: ORDER in al_dev_lift.h); without the flag none of these is launched:
+//   k_lift_flag          lane per record: 1 for a kept record (verdict KEPT or UNMAPPED), the scan's input
+//   (scan)               al_stream_scan_excl_u64 over the flags: a kept record's index in the compacted list, and their number
+//   k_lift_compact       lane per record: (key, record index) of a kept record to its compacted index
+//   k_lift_descents      lane per compacted index: key[i] < key[i - 1] counted per wavefront, one atomic per wavefront; the count comes down with run()'s counts
+//   (sort)               rocprim::radix_sort_pairs (stable) through al_prim_run, only when the piece has a descent
+//   k_lift_plen          lane per compacted index: the length of the record that leaves at that index; then the scan over them
+//   k_lift_gather_sorted 16 lanes per record: the unlifted records to the arena as k_lift_gather does, then kept record perm[i] to off[i]
 // A backend slot is an input-only AlStreamSlot (text, stream, inflater staging), as in al_select.hip.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
@@ -25,6 +33,8 @@
 #include "al_dev_inflate.h"
 #include "al_bam.h"
 #include "al_lift.h"
+#include "al_run_store.h"
+#include "al_prim.h"
 #include "../../include/airlift.h"
 
 #define AL_LIFT_W 8192u                       // bytes of a window (a power of two, a multiple of 64 x 16)
@@ -124,6 +134,54 @@ k_lift_gather(const uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_of
 	}
 }
 
+// ---- lift --sorted ---------------------------------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256)
+k_lift_flag(const uint32_t *__restrict__ verdict, uint32_t n_rec, uint32_t *__restrict__ flag)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r < n_rec) { const uint32_t v = verdict[r]; flag[r] = v == AL_LIFT_KEPT || v == AL_LIFT_UNMAPPED ? 1u : 0u; }
+	else if (r == n_rec) flag[r] = 0;                                       // (the scan's last element: the number of kept records)
+}
+__global__ void __launch_bounds__(256)
+k_lift_compact(const uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_off, uint32_t n_rec, const uint32_t *__restrict__ flag, const uint64_t *__restrict__ idx,
+               uint64_t *__restrict__ key, uint32_t *__restrict__ ridx)
+{
+	const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
+	if (r >= n_rec || !flag[r]) return;
+	const uint64_t i = idx[r];                                              // (< the number of kept records <= n_rec: the arrays hold n_rec + 2)
+	key[i] = al_lift_key(t + rec_off[r]); ridx[i] = r;
+}
+// n_kept: on the device (the scan's total); the grid covers n_rec, an upper bound of it
+__global__ void __launch_bounds__(256)
+k_lift_descents(const uint64_t *__restrict__ key, const uint64_t *__restrict__ n_kept, unsigned long long *__restrict__ cnt)
+{
+	const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x, n = *n_kept;
+	const bool d = i > 0 && i < n && key[i] < key[i - 1];
+	const unsigned long long m = __ballot(d);
+	if ((threadIdx.x & 63) == 0 && m) atomicAdd(cnt, (unsigned long long)__popcll(m));
+}
+__global__ void __launch_bounds__(256)
+k_lift_plen(const uint32_t *__restrict__ keep_len, const uint32_t *__restrict__ perm, uint32_t n_kept, uint32_t *__restrict__ plen)
+{
+	const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+	if (i < n_kept) plen[i] = keep_len[perm[i]];
+	else if (i == n_kept) plen[i] = 0;
+}
+// groups [0, n_rec): record r, when it is unlifted, to the arena; groups [n_rec, n_rec + n_kept): the kept record perm[i] to packed + off[i]
+__global__ void __launch_bounds__(256)
+k_lift_gather_sorted(const uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_off, uint32_t n_rec, const uint32_t *__restrict__ verdict, const uint64_t *__restrict__ arena_off, uint8_t *__restrict__ arena,
+                     const uint32_t *__restrict__ perm, uint32_t n_kept, const uint32_t *__restrict__ plen, const uint64_t *__restrict__ off, uint8_t *__restrict__ packed)
+{
+	const uint32_t g = blockIdx.x * 16 + (threadIdx.x >> 4), l = threadIdx.x & 15;
+	if (g < n_rec) { if (verdict[g] == AL_LIFT_UNLIFTED) al_lift_arena_put(t + rec_off[g], arena + arena_off[g], l, 16); return; }
+	const uint32_t i = g - n_rec;
+	if (i >= n_kept) return;
+	const uint8_t *src = t + rec_off[perm[i]];
+	const uint32_t len = plen[i];
+	uint8_t *o = packed + off[i];
+	for (uint32_t j = l; j < len; j += 16) o[j] = src[j];
+}
+
 namespace {
 
 #define LIFT_CHECK(x) AL_HIP_CHECK_AS("lift", x)
@@ -140,6 +198,13 @@ struct AlLiftDevBackend : AlLiftBackend {
 	hipEvent_t ev[2][6] = {};                                          // per slot: walk from / to, lift to, gather from / to, copy down to
 	bool gathered[2] = {false, false}; uint32_t n_rec[2] = {0, 0};
 	double up_s = 0, walk_s = 0, lift_s = 0, down_s = 0;
+	// lift --sorted: the kept flags and their scan, the compacted (key, record index) pairs and the sort's outputs and temporaries, lengths and offsets in packed order
+	DevBuf<uint32_t> kflag[2], ridx[2], ridx2[2], plen[2]; DevBuf<uint64_t> kidx[2], key[2], key2[2], poff[2]; DevBuf<uint8_t> sort_tmp[2];
+	PinnedVec<uint64_t> h_key[2]; PinnedVec<uint32_t> h_len[2];
+	const uint64_t *key_s[2] = {nullptr, nullptr}; const uint32_t *ridx_s[2] = {nullptr, nullptr};   // the pairs in packed order: key / ridx, or key2 / ridx2 after a sort
+	hipEvent_t ev_sort[2][2] = {};
+	bool did_sort[2] = {false, false}, refuse_tmp = false, noticed = false; size_t n_packed[2] = {0, 0};   // refuse_tmp (the taps): the sort's temporaries count as refused
+	double sort_s = 0, sgather_s = 0;
 
 	const char *name() const override { return "k_lift"; }
 	// 0, or 1 when there is no usable device or it refuses the memory (nothing is left allocated after the destructor)
@@ -153,6 +218,7 @@ struct AlLiftDevBackend : AlLiftBackend {
 		for (int i = 0; i < 2; ++i) {
 			if (al_stream_slot_init(S[i], nullptr, device, 1)) return 1;
 			for (hipEvent_t &e : ev[i]) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return 1; }
+			for (hipEvent_t &e : ev_sort[i]) if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return 1; }
 			if (al_stream_begin_text(S[i], 0, 2 * piece + 65536) || cnt[i].ensure(8)) return 1;
 			if (cap_in && al_stream_bgzf_init(S[i], cap_in, cap_mem)) return 1;
 		}
@@ -172,8 +238,10 @@ struct AlLiftDevBackend : AlLiftBackend {
 		for (int i = 0; i < 2; ++i) {
 			if (S[i].io) (void)hipStreamSynchronize(S[i].io);
 			rec_off[i].release(); verdict[i].release(); keep_len[i].release(); arena_len[i].release(); keep_off[i].release(); arena_off[i].release(); packed[i].release(); arena[i].release(); cnt[i].release();
+			kflag[i].release(); ridx[i].release(); ridx2[i].release(); plen[i].release(); kidx[i].release(); key[i].release(); key2[i].release(); poff[i].release(); sort_tmp[i].release();
 			al_stream_slot_destroy(S[i]);
 			for (hipEvent_t &e : ev[i]) if (e) (void)hipEventDestroy(e);
+			for (hipEvent_t &e : ev_sort[i]) if (e) (void)hipEventDestroy(e);
 		}
 		if (d_blk) al_dev_free(d_blk); if (d_pmax) al_dev_free(d_pmax); if (d_first) al_dev_free(d_first); if (d_ref) al_dev_free(d_ref);
 		if (h_cnt) (void)hipHostFree(h_cnt);
@@ -231,6 +299,17 @@ struct AlLiftDevBackend : AlLiftBackend {
 		if (verdict[s].ensure((size_t)nr + 2) || keep_len[s].ensure((size_t)nr + 2) || arena_len[s].ensure((size_t)nr + 2) || keep_off[s].ensure((size_t)nr + 2) || arena_off[s].ensure((size_t)nr + 2)) return -1;
 		hipLaunchKernelGGL(k_lift, dim3((nr + 256) / 256), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, nr, T, verdict[s].p, keep_len[s].p, arena_len[s].p, cnt[s].p, cnt[s].p + 1);
 		if (al_stream_scan_excl_u64(X, keep_len[s].p, keep_off[s].p, (size_t)nr + 1, st) || al_stream_scan_excl_u64(X, arena_len[s].p, arena_off[s].p, (size_t)nr + 1, st)) return -1;
+		if (sorted) {                                                   // the compacted (key, record index) pairs and their descents; the count comes down with the others
+			if (kflag[s].ensure((size_t)nr + 2) || kidx[s].ensure((size_t)nr + 2) || key[s].ensure((size_t)nr + 2) || ridx[s].ensure((size_t)nr + 2)) return -1;
+			LIFT_CHECK(hipMemsetAsync(cnt[s].p + 6, 0, 8, st));
+			hipLaunchKernelGGL(k_lift_flag, dim3((nr + 256) / 256), dim3(256), 0, st, verdict[s].p, nr, kflag[s].p);
+			if (al_stream_scan_excl_u64(X, kflag[s].p, kidx[s].p, (size_t)nr + 1, st)) return -1;
+			if (nr) {
+				hipLaunchKernelGGL(k_lift_compact, dim3((nr + 255) / 256), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, nr, kflag[s].p, kidx[s].p, key[s].p, ridx[s].p);
+				hipLaunchKernelGGL(k_lift_descents, dim3((nr + 255) / 256), dim3(256), 0, st, key[s].p, kidx[s].p + nr, cnt[s].p + 6);
+			}
+			LIFT_CHECK(hipMemcpyAsync(h + 8, cnt[s].p + 6, 8, hipMemcpyDeviceToHost, st));
+		}
 		LIFT_CHECK(hipEventRecord(ev[s][2], st));
 		LIFT_CHECK(hipMemcpyAsync(h, cnt[s].p, 32, hipMemcpyDeviceToHost, st));
 		LIFT_CHECK(hipMemcpyAsync(h + 6, keep_off[s].p + nr, 8, hipMemcpyDeviceToHost, st));
@@ -238,6 +317,7 @@ struct AlLiftDevBackend : AlLiftBackend {
 		LIFT_CHECK(hipStreamSynchronize(st));
 		LIFT_CHECK(hipGetLastError());
 		r->first_bad = h[0]; r->n_kept = h[1]; r->n_unlifted = h[2]; r->n_unmapped = h[3]; r->kept_bytes = h[6]; r->arena_bytes = h[7];
+		if (sorted) r->descents = h[8];
 		if (r->first_bad != ~0ull) {
 			uint32_t two[2] = {0, 0};
 			LIFT_CHECK(hipMemcpy(&two[0], rec_off[s].p + r->first_bad, 4, hipMemcpyDeviceToHost)); LIFT_CHECK(hipMemcpy(&two[1], verdict[s].p + r->first_bad, 4, hipMemcpyDeviceToHost));
@@ -251,6 +331,7 @@ struct AlLiftDevBackend : AlLiftBackend {
 	{
 		AlStreamSlot &X = S[s]; hipStream_t st = X.io;
 		if (packed[s].ensure((size_t)r.kept_bytes + 16) || arena[s].ensure((size_t)r.arena_bytes + 16) || h_arena[s].resize((size_t)r.arena_bytes + 1) || (packed_down && h_packed[s].resize((size_t)r.kept_bytes + 1))) return -1;
+		if (sorted) return gather_sorted(s, r);
 		LIFT_CHECK(hipEventRecord(ev[s][3], st));
 		if (r.n_rec) hipLaunchKernelGGL(k_lift_gather, dim3((unsigned)((r.n_rec + 15) / 16)), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, (uint32_t)r.n_rec, verdict[s].p, keep_len[s].p, keep_off[s].p, arena_off[s].p, packed[s].p, arena[s].p);
 		LIFT_CHECK(hipEventRecord(ev[s][4], st));
@@ -261,6 +342,51 @@ struct AlLiftDevBackend : AlLiftBackend {
 		gathered[s] = true;
 		return 0;
 	}
+	// lift --sorted: the pairs sorted when the piece has a descent, the kept records packed in that order, their keys and lengths brought down beside the bytes
+	int gather_sorted(int s, const AlLiftPiece &r)
+	{
+		AlStreamSlot &X = S[s]; hipStream_t st = X.io;
+		const size_t nk = (size_t)r.n_packed(); const uint32_t nr = (uint32_t)r.n_rec;
+		if (h_packed[s].resize((size_t)r.kept_bytes + 1)) return -1;
+		n_packed[s] = nk; did_sort[s] = false; key_s[s] = key[s].p; ridx_s[s] = ridx[s].p;
+		if (plen[s].ensure(nk + 2) || poff[s].ensure(nk + 2) || h_key[s].resize(nk + 1) || h_len[s].resize(nk + 1)) return -1;
+		if (r.descents) {
+			if (key2[s].ensure(nk + 2) || ridx2[s].ensure(nk + 2)) return -1;
+			LIFT_CHECK(hipEventRecord(ev_sort[s][0], st));
+			const int sr = refuse_tmp ? AL_ERR_NOMEM : al_prim_run(sort_tmp[s], [&](void *t, size_t &b) { return rocprim::radix_sort_pairs(t, b, (const uint64_t *)key[s].p, key2[s].p, (const uint32_t *)ridx[s].p, ridx2[s].p, nk, 0, 64, st); }, "lift");
+			if (sr == AL_ERR_NOMEM) {                                        // the temporaries are refused: this piece's order is made on the host from the keys
+				al_nomem_flag() = false;
+				if (!noticed) { fprintf(stderr, "[airlift] lift --sorted: no device memory for the sort's temporaries; the keys of such a piece are sorted on the host\n"); noticed = true; }
+				std::vector<uint64_t> k(nk), k2(nk); std::vector<uint32_t> x(nk), x2(nk), perm(nk);
+				LIFT_CHECK(hipMemcpyAsync(k.data(), key[s].p, nk * 8, hipMemcpyDeviceToHost, st)); LIFT_CHECK(hipMemcpyAsync(x.data(), ridx[s].p, nk * 4, hipMemcpyDeviceToHost, st));
+				LIFT_CHECK(hipStreamSynchronize(st));
+				for (size_t i = 0; i < nk; ++i) perm[i] = (uint32_t)i;
+				std::stable_sort(perm.begin(), perm.end(), [&](uint32_t a, uint32_t b) { return k[a] < k[b]; });
+				for (size_t i = 0; i < nk; ++i) { k2[i] = k[perm[i]]; x2[i] = x[perm[i]]; }
+				LIFT_CHECK(hipMemcpyAsync(key2[s].p, k2.data(), nk * 8, hipMemcpyHostToDevice, st)); LIFT_CHECK(hipMemcpyAsync(ridx2[s].p, x2.data(), nk * 4, hipMemcpyHostToDevice, st));
+				LIFT_CHECK(hipStreamSynchronize(st));                           // (the vectors go out of scope)
+			} else if (sr) return -1;
+			else did_sort[s] = true;
+			LIFT_CHECK(hipEventRecord(ev_sort[s][1], st));
+			key_s[s] = key2[s].p; ridx_s[s] = ridx2[s].p;
+		}
+		LIFT_CHECK(hipEventRecord(ev[s][3], st));
+		hipLaunchKernelGGL(k_lift_plen, dim3((unsigned)((nk + 256) / 256)), dim3(256), 0, st, keep_len[s].p, ridx_s[s], (uint32_t)nk, plen[s].p);
+		if (al_stream_scan_excl_u64(X, plen[s].p, poff[s].p, nk + 1, st)) return -1;
+		if (nr + nk) hipLaunchKernelGGL(k_lift_gather_sorted, dim3((unsigned)(((size_t)nr + nk + 15) / 16)), dim3(256), 0, st, X.txt[0].p, rec_off[s].p, nr, verdict[s].p, arena_off[s].p, arena[s].p,
+		                                ridx_s[s], (uint32_t)nk, plen[s].p, poff[s].p, packed[s].p);
+		LIFT_CHECK(hipEventRecord(ev[s][4], st));
+		if (r.arena_bytes) LIFT_CHECK(hipMemcpyAsync(h_arena[s].data(), arena[s].p, (size_t)r.arena_bytes, hipMemcpyDeviceToHost, st));
+		if (r.kept_bytes) LIFT_CHECK(hipMemcpyAsync(h_packed[s].data(), packed[s].p, (size_t)r.kept_bytes, hipMemcpyDeviceToHost, st));
+		if (nk) { LIFT_CHECK(hipMemcpyAsync(h_key[s].data(), key_s[s], nk * 8, hipMemcpyDeviceToHost, st)); LIFT_CHECK(hipMemcpyAsync(h_len[s].data(), plen[s].p, nk * 4, hipMemcpyDeviceToHost, st)); }
+		LIFT_CHECK(hipEventRecord(ev[s][5], st));
+		LIFT_CHECK(hipGetLastError());
+		gathered[s] = true;
+		return 0;
+	}
+	int sorted_out(int s, const uint64_t **k, const uint32_t **l) override { *k = h_key[s].data(); *l = h_len[s].data(); return 0; }
+	int fetch_perm(int s, uint32_t *perm, size_t n) override { if (n > n_packed[s]) return -1; if (n) LIFT_CHECK(hipMemcpy(perm, ridx_s[s], n * 4, hipMemcpyDeviceToHost)); return 0; }
+	bool sort_launched(int s) const override { return did_sort[s]; }
 	int finish(int s, const uint8_t **p, const uint8_t **a) override
 	{
 		LIFT_CHECK(hipStreamSynchronize(S[s].io));
@@ -268,7 +394,8 @@ struct AlLiftDevBackend : AlLiftBackend {
 		*p = h_packed[s].data(); *a = h_arena[s].data();
 		if (gathered[s]) {
 			float ms[2] = {0, 0};
-			if (hipEventElapsedTime(&ms[0], ev[s][3], ev[s][4]) == hipSuccess && hipEventElapsedTime(&ms[1], ev[s][4], ev[s][5]) == hipSuccess) { lift_s += ms[0] * 1e-3; down_s += ms[1] * 1e-3; } else (void)hipGetLastError();
+			if (hipEventElapsedTime(&ms[0], ev[s][3], ev[s][4]) == hipSuccess && hipEventElapsedTime(&ms[1], ev[s][4], ev[s][5]) == hipSuccess) { lift_s += ms[0] * 1e-3; down_s += ms[1] * 1e-3; if (sorted) sgather_s += ms[0] * 1e-3; } else (void)hipGetLastError();
+			if (sorted && did_sort[s]) { if (hipEventElapsedTime(&ms[0], ev_sort[s][0], ev_sort[s][1]) == hipSuccess) sort_s += ms[0] * 1e-3; else (void)hipGetLastError(); }
 			gathered[s] = false;
 		}
 		return 0;
@@ -290,7 +417,7 @@ struct AlLiftDevBackend : AlLiftBackend {
 		if (n) { LIFT_CHECK(hipMemcpy(ro, rec_off[s].p, n * 4, hipMemcpyDeviceToHost)); LIFT_CHECK(hipMemcpy(v, verdict[s].p, n * 4, hipMemcpyDeviceToHost)); }
 		return 0;
 	}
-	void stat(AlLiftRun &st) override { st.up_s += up_s; st.inflate_s += S[0].bz.kernel_s + S[1].bz.kernel_s; st.walk_s += walk_s; st.lift_s += lift_s; st.down_s += down_s; }
+	void stat(AlLiftRun &st) override { st.up_s += up_s; st.inflate_s += S[0].bz.kernel_s + S[1].bz.kernel_s; st.walk_s += walk_s; st.lift_s += lift_s; st.down_s += down_s; st.sort_s += sort_s; st.sgather_s += sgather_s; }
 };
 
 // The BAM header of a BGZF file: leading members inflated on the host until it is complete.  *file_off / *out_off: file and stream offset of the member
@@ -346,11 +473,12 @@ extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char 
 	if (rc) { close(fd); return rc; }
 	FILE *fo = fopen(bam_out, "wb"), *fb = fo ? fopen(bed_out, "wb") : nullptr;
 	if (!fo || !fb) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", fo ? bed_out : bam_out); if (fo) { fclose(fo); unlink(bam_out); } close(fd); return -1; }
+	const bool sorted = (flags & AL_LIFT_SORTED) != 0;
 	const bool host_backend = (flags & AL_LIFT_HOST) != 0, gpu_deflate = (flags & AL_LIFT_GPU_DEFLATE) != 0 && !host_backend;
 	const size_t zpiece = (size_t)al_env().inflate_piece_kb << 10, zcap = 2 * zpiece + 65536, zmem = zcap / 64 + 1024;
 	if (piece_bytes == 0) piece_bytes = std::max((size_t)8 << 20, 4 * zpiece);
 	if (piece_bytes >= ((size_t)1 << 29)) piece_bytes = (size_t)1 << 29;
-	std::atomic<size_t> acct{0}; AlLiftRun run; const char *backend = ""; double deflate_s = 0; rc = -1;
+	std::atomic<size_t> acct{0}; AlLiftRun run; const char *backend = ""; double deflate_s = 0, merge_s = 0; uint64_t spills = 0, runs_chained = 0; rc = -1;
 	{
 		std::unique_ptr<AlLiftBackend> B; AlLiftDevBackend *D = nullptr;
 		if (!host_backend) {
@@ -360,22 +488,32 @@ extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char 
 		}
 		if (!B) B.reset(new AlLiftHostBackend(C.tab(), n_threads));
 		backend = B->name();
+		B->set_sorted(sorted);
+		AlRunStore store; store.limit = (size_t)al_env_sort_mem();      // lift --sorted: the pieces, each in order, until the end of the input
 		{
 			AlBgzf z(fo, (level & 0xff) | (gpu_deflate && D ? 0x100 : 0), n_threads, D ? D->device : -1);
 			const size_t CH = (size_t)al_env().out_piece_mb << 20; char *ring[2] = {nullptr, nullptr};
 			bool ok = true;
 			if (z.dev_on) for (int i = 0; i < 2; ++i) if (hipHostMalloc((void **)&ring[i], CH, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); ring[i] = nullptr; ok = false; }
 			if (!ok) fprintf(stderr, "[ERROR] airlift: lift: no page-locked memory for the BAM output\n");
-			std::vector<uint8_t> hdr; al_lift_header_write(H, C, hdr);
+			std::vector<uint8_t> hdr; al_lift_header_write(H, C, hdr, sorted);
 			std::string rows;
 			if (ok && z.write((const char *)hdr.data(), hdr.size()) == 0) {
 				AlLiftBgzfSource src; src.fd = fd; src.B = B.get(); src.fn = bam_in;
 				if (src.open(zpiece, file_off, out_off) == 0) {
 					src.max_in = zcap; src.max_mem = zmem;
-					rc = al_lift_stream(*B, src, piece_bytes, start, out_off, bam_in, !z.dev_on, [&](int slot, const AlLiftPiece &r) -> int {
+					rc = al_lift_stream(*B, src, piece_bytes, start, out_off, bam_in, !z.dev_on || sorted, [&](int slot, const AlLiftPiece &r) -> int {
 						const uint8_t *packed = nullptr, *arena = nullptr;
 						if (B->finish(slot, &packed, &arena)) return -1;
-						if (z.dev_on) {
+						if (sorted) {
+							const uint64_t *keys = nullptr; const uint32_t *lens = nullptr;
+							if (B->sorted_out(slot, &keys, &lens)) return -1;
+							++(r.descents ? run.sorted_pieces : run.in_order);
+							const auto t0 = std::chrono::steady_clock::now();
+							const int ar = store.add_run(packed, (size_t)r.kept_bytes, keys, lens, (size_t)r.n_packed());
+							merge_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+							if (ar) return -1;
+						} else if (z.dev_on) {
 							const int wd = z.write_device((const char *)D->packed[slot].p, (size_t)r.kept_bytes, D->S[slot].io, ring, CH, D->S[slot].ev_out);
 							if (wd < 0) return -1;
 							if (wd > 0 && (D->fetch_packed(slot, r, &packed) || z.write((const char *)packed, (size_t)r.kept_bytes))) return -1;
@@ -384,6 +522,12 @@ extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char 
 						if (fwrite(rows.data(), 1, rows.size(), fb) != rows.size()) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bed_out); return -1; }
 						return 0;
 					}, run);
+				}
+				if (rc == 0 && sorted) {                                    // the merge: host bytes into the compressor, whichever it is
+					const auto t0 = std::chrono::steady_clock::now();
+					if (store.finish([&](const uint8_t *p, size_t n) { return z.write((const char *)p, n); })) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out); rc = -1; }
+					merge_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() - store.emit_s;
+					spills = store.spills; runs_chained = store.chained;
 				}
 				if (rc == 0 && z.finish()) { fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out); rc = -1; }
 			} else if (ok) fprintf(stderr, "[ERROR] failed to write the output to file '%s'\n", bam_out);
@@ -408,6 +552,9 @@ extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char 
 		fprintf(stderr, "[airlift] lift: '%s' (%s): %llu pieces, %llu bytes in, %llu kept, %llu unlifted, %llu unmapped kept; file read %.3f s, copy up %.3f s, inflate %.3f s, walk %.3f s, lift and gather %.3f s, copy down %.3f s, deflate %.3f s, wall %.3f s; device bytes held at return: %zu\n",
 		        bam_in, backend, (unsigned long long)run.pieces, (unsigned long long)run.bytes_in, (unsigned long long)run.kept, (unsigned long long)run.unlifted, (unsigned long long)run.unmapped_kept,
 		        run.read_s, run.up_s, run.inflate_s, run.walk_s, run.lift_s, run.down_s, deflate_s, wall, acct.load());
+	if (rc == 0 && sorted && al_env().timing)
+		fprintf(stderr, "[airlift] lift --sorted: %llu pieces in order, %llu pieces sorted, %llu chained onto the run before, %llu spills; sort %.3f s, permuted gather %.3f s, host merge %.3f s\n",
+		        (unsigned long long)run.in_order, (unsigned long long)run.sorted_pieces, (unsigned long long)runs_chained, (unsigned long long)spills, run.sort_s, run.sgather_s, merge_s);
 	return rc;
 }
 
@@ -435,6 +582,55 @@ static int lift_tap(AlLiftBackend &B, const void *bam, size_t n, size_t start, u
 	if (r.kept_bytes) memcpy(packed, p, (size_t)r.kept_bytes);
 	if (r.arena_bytes) memcpy(arena, a, (size_t)r.arena_bytes);
 	return 0;
+}
+// the sorted form: perm[0, sort3[0]): the record index of every packed record; sort3: packed records, descents, 1 when a sort was launched
+static int lift_tap_sorted(AlLiftBackend &B, const void *bam, size_t n, size_t start, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n,
+                           uint32_t *perm, uint64_t *sort3)
+{
+	AlLiftPiece r; const uint8_t *p = nullptr, *a = nullptr;
+	B.set_sorted(true);
+	sort3[0] = sort3[1] = sort3[2] = 0;
+	if (B.begin(0, n + 1) || B.append(0, (const uint8_t *)bam, n) || B.run(0, start, &r)) return -1;
+	out4[0] = r.n_rec; out4[1] = r.consumed; out4[2] = r.first_bad != ~0ull ? r.first_bad : r.walk_bad ? r.n_rec : ~0ull; out4[3] = r.first_bad != ~0ull ? r.bad_code : r.walk_bad ? AL_LIFT_BAD_SIZE : 0;
+	*packed_n = (size_t)r.kept_bytes; *arena_n = (size_t)r.arena_bytes;
+	if (r.n_rec > rec_cap || r.kept_bytes > packed_cap || r.arena_bytes > arena_cap) return -3;
+	if (B.fetch_records(0, rec_off, verdict, (size_t)r.n_rec)) return -1;
+	if (r.first_bad != ~0ull) { *packed_n = *arena_n = 0; return 0; }
+	if (B.gather(0, r, true) || B.finish(0, &p, &a) || B.fetch_perm(0, perm, (size_t)r.n_packed())) return -1;
+	sort3[0] = r.n_packed(); sort3[1] = r.descents; sort3[2] = B.sort_launched(0) ? 1 : 0;
+	const uint64_t *keys = nullptr; const uint32_t *lens = nullptr;
+	if (B.sorted_out(0, &keys, &lens)) return -1;
+	uint64_t sum = 0;
+	for (size_t i = 0; i < (size_t)r.n_packed(); ++i) { sum += lens[i]; if (i && keys[i] < keys[i - 1]) { fprintf(stderr, "[airlift] lift --sorted: the keys of the packed records descend at %zu\n", i); return -1; } }
+	if (sum != r.kept_bytes) { fprintf(stderr, "[airlift] lift --sorted: the lengths of the packed records sum to %llu, not %llu\n", (unsigned long long)sum, (unsigned long long)r.kept_bytes); return -1; }
+	if (r.kept_bytes) memcpy(packed, p, (size_t)r.kept_bytes);
+	if (r.arena_bytes) memcpy(arena, a, (size_t)r.arena_bytes);
+	return 0;
+}
+extern "C" int al_dbg_lift_sorted_host(const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n,
+                                       uint32_t *perm, uint64_t *sort3)
+{
+	AlLiftChain C; AlLiftHeader H; size_t start = 0;
+	if (const int r = lift_tap_prepare(bam, n, chain_fn, C, H, &start)) return r;
+	AlLiftHostBackend B(C.tab());
+	return lift_tap_sorted(B, bam, n, start, rec_off, verdict, rec_cap, out4, packed, packed_cap, packed_n, arena, arena_cap, arena_n, perm, sort3);
+}
+// tap_flags & 1: the sort's temporaries count as refused (the order of a piece with a descent is then made on the host, and no sort is launched)
+extern "C" int al_dbg_lift_sorted(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n,
+                                  uint32_t *perm, uint64_t *sort3, unsigned tap_flags, size_t *held)
+{
+	AlLiftChain C; AlLiftHeader H; size_t start = 0;
+	*held = 0;
+	if (const int r = lift_tap_prepare(bam, n, chain_fn, C, H, &start)) return r;
+	if (n >= ((size_t)1 << 31) - 65536) return -3;
+	std::atomic<size_t> acct{0}; int rc;
+	{
+		AlLiftDevBackend B; B.acct = &acct; B.refuse_tmp = (tap_flags & 1u) != 0;
+		if (B.open(device, C, n / 2 + 1, 0, 0)) return -1;
+		rc = lift_tap_sorted(B, bam, n, start, rec_off, verdict, rec_cap, out4, packed, packed_cap, packed_n, arena, arena_cap, arena_n, perm, sort3);
+	}
+	*held = acct.load();
+	return rc;
 }
 extern "C" int al_dbg_lift_host(const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n, void *arena, size_t arena_cap, size_t *arena_n)
 {

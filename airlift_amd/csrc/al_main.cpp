@@ -22,7 +22,7 @@
 //                                                                   the three scripts alone, file for file
 //          airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] OLD.fa NEW.fa CHAIN
 //                                                                   run/1_build_exact_chain_file.py: the exact chain file those scripts assume, verified or built on the GPU
-//          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
+//          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
 //                                                                   run_pipeline.sh:92-95 (FastRemap): the constant-region reads moved across the chain file on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
@@ -115,8 +115,9 @@ static int usage()
 	                "       --merged-in; --host: the kernels' host twin, no device is opened; malformed input is refused as FILE:LINE: reason)\n"
 	                "chain-exact: airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] old.fa new.fa chain  (1_build_exact_chain_file.py: the two\n"
 	                "       references compared over every block of the chain file on the GPU; verify prints the mismatch lines or PASS VERIFICATION, build the exact chain file)\n"
-	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
-	                "       (the reads in constant regions moved across the chain file on the GPU; the reads that do not lift leave as the rows extract-reads writes)\n"
+	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+	                "       (the reads in constant regions moved across the chain file on the GPU; the reads that do not lift leave as the rows extract-reads writes;\n"
+	                "       --sorted: OUT.bam in coordinate order, what samtools sort makes of it)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -157,6 +158,8 @@ int main(int argc, char **argv)
 			else if (!strcmp(argv[j], "--unmapped-bed") && j + 1 < argc) b_fn = argv[++j];
 			else if (!strcmp(argv[j], "--host")) lf |= AL_LIFT_HOST;
 			else if (!strcmp(argv[j], "--gpu-deflate")) lf |= AL_LIFT_GPU_DEFLATE;
+			else if (!strcmp(argv[j], "--sorted")) lf |= AL_LIFT_SORTED;
+			else if (!strcmp(argv[j], "--sort-mem") && j + 1 < argc) setenv("AL_SORT_MEM", std::to_string(parse_num(argv[++j], "--sort-mem")).c_str(), 1);   // --sorted: bytes held before the held runs are merged into a file
 			else if (!strcmp(argv[j], "-l") && j + 1 < argc) level = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
@@ -164,11 +167,14 @@ int main(int argc, char **argv)
 			else p.push_back(argv[j]);
 		}
 		if (p.size() != 1 || !c_fn || !o_fn || !b_fn || level < 0 || level > 9) {
-			fprintf(stderr, "Usage: airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+			fprintf(stderr, "Usage: airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
 			                "       (every record of in.bam, a BGZF file, through the chain file on the GPU: a mapped read that lies wholly and uniquely inside one block of a '+' chain\n"
 			                "       gets its new contig, position and bin and stays in OUT.bam, in input order and unsorted; one that does not becomes a row of FILE -- chrom start end\n"
 			                "       name[.1|.2] MAPQ CIGAR, what extract-reads writes -- and is re-aligned; unmapped reads are kept; --host: the kernels' host twin, no device is opened;\n"
-			                "       --gpu-deflate: OUT.bam's blocks are deflated on the GPU; -t: host threads of the compressor; --piece: inflated bytes per piece)\n");
+			                "       --gpu-deflate: OUT.bam's blocks are deflated on the GPU; -t: host threads of the compressor; --piece: inflated bytes per piece;\n"
+			                "       --sorted: OUT.bam holds the same records in coordinate order -- by new contig and position, records without a contig last, equal positions in\n"
+			                "       input order -- and its header says SO:coordinate: each piece is put in order on the GPU, the pieces are merged on the host; --sort-mem BYTES:\n"
+			                "       bytes held before the merged runs go to a temporary file in TMPDIR, default 16 GB, 0: never)\n");
 			return 1;
 		}
 		if ((lf & AL_LIFT_HOST) && (lf & AL_LIFT_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] lift: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }

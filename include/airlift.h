@@ -489,13 +489,19 @@ uint32_t al_dbg_chainexact_tile(void);
  * input order; a mapped record that does not lift leaves the BAM and becomes a row "chrom s e name[.1|.2] MAPQ CIGAR" of `bed_out` (the six columns
  * extract-reads writes); an unmapped record is always kept.  The header's @SQ lines and reference list become the chain's qNames, an SO: value becomes
  * unsorted.  The function is stated in full in airlift_amd/csrc/al_dev_lift.h.  flags: AL_LIFT_HOST -- the kernels' host twin, no device is opened (it also
- * takes over, with a notice, where the device or its memory is refused); AL_LIFT_GPU_DEFLATE -- the packed records are deflated where they lie.
+ * takes over, with a notice, where the device or its memory is refused); AL_LIFT_GPU_DEFLATE -- the packed records are deflated where they lie;
+ * AL_LIFT_SORTED -- `bam_out` holds the same records, byte for byte, in coordinate order: by refID << 32 | pos after the lift, records without a refID last
+ * (unmapped records stay: a placed one sorts at its lifted position), equal keys in input order; the header says SO:coordinate (a text without @HD gets the
+ * line "@HD VN:1.6 SO:coordinate" first); `bed_out` is the same.  Each piece is put in order on the device -- sorted only when it is not in order already --
+ * and the pieces are merged on the host, spilling merged runs to unlinked files in TMPDIR beyond AL_SORT_MEM bytes (0: never), as --sorted-bam does; the
+ * merged bytes go through the compressor from host memory, with AL_LIFT_GPU_DEFLATE too.  The figures of the sort are on the AL_TIMING line only.
  * level: the BGZF level; n_threads: host threads of the compressor and of the twin's inflater; piece_bytes: inflated bytes per piece (0: the default).
  * 0; -1 with a message (a chain file refused as FILE:LINE: reason, a file that is no BGZF file, the wrong reference, I/O); -2 malformed BAM input, the
  * message names the record's offset in the inflated stream.  On an error the two output files are removed.  All device memory is released before the
  * return (stat->held == 0). */
 #define AL_LIFT_HOST 1u
 #define AL_LIFT_GPU_DEFLATE 2u
+#define AL_LIFT_SORTED 4u
 typedef struct {
 	uint64_t kept, unlifted, unmapped_kept;   /* records: lifted and kept, gone to the BED, unmapped and kept */
 	uint64_t pieces, bytes_in, held;          /* pieces walked, inflated bytes, device bytes of the call's account at return */
@@ -514,6 +520,14 @@ int  al_dbg_lift_host(const void *bam, size_t n, const char *chain_fn, uint32_t 
 int  al_dbg_lift(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
                  void *arena, size_t arena_cap, size_t *arena_n, size_t *held);
 uint32_t al_dbg_lift_window(void);
+/* The same pass as AL_LIFT_SORTED makes it: packed holds the kept records in key order; perm[0, sort3[0]) (room for rec_cap): the record index of every
+ * packed record; sort3: packed records, descents (positions i of the kept records, in input order, whose key is below the key of the one before), 1 when a
+ * sort was launched (the twin: when it sorted) -- 0 for a piece without a descent.  tap_flags & 1: the sort's temporaries count as refused, the order is
+ * then made on the host and no sort is launched. */
+int  al_dbg_lift_sorted_host(const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
+                             void *arena, size_t arena_cap, size_t *arena_n, uint32_t *perm, uint64_t *sort3);
+int  al_dbg_lift_sorted(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
+                        void *arena, size_t arena_cap, size_t *arena_n, uint32_t *perm, uint64_t *sort3, unsigned tap_flags, size_t *held);
 
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
