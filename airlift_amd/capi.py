@@ -219,6 +219,8 @@ def load():
     if hasattr(L, "al_dbg_regs"):
         L.al_dbg_regs.argtypes = [vp] * 13; L.al_dbg_regs.restype = ci
         L.al_dbg_regs_fetch.argtypes = [vp, vp, C.c_uint64, vp, vp, C.c_uint64]; L.al_dbg_regs_fetch.restype = ci
+    if hasattr(L, "al_dbg_align"):
+        L.al_dbg_align.argtypes = [vp] * 8; L.al_dbg_align.restype = ci
     if hasattr(L, "al_dbg_seed"):
         L.al_dbg_seed.argtypes = [vp, vp, ci, vp]; L.al_dbg_seed.restype = ci
     L.al_version.restype = cs
@@ -425,6 +427,25 @@ class Context:
             raise AirliftError("al_dbg_regs_fetch failed: %d" % rc)
         return {"reg_cnt": rc_, "seg_na": sna, "regs_n0": n0, "frag_hash": fh, "regs": regs[:-1], "seg_a": seg_a[:tot], "dense": dense[:-1] if self.idx.mo.flag & AL_F_OUT_PAF and not self.idx.mo.flag & AL_F_CIGAR else None,
                 "counts": dict(zip(self.REGS_COUNTS, (int(x) for x in cnt)))}
+
+    ALIGN_COUNTS = ("n_early", "n_slow", "solo_early", "solo_slow", "mono_all", "long_mode", "tmax", "prep_heavy", "fin_heavy", "wave_prep", "wave_finish", "closed_form", "n_jobs",
+                    "limit", "log_miss", "arena_overflow", "reruns", "records", "arena_words", "dp_lane16", "dp_lane32", "dp_lane64", "dp_g1", "dp_g2", "dp_g4", "dp_g8", "dp_g22", "dp_g32", "dp_lds")
+
+    def align(self, nu, u, uo, chained, a_off, frag_rep):
+        """al_dbg_align: the extension stage on caller-supplied chains (what chain() returns, and the fragments' rep_len) for the uploaded batch (not
+        run), to its end and through the arena-overflow re-runs; fetch() then returns the records as after run().  Returns the counts by name."""
+        nf = self.n_frag
+        a_off = np.ascontiguousarray(a_off, dtype=np.uint64); tot = int(a_off[-1])
+        nu = np.ascontiguousarray(nu, dtype=np.uint32); u = np.ascontiguousarray(u, dtype=np.uint64); uo = np.ascontiguousarray(uo, dtype=np.uint32)
+        chained = np.ascontiguousarray(chained, dtype=np.uint64).reshape(-1, 2); frag_rep = np.ascontiguousarray(frag_rep, dtype=np.int32)
+        if len(a_off) != nf + 1 or len(nu) != nf or len(frag_rep) != nf or len(u) != tot + nf + 1 or len(uo) != tot + nf + 1 or len(chained) != tot:
+            raise AirliftError("al_dbg_align: arrays do not fit the uploaded batch")
+        cnt = np.zeros(len(self.ALIGN_COUNTS), dtype=np.uint64)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = load().al_dbg_align(self.h, p(nu), p(u), p(uo), p(chained), p(a_off), p(frag_rep), p(cnt))
+        if rc != 0:
+            raise AirliftError("al_dbg_align failed: %d" % rc)
+        return dict(zip(self.ALIGN_COUNTS, (int(x) for x in cnt)))
 
     SEED_COUNTS = ("small", "reg_2_1_128", "reg_4_1_256", "reg_8_1_512", "reg_16_1_512", "reg_8_4_1024", "reg_16_4_1024", "reg_16_8_1024", "sort1024", "merge_frags", "merge_tiles", "merge_passes",
                    "radix_frags", "radix_chunks", "flag_all", "compact", "rid_bits", "pos_bits", "rank_bits", "nl", "lb65", "lb129", "lb257", "lb513", "lb1025", "lb2049", "lb4097", "lb_big",

@@ -2894,6 +2894,8 @@ struct AlignState {            // lives in al_ctx_s::align_state (opaque there)
 	bool regs_only = false;
 	uint32_t tap_lb[7] = {}, tap_hv[5] = {};     // the chain-count class bounds in the order of k_lower_bounds' thresholds, fragments per k_regs_heavy tile
 	bool tap_select = false;                     // the selection kernels ran (regs_n0 is the last run's)
+	// the al_dbg_align tap: what the last run's host code decided in the extension stage (host words only; nothing is read back for them in a run)
+	struct { uint32_t n_early, n_slow, solo_early, solo_slow, mono_all, long_mode, tmax, prep_heavy, fin_heavy, n_jobs; } tap_ext = {};
 };
 static std::map<al_ctx_t *, AlignState *> g_states;
 static std::mutex g_states_mtx;
@@ -3269,6 +3271,8 @@ int al_run_align_stage(al_ctx_t *c)
 	AlLogTab lt; lt.t = A->logtab.p; lt.n = A->logtab_n; lt.miss = c->counters.p + 8;
 	const int tmax = eg.dp.tmax, qmax = eg.qmax;
 	const bool long_mode = eg.long_mode;              // reads beyond the LDS tiles: the whole batch through k_align_long (state blocks in HBM)
+	A->tap_ext = {}; A->tap_ext.long_mode = long_mode; A->tap_ext.tmax = (uint32_t)tmax;
+	bool last_solo = false;
 	if (long_mode && (Lmax > AL_LONG_QMAX || tbound > AL_LONG_TMAX)) { fprintf(stderr, "[airlift] reads longer than %d bp (or an extension window longer than %d bp: read length + (read length * A + end bonus - O) / E + 16) are not supported by the device extension kernels (max read length in batch: %d, window %d)\n", AL_LONG_QMAX, AL_LONG_TMAX, Lmax, tbound); return -3; }
 	if (long_mode) {   // few groups: each needs a state block of ~1.3 MB and a traceback area of (Lmax + window) * band columns bytes
 		if (nb > 16) nb = 16;
@@ -3280,6 +3284,7 @@ int al_run_align_stage(al_ctx_t *c)
 		// hits and DP calls, i.e. four divergent code paths executed one after the other -- and the stage waits for the slowest fragment (C5: 70 fragments,
 		// 111 ms).  Sixteen lanes of a wavefront alone run it up to four times as fast; the chip has room for a few hundred such wavefronts.
 		const bool solo = !long_mode && n_list > 0 && n_list <= nb * AL_GPB && n_list <= 512;
+		last_solo = solo;
 		const dim3 blk(solo ? GW : GW * AL_GPB);
 		if (solo) nbm = n_list;
 		if (long_mode) hipLaunchKernelGGL(k_align_long, dim3(nbm), dim3(GW * AL_GPB), 0, st, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, lt, wsp, stride, p_bytes, cig_words, nf, c->P, list, n_list, (GroupLong *)A->long_state.p);
@@ -3288,7 +3293,7 @@ int al_run_align_stage(al_ctx_t *c)
 		else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_align<1024, 512>), dim3(nbm), blk, 0, st, c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, lt, wsp, stride, p_bytes, cig_words, nf, c->P, list, n_list);
 		return 0;
 	};
-	if (((c->P.dbg >> 26) & 1) || long_mode) { if (A->gws.ensure((size_t)nb * AL_GPB * stride + 64)) return -1; if (launch_mono(nullptr, nf, s, A->gws.p, nb)) return -1; for (int i = ST_EXT_PREP; i <= ST_EXT_FINISH; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); }   // AL_DBG bit 26: whole batch through the monolithic kernel
+	if (((c->P.dbg >> 26) & 1) || long_mode) { if (A->gws.ensure((size_t)nb * AL_GPB * stride + 64)) return -1; if (launch_mono(nullptr, nf, s, A->gws.p, nb)) return -1; A->tap_ext.mono_all = 1; for (int i = ST_EXT_PREP; i <= ST_EXT_FINISH; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], s)); }   // AL_DBG bit 26: whole batch through the monolithic kernel
 	else {
 		// ---- fast path: prep -> size-sorted DP job queue -> finish -> (slow list) monolithic
 		if (A->n_jobs.ensure(nf + 2) || A->n_sc.ensure(nf + 2) || A->job_off.ensure(nf + 2) || A->sc_off.ensure(nf + 2) || A->frag_slow.ensure(nf + 1) || A->slow_list.ensure(nf + 1) || A->hist.ensure(AL_HIST_N)) return -1;
@@ -3315,6 +3320,7 @@ int al_run_align_stage(al_ctx_t *c)
 		// fragments with a dozen hits or more (the head of the hits-descending order): a wavefront each, a lane per hit, on the side stream beside the rest
 		const int heavy_env = al_env().prep_heavy.value_or(AL_PREP_HEAVY);      // (0: every fragment on a lane)
 		const int heavy_jobs = frag_ord ? heavy_env : 0;
+		A->tap_ext.prep_heavy = (uint32_t)heavy_jobs;
 		if (heavy_jobs > 0) {
 			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_fj[0], 0));
 			hipLaunchKernelGGL(k_ext_prep_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->on(AL_ROLE_SIDE), c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, W, G, E, nf, c->P, tmax, qmax, frag_ord, heavy_jobs);
@@ -3336,6 +3342,7 @@ int al_run_align_stage(al_ctx_t *c)
 			if (A->gws2.ensure((size_t)nbs * AL_GPB * stride + 64)) return -1;
 			AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_SIDE), c->ev_fj[0], 0));
 			if (launch_mono(A->early_list.p, (int)n_early, c->on(AL_ROLE_SIDE), A->gws2.p, nbs)) return -1;
+			A->tap_ext.solo_early = last_solo;
 			AL_HIP_CHECK(hipEventRecord(c->ev_fj[1], c->on(AL_ROLE_SIDE)));
 			return 0;
 		};
@@ -3366,6 +3373,7 @@ int al_run_align_stage(al_ctx_t *c)
 			// against 6.5 ... 8.4 with the wavefront form), while a 262 144-pair batch has few enough for the per-hit part to matter (3.6 -> 2.2 ms).
 			const int fin_env = al_env().fin_heavy;                    // (0: every fragment on a lane)
 			const int fin_heavy = !frag_ord ? 0 : fin_env >= 0 ? fin_env : nf <= 400000 ? AL_FIN_HEAVY : 0;
+			A->tap_ext.fin_heavy = (uint32_t)fin_heavy;
 			if (fin_heavy > 0) {
 				AL_HIP_CHECK(hipEventRecord(c->ev_fj[0], s)); AL_HIP_CHECK(hipStreamWaitEvent(c->on(AL_ROLE_AUX0), c->ev_fj[0], 0));   // (not the side stream: the monolithic kernel may still be running there)
 				hipLaunchKernelGGL(k_ext_finish_wave, dim3(std::min(nf, 16384)), dim3(64), 0, c->on(AL_ROLE_AUX0), c->rd_seq.p, c->rd_off.p, c->rd_len.p, c->frag_first.p, c->frag_rep.p, W, G, E, lt, A->sc_ws.p, A->sc_off.p, nf, c->P, A->slow_list.p, n_slow_d, 1, frag_ord, fin_heavy);
@@ -3381,9 +3389,11 @@ int al_run_align_stage(al_ctx_t *c)
 			int nbs = ((int)n_slow + AL_GPB - 1) / AL_GPB; if (nbs > 1024) nbs = 1024;
 			if (A->gws.ensure((size_t)nbs * AL_GPB * stride + 64)) return -1;
 			if (launch_mono(A->slow_list.p, (int)n_slow, s, A->gws.p, nbs)) return -1;
+			A->tap_ext.solo_slow = last_solo;
 		}
 		if (n_early > 0) AL_HIP_CHECK(hipStreamWaitEvent(s, c->ev_fj[1], 0));
 		c->stat_n_slow = n_slow + n_early;
+		A->tap_ext.n_early = n_early; A->tap_ext.n_slow = n_slow; A->tap_ext.n_jobs = nj;
 		if (al_env().trace) fprintf(stderr, "[airlift] trace: ext: of %d fragments the monolithic kernel takes %u known after prep (oversize, z-drop in a closed-form flank; side stream) and %u after the DP (CIGAR above the fast path's buffer)\n", nf, n_early, n_slow);
 		AL_HIP_CHECK(hipEventRecord(c->ev[ST_EXT_FINISH + 1], s));
 	}
@@ -3524,12 +3534,13 @@ extern "C" int al_dbg_ext_dp(al_ctx_t *c, int n, const int64_t *jobs8 /* read, r
 // and name hashes are the uploaded ones; the chain lists take the place of what the chain stage would have left.  al_run_align_stage itself runs, up to the
 // ST_REGS event (a map-only context: to its end), so the class bounds, the launches and their streams are the stage's own.
 static_assert(sizeof(AlReg) == 112, "al_dbg_regs_fetch hands AlReg records out as 28 words each");
-extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep,
-                           uint32_t *reg_cnt, uint32_t *seg_na, uint32_t *regs_n0, uint32_t *frag_hash, uint64_t *counts, uint64_t *sizes)
+// What al_dbg_regs and al_dbg_align check of the caller's chains before anything runs: every chain inside its fragment's range and every anchor inside its
+// read (the kernels index their tables by both); with_ref (the extension stage reads the reference by them): every anchor's k-mer inside its contig, and
+// every chain in the form chaining leaves it -- one contig and strand, reference and query positions ascending, so that a stretch's core has a length.
+static int dbg_chains_check(const al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, bool with_ref)
 {
-	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || (int)c->h_rd_len.size() < c->n_reads || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_regs: needs a batch uploaded with al_batch_upload\n"); return -1; }
-	const int nf = c->n_frag, nr = c->n_reads;
-	// every chain inside its fragment's range and every anchor inside its read: the kernels index their tables by both
+	const int nf = c->n_frag;
+	const uint32_t n_seq = with_ref ? al_idx_n_seq(c->mi) : 0;
 	if (a_off[0] != 0) return -2;
 	for (int f = 0; f < nf; ++f) {
 		if (a_off[f + 1] < a_off[f] || a_off[f + 1] - a_off[f] > 0x7fffffffu) return -2;
@@ -3547,15 +3558,28 @@ extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, c
 				if (sid >= (int64_t)n_segs || span < 1 || (y >> 56) != 0 || (int32_t)x < 0) return -2;
 				const int64_t qls = sid ? ql1 : ql0, acc = sid ? ql0 : 0, q1 = q - ((x >> 63) ? (ql0 + ql1) - (qls + acc) : acc);   // the position inside its mate (hit.c:397)
 				if (q1 + 1 - span < 0 || q1 >= qls) return -2;
+				if (with_ref) {
+					const uint64_t rid = x << 1 >> 33; const int64_t pos = (int32_t)x;
+					if (rid >= n_seq || pos + 1 - span < 0 || pos >= (int64_t)al_idx_seq_len(c->mi, (uint32_t)rid)) return -2;
+					if (j > 0) {
+						const uint64_t px = chained_xy[2 * (a_off[f] + uo[base + i] + j - 1)], py = chained_xy[2 * (a_off[f] + uo[base + i] + j - 1) + 1];
+						if ((px >> 32) != (x >> 32) || (int32_t)px >= (int32_t)x || (int32_t)py >= (int32_t)y) return -2;
+					}
+				}
 			}
 		}
 		if (sum > na) return -2;
 	}
+	return 0;
+}
+// ... and how both put them in the place of what the chain stage would have left
+static int dbg_chains_upload(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep)
+{
+	const int nf = c->n_frag;
 	const uint64_t total = a_off[nf];
 	AL_HIP_CHECK(hipSetDevice(c->device));
 	al_nomem_flag() = false;
 	hipStream_t s = c->stream;
-	AlignState *A = get_state(c);
 	c->n_anchor_pass1 = total; c->n_anchor_total = total; c->n_rechain = 0; c->ran = false;
 	if (c->anchors.ensure(total + 1) || c->chained.ensure(total + 1) || c->u.ensure(total + nf + 2) || c->uo.ensure(total + nf + 2)) return -1;
 	AL_HIP_CHECK(hipMemsetAsync(c->counters.p, 0, 32 * sizeof(unsigned long long), s));
@@ -3566,6 +3590,18 @@ extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, c
 	AL_HIP_CHECK(hipMemcpyAsync(c->frag_nu.p, nu, (size_t)nf * 4, hipMemcpyHostToDevice, s));
 	AL_HIP_CHECK(hipMemcpyAsync(c->frag_rep.p, frag_rep, (size_t)nf * 4, hipMemcpyHostToDevice, s));
 	AL_HIP_CHECK(hipStreamSynchronize(s));                                   // (the host arrays are the caller's)
+	return 0;
+}
+
+extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep,
+                           uint32_t *reg_cnt, uint32_t *seg_na, uint32_t *regs_n0, uint32_t *frag_hash, uint64_t *counts, uint64_t *sizes)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || (int)c->h_rd_len.size() < c->n_reads || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_regs: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	const int nf = c->n_frag, nr = c->n_reads;
+	if (int rc = dbg_chains_check(c, nu, u, uo, chained_xy, a_off, false)) return rc;
+	if (int rc = dbg_chains_upload(c, nu, u, uo, chained_xy, a_off, frag_rep)) return rc;
+	hipStream_t s = c->stream;
+	AlignState *A = get_state(c);
 	A->regs_only = true;
 	const int rc = al_run_align_stage(c);
 	A->regs_only = false;
@@ -3585,6 +3621,71 @@ extern "C" int al_dbg_regs(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, c
 	counts[12] = cn[8]; counts[13] = cn[10]; counts[14] = A->tap_select ? 1 : 0; counts[15] = al_map_only(c->opt.flag) ? (uint32_t)cn[14] : 0; counts[16] = (uint64_t)A->logtab_n;
 	uint64_t n_regs = 0; for (int r = 0; r < nr; ++r) n_regs += reg_cnt[r];
 	sizes[0] = n_regs; sizes[1] = al_map_only(c->opt.flag) ? A->out_total : 0;
+	return 0;
+}
+
+// al_run_align_stage until the batch's CIGARs fit the arena: what a batch run and the al_dbg_align tap both do.  reruns (may be NULL): how often the stage ran again.
+int al_align_run_to_fit(al_ctx_t *c, int *reruns)
+{
+	if (reruns) *reruns = 0;
+	for (int attempt = 0; ; ++attempt) {
+		if (al_run_align_stage(c)) return -1;
+		AL_HIP_CHECK(hipEventRecord(c->ev[ST_COMPACT + 1], c->stream));
+		AL_HIP_CHECK(hipStreamSynchronize(c->stream));
+		unsigned long long ovf = 0;
+		AL_HIP_CHECK(hipMemcpy(&ovf, c->counters.p + 9, 8, hipMemcpyDeviceToHost));
+		if (ovf == 0 || attempt >= 8) break;
+		// long CIGARs (repeat-rich or indel-rich batches) did not fit the arena: the alignment stage only reads the chaining
+		// results, so it is simply run again with twice the arena
+		if (al_env().trace) fprintf(stderr, "[airlift] trace: CIGAR arena overflow (%llu), re-running the alignment stage with twice the arena\n", ovf);
+		al_align_grow_arena(c);
+		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 4, 0, 8 * sizeof(unsigned long long), c->stream));     // [4..11]: stage statistics, error words, arena cursor
+		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 14, 0, sizeof(unsigned long long), c->stream));
+		if (reruns) ++*reruns;
+	}
+	return 0;
+}
+
+// Tap (parity tests): the extension stage on caller-supplied chains -- see include/airlift.h.  The batch is the uploaded one (real reads on the index's
+// contigs); the chain lists take the place of what the chain stage would have left, as in al_dbg_regs.  al_run_align_stage runs to its end inside the loop a
+// batch run has around it, the tag stage follows where the options ask for it, and the context is left as al_batch_run leaves it: al_batch_fetch works.
+// The counts are the host's own words of the last run (AlignState::tap_ext) and, read back here only, the job table k_ext_prep left.
+extern "C" int al_dbg_align(al_ctx_t *c, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep, uint64_t *counts)
+{
+	if (!c || c->dev_batch || c->n_frag <= 0 || (int)c->h_frag_first.size() < c->n_frag + 1 || (int)c->h_rd_len.size() < c->n_reads || !c->frag_first.p) { fprintf(stderr, "[airlift] al_dbg_align: needs a batch uploaded with al_batch_upload\n"); return -1; }
+	if (al_map_only(c->opt.flag)) return -1;
+	const int nf = c->n_frag;
+	if (int rc = dbg_chains_check(c, nu, u, uo, chained_xy, a_off, true)) return rc;
+	if (int rc = dbg_chains_upload(c, nu, u, uo, chained_xy, a_off, frag_rep)) return rc;
+	AlignState *A = get_state(c);
+	int reruns = 0;
+	int rc = al_align_run_to_fit(c, &reruns);
+	if (!rc && (al_tag_kind(c->opt.flag) || (c->opt.flag & AL_F_EQX))) rc = al_run_tags(c);
+	if (rc) { (void)hipDeviceSynchronize(); return rc; }
+	for (int p = 0; p < c->n_phys; ++p) if (c->phys[p]) AL_HIP_CHECK(hipStreamSynchronize(c->phys[p]));
+	AL_HIP_CHECK(hipGetLastError());
+	c->ran = true;
+	if (al_env().test_guard && al_dev_guard_check()) fprintf(stderr, "[airlift] GUARD: violations after al_dbg_align\n");
+	unsigned long long cn[16] = {};
+	AL_HIP_CHECK(hipMemcpy(cn, c->counters.p, sizeof(cn), hipMemcpyDeviceToHost));
+	const auto &T = A->tap_ext;
+	uint64_t wave_prep = 0, wave_fin = 0, closed = 0;
+	if (!T.mono_all) {                                                          // the fast path ran: its job table is the last run's
+		std::vector<uint64_t> jo((size_t)nf + 1);
+		AL_HIP_CHECK(hipMemcpy(jo.data(), A->job_off.p, ((size_t)nf + 1) * 8, hipMemcpyDeviceToHost));
+		for (int f = 0; f < nf; ++f) {
+			const uint64_t slots = jo[f + 1] - jo[f];
+			if (nu[f] == 0) continue;
+			wave_prep += T.prep_heavy > 0 && slots >= T.prep_heavy; wave_fin += T.fin_heavy > 0 && slots >= T.fin_heavy;
+		}
+		std::vector<ExtJob> jobs((size_t)jo[nf] + 1);
+		if (jo[nf]) AL_HIP_CHECK(hipMemcpy(jobs.data(), A->jobs.p, (size_t)jo[nf] * sizeof(ExtJob), hipMemcpyDeviceToHost));
+		for (uint64_t j = 0; j < jo[nf]; ++j) closed += jobs[j].qlen != 0 && jobs[j].pad0 == 1;
+	}
+	counts[0] = T.n_early; counts[1] = T.n_slow; counts[2] = T.solo_early; counts[3] = T.solo_slow; counts[4] = T.mono_all; counts[5] = T.long_mode; counts[6] = T.tmax;
+	counts[7] = T.prep_heavy; counts[8] = T.fin_heavy; counts[9] = wave_prep; counts[10] = wave_fin; counts[11] = closed; counts[12] = T.n_jobs;
+	counts[13] = cn[7]; counts[14] = cn[8]; counts[15] = cn[9]; counts[16] = (uint64_t)reruns; counts[17] = A->out_total; counts[18] = cn[11];
+	for (int i = 0; i < 10; ++i) counts[19 + i] = T.mono_all ? 0 : c->stat_dp_jobs[i];
 	return 0;
 }
 

@@ -179,6 +179,7 @@ static inline bool al_map_only(int64_t flag) { return (flag & AL_F_OUT_PAF) && !
 static inline int al_tag_kind(int64_t flag) { return al_map_only(flag) ? 0 : (flag & AL_F_OUT_MD) ? 1 : (flag & AL_F_OUT_CS) ? 2 : 0; }   // 0 none, 1 MD, 2 cs (MD wins, format.c:533)
 int al_fetch_align(al_ctx_t *c, int *n_regs, al_reg1_t **regs, int *rep_len);
 void al_align_grow_arena(al_ctx_t *c);
+int al_align_run_to_fit(al_ctx_t *c, int *reruns);   // al_kernels_align.hip: al_run_align_stage, run again with twice the CIGAR arena while it overflows
 
 template <typename T> struct PinnedVec {    // grow-only page-locked host array (fast, asynchronous-capable D2H target)
 	T *p = nullptr; size_t n = 0, cap = 0;

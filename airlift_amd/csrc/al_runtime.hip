@@ -1270,21 +1270,8 @@ extern "C" int al_batch_run(al_ctx_t *c)
 		if (lim && c->n_frag > atoi(lim)) { fprintf(stderr, "[airlift] AL_TEST_NOMEM_ABOVE: pretending %d fragments do not fit\n", c->n_frag); al_nomem_flag() = true; return failed(); }
 	}
 	if (al_run_seed_stages(c)) return failed();
-	for (int attempt = 0; ; ++attempt) {
-		if ((c->P.dbg2 >> 20) & 1) { for (int i = ST_REGS; i < ST_N; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], c->stream)); AL_HIP_CHECK(hipStreamSynchronize(c->stream)); break; }   // (AL_DBG2 bit 20, timing experiments: seed / sort / chain stages only)
-		if (al_run_align_stage(c)) return failed();
-		AL_HIP_CHECK(hipEventRecord(c->ev[ST_COMPACT + 1], c->stream));
-		AL_HIP_CHECK(hipStreamSynchronize(c->stream));
-		unsigned long long ovf = 0;
-		AL_HIP_CHECK(hipMemcpy(&ovf, c->counters.p + 9, 8, hipMemcpyDeviceToHost));
-		if (ovf == 0 || attempt >= 8) break;
-		// long CIGARs (repeat-rich or indel-rich batches) did not fit the arena: the alignment stage only reads the chaining
-		// results, so it is simply run again with twice the arena
-		if (al_env().trace) fprintf(stderr, "[airlift] trace: CIGAR arena overflow (%llu), re-running the alignment stage with twice the arena\n", ovf);
-		al_align_grow_arena(c);
-		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 4, 0, 8 * sizeof(unsigned long long), c->stream));     // [4..11]: stage statistics, error words, arena cursor
-		AL_HIP_CHECK(hipMemsetAsync(c->counters.p + 14, 0, sizeof(unsigned long long), c->stream));
-	}
+	if ((c->P.dbg2 >> 20) & 1) { for (int i = ST_REGS; i < ST_N; ++i) AL_HIP_CHECK(hipEventRecord(c->ev[i + 1], c->stream)); AL_HIP_CHECK(hipStreamSynchronize(c->stream)); }   // (AL_DBG2 bit 20, timing experiments: seed / sort / chain stages only)
+	else if (al_align_run_to_fit(c, nullptr)) return failed();               // (again with twice the CIGAR arena while a batch's long CIGARs overflow it)
 	if (!al_map_only(c->opt.flag) && (al_tag_kind(c->opt.flag) || (c->opt.flag & AL_F_EQX)) && al_run_tags(c)) return failed();
 	for (int i = 0; i < ST_N; ++i) { float ms = 0; if (hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]) != hipSuccess) ms = 0; c->ms_stage[i] = ms; }
 	float tot = 0; (void)hipEventElapsedTime(&tot, c->ev[0], c->ev[ST_N]); c->ms_total = tot;

@@ -313,6 +313,18 @@ int  al_dbg_chain(al_ctx_t *ctx, const uint64_t *anchors_xy, const uint64_t *a_o
 int  al_dbg_regs(al_ctx_t *ctx, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep,
                  uint32_t *reg_cnt, uint32_t *seg_na, uint32_t *regs_n0, uint32_t *frag_hash, uint64_t *counts, uint64_t *sizes);
 int  al_dbg_regs_fetch(al_ctx_t *ctx, void *regs_out, uint64_t n_regs, uint64_t *seg_a_xy, void *dense_out, uint64_t n_dense);
+/* Tap (parity tests): the extension stage -- a mate's hits and anchors to its final records: k_ext_prep(_wave), the DP job classes, k_ext_finish(_wave), the
+ * monolithic k_align / k_align_long with their early, late and solo launches, k_compact -- on caller-supplied chains, through al_run_align_stage itself, run
+ * to its end inside the loop that runs it again with twice the CIGAR arena while the arena overflows (the loop al_batch_run has).  Needs a batch uploaded
+ * with al_batch_upload and NOT run, of the real reads, on an index of the contigs the anchors point into, and a context that is not map-only.  In: as
+ * al_dbg_regs.  Afterwards the context is as al_batch_run leaves it: al_batch_fetch returns the records.  counts[29]: fragments left to the monolithic
+ * kernel after prep and after the DP, whether those two launches were solo, whether the whole batch went through the monolithic kernel (AL_DBG bit 26, long
+ * mode), long mode, the k_align instance's target tile (336, 512, 1024; 0: k_align_long), the job-slot thresholds of the wavefront forms of prep and finish
+ * in effect (0: none), the fragments at or above each, the flanks done in closed form, the job slots, counters[7] (oversize and window bail-outs), log-table
+ * misses, counters[9] of the last run (arena overflow), how often the stage ran again, the records, the arena words used, the DP jobs per class [10].  All of
+ * it is what the host already holds or, read back here only, the job table the last run left: a batch run launches what it launched before.
+ * Returns 0; -2: as al_dbg_regs, or an anchor whose k-mer leaves its contig, or a chain that changes contig or strand or does not ascend (nothing ran). */
+int  al_dbg_align(al_ctx_t *ctx, const uint32_t *nu, const uint64_t *u, const uint32_t *uo, const uint64_t *chained_xy, const uint64_t *a_off, const int32_t *frag_rep, uint64_t *counts);
 /* Tap (parity tests): the seed stage of a pass as a batch run launches it -- sketch, seed lookup, anchor collection, the sorts and the merges of the
  * flagged fragments, on their streams and in their order -- without the chaining.  Needs a batch uploaded with al_batch_upload.  list == NULL: the
  * first pass (mid_occ) on every fragment.  list[n_list], ascending fragment ids: the re-chain pass of those fragments with max_occ, in the place of

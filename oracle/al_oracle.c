@@ -665,6 +665,10 @@ static void select_sub_multi(float pri_ratio, float pri1, float pri2, int max_ga
 	}
 }
 
+/* which branches of the align half ran, counted only while o_frag_align() is on the stack (tests/test_align_oracle_cpu.py: the reach of the directed cases) */
+static __thread int64_t *al_cnt = 0;
+#define AL_CNT(i) do { if (al_cnt) ++al_cnt[i]; } while (0)
+
 static void filter_regs(const oopt_t *opt, int qlen, int *n_regs, oreg_t *regs)
 {   /* ref: hit.c:257-276 */
 	int i, k;
@@ -672,9 +676,10 @@ static void filter_regs(const oopt_t *opt, int qlen, int *n_regs, oreg_t *regs)
 		oreg_t *r = &regs[i]; int flt = 0;
 		if (!r->inv && !r->seg_split && r->cnt < opt->min_cnt) flt = 1;
 		if (r->p) {
-			if (r->mlen < opt->min_chain_score) flt = 1;
-			else if (r->p->dp_max < opt->min_dp_max) flt = 1;
-			else if (r->qs > qlen * opt->max_clip_ratio && qlen - r->qe > qlen * opt->max_clip_ratio) flt = 1;
+			if (r->mlen < opt->min_chain_score) { flt = 1; AL_CNT(O_AC_FLT_MLEN); }
+			else if (r->p->dp_max < opt->min_dp_max) { flt = 1; AL_CNT(O_AC_FLT_DP); if (r->p->dp_max >= opt->min_dp_max - opt->a) AL_CNT(O_AC_FLT_DP_JUST_BELOW); }
+			else if (r->qs > qlen * opt->max_clip_ratio && qlen - r->qe > qlen * opt->max_clip_ratio) { flt = 1; AL_CNT(O_AC_FLT_CLIP); if ((r->qs < qlen - r->qe? r->qs : qlen - r->qe) <= qlen * opt->max_clip_ratio + 1) AL_CNT(O_AC_FLT_CLIP_JUST_ABOVE); }
+			else { int c = r->qs < qlen - r->qe? r->qs : qlen - r->qe; if (r->p->dp_max == opt->min_dp_max) AL_CNT(O_AC_KEPT_AT_MIN_DP); if (c > 0 && c <= qlen * opt->max_clip_ratio && c > qlen * opt->max_clip_ratio - 1) AL_CNT(O_AC_KEPT_CLIP_AT_BOUND); }
 			if (flt) free(r->p);
 		}
 		if (!flt) { if (k < i) regs[k++] = regs[i]; else ++k; }
@@ -1007,6 +1012,7 @@ static int test_zdrop(const oopt_t *opt, const uint8_t *qseq, const uint8_t *tse
 		}
 	}
 #undef UPD
+	if (max_zdrop == opt->zdrop) AL_CNT(O_AC_FALL_EQ_ZDROP); else if (max_zdrop == opt->zdrop + 1) AL_CNT(O_AC_FALL_ZDROP_PLUS1);
 	return max_zdrop > opt->zdrop? 1 : 0;
 }
 
@@ -1116,6 +1122,7 @@ static void append_cigar(oreg_t *r, uint32_t n_cigar, uint32_t *cigar)
 		(void)oc;
 	}
 	p = r->p;
+	if (p->n_cigar > 0) AL_CNT((p->cigar[p->n_cigar-1]&0xf) == (cigar[0]&0xf)? O_AC_CIGAR_MERGED : O_AC_CIGAR_NOT_MERGED);
 	if (p->n_cigar > 0 && (p->cigar[p->n_cigar-1]&0xf) == (cigar[0]&0xf)) {
 		p->cigar[p->n_cigar-1] += cigar[0]>>4<<4;
 		if (n_cigar > 1) memcpy(p->cigar + p->n_cigar, cigar + 1, (n_cigar - 1) * 4);
@@ -1183,13 +1190,19 @@ static void align1(const oopt_t *opt, const oidx_t *mi, int qlen, uint8_t *qseq0
 	re = (int32_t)a[as1+cnt1-1].x + 1;
 	qe = (int32_t)a[as1+cnt1-1].y + 1;
 	assert(cnt1 > 0);
+	AL_CNT(O_AC_ALIGN1);
+	if (cnt1 < r->cnt) AL_CNT(as1 == r->as? O_AC_STRETCH_FIRST : as1 + cnt1 == r->as + r->cnt? O_AC_STRETCH_LAST : O_AC_STRETCH_MID);
 	qs0 = 0, qe0 = qlen;                                                    /* ref: align.c:613-620 */
 	l = qs;
+	AL_CNT(l * opt->a + opt->end_bonus > opt->q? O_AC_WIN_GROWN : O_AC_WIN_PLAIN);
 	l += l * opt->a + opt->end_bonus > opt->q? (l * opt->a + opt->end_bonus - opt->q) / opt->e : 0;
 	rs0 = rs - l > 0? rs - l : 0;
+	if (rs - l <= 0) AL_CNT(rs - l == 0? O_AC_WIN_LEFT_AT0 : O_AC_WIN_LEFT_CUT);
 	l = qlen - qe;
+	AL_CNT(l * opt->a + opt->end_bonus > opt->q? O_AC_WIN_GROWN : O_AC_WIN_PLAIN);
 	l += l * opt->a + opt->end_bonus > opt->q? (l * opt->a + opt->end_bonus - opt->q) / opt->e : 0;
 	re0 = re + l < (int32_t)mi->seq[rid].len? re + l : (int32_t)mi->seq[rid].len;
+	if (re + l >= (int32_t)mi->seq[rid].len) AL_CNT(re + l == (int32_t)mi->seq[rid].len? O_AC_WIN_RIGHT_AT_END : O_AC_WIN_RIGHT_CUT);
 	assert(re0 > rs0);
 	tseq = (uint8_t*)malloc(re0 - rs0 + 16);
 	if (st) st->n_regs_aln++, st->n_refbases += re0 - rs0;
@@ -1200,6 +1213,8 @@ static void align1(const oopt_t *opt, const oidx_t *mi, int qlen, uint8_t *qseq0
 		seq_rev(qs - qs0, qseq); seq_rev(rs - rs0, tseq);
 		align_pair(opt, qs - qs0, qseq, rs - rs0, tseq, mat, bw, opt->end_bonus, r->split_inv? opt->zdrop_inv : opt->zdrop, EZ_EXTZ_ONLY|EZ_RIGHT|EZ_REV_CIGAR, ez, st);
 		if (ez->n_cigar > 0) { append_cigar(r, ez->n_cigar, ez->cigar); r->p->dp_score += ez->max; }
+		AL_CNT(O_AC_LEFT); if (ez->zdropped) AL_CNT(O_AC_FLANK_ZDROP); if (ez->reach_end) AL_CNT(O_AC_REACH_END); else AL_CNT(O_AC_CLIPPED); if (ez->n_cigar == 0) AL_CNT(O_AC_FLANK_EMPTY);
+		if (ez->mqe != KSW_NEG_INF && !ez->zdropped) { if (ez->mqe + opt->end_bonus == (int)ez->max) AL_CNT(O_AC_TIE_EQ); else if (ez->mqe + opt->end_bonus > (int)ez->max && ez->mqe + opt->end_bonus <= (int)ez->max + opt->a) AL_CNT(O_AC_TIE_ABOVE); }
 		rs1 = rs - (ez->reach_end? ez->mqe_t + 1 : ez->max_t + 1);
 		qs1 = qs - (ez->reach_end? qs - qs0 : ez->max_q + 1);
 		seq_rev(qs - qs0, qseq);
@@ -1221,8 +1236,10 @@ static void align1(const oopt_t *opt, const oidx_t *mi, int qlen, uint8_t *qseq0
 			else ez->score += qseq[j] == tseq[j]? opt->a : -opt->b;
 		}
 		ez->cigar = push_cigar(&ez->n_cigar, &ez->m_cigar, ez->cigar, 0, qe - qs);
-		if ((zdrop_code = test_zdrop(opt, qseq, tseq, ez->n_cigar, ez->cigar, mat)) != 0)
+		if ((zdrop_code = test_zdrop(opt, qseq, tseq, ez->n_cigar, ez->cigar, mat)) != 0) {
 			align_pair(opt, qe - qs, qseq, re - rs, tseq, mat, bw, -1, opt->zdrop, 0, ez, st);
+			AL_CNT(O_AC_CORE_ZDROP); if (!ez->zdropped) AL_CNT(O_AC_CORE_SECOND_PASS_KEPT);
+		}
 		if (ez->n_cigar > 0) append_cigar(r, ez->n_cigar, ez->cigar);
 		if (ez->zdropped) {
 			for (j = i - 1; j >= 0; --j) if ((int32_t)a[as1 + j].x <= rs + ez->max_t) break;
@@ -1231,7 +1248,8 @@ static void align1(const oopt_t *opt, const oidx_t *mi, int qlen, uint8_t *qseq0
 			r->p->dp_score += ez->max;
 			re1 = rs + (ez->max_t + 1);
 			qe1 = qs + (ez->max_q + 1);
-			if (cnt1 - (j + 1) >= opt->min_cnt) split_reg(r, r2, as1 + j + 1 - r->as, qlen, a);
+			if (cnt1 - (j + 1) >= opt->min_cnt) { split_reg(r, r2, as1 + j + 1 - r->as, qlen, a); AL_CNT(O_AC_SPLIT); }
+			else AL_CNT(O_AC_DROP_NO_SPLIT);
 			break;
 		} else r->p->dp_score += ez->score;
 		rs = re, qs = qe;
@@ -1242,6 +1260,8 @@ static void align1(const oopt_t *opt, const oidx_t *mi, int qlen, uint8_t *qseq0
 		idx_getseq(mi, rid, re, re0, tseq);
 		align_pair(opt, qe0 - qe, qseq, re0 - re, tseq, mat, bw, opt->end_bonus, opt->zdrop, EZ_EXTZ_ONLY, ez, st);
 		if (ez->n_cigar > 0) { append_cigar(r, ez->n_cigar, ez->cigar); r->p->dp_score += ez->max; }
+		AL_CNT(O_AC_RIGHT); if (ez->zdropped) AL_CNT(O_AC_FLANK_ZDROP); if (ez->reach_end) AL_CNT(O_AC_REACH_END); else AL_CNT(O_AC_CLIPPED); if (ez->n_cigar == 0) AL_CNT(O_AC_FLANK_EMPTY);
+		if (ez->mqe != KSW_NEG_INF && !ez->zdropped) { if (ez->mqe + opt->end_bonus == (int)ez->max) AL_CNT(O_AC_TIE_EQ); else if (ez->mqe + opt->end_bonus > (int)ez->max && ez->mqe + opt->end_bonus <= (int)ez->max + opt->a) AL_CNT(O_AC_TIE_ABOVE); }
 		re1 = re + (ez->reach_end? ez->mqe_t + 1 : ez->max_t + 1);
 		qe1 = qe + (ez->reach_end? qe0 - qe : ez->max_q + 1);
 	}
@@ -1431,7 +1451,9 @@ static oreg_t *align_regs(const oopt_t *opt, const oidx_t *mi, int qlen, const c
 {   /* ref: map.c:260-270 */
 	regs = align_skeleton(opt, mi, qlen, seq, n_regs, regs, a, st);
 	set_parent(opt->mask_level, *n_regs, regs, opt->a * 2 + opt->b);
+	{ int n0 = *n_regs;
 	select_sub(opt->pri_ratio, mi->k*2, opt->best_n, n_regs, regs);
+	if (al_cnt) al_cnt[O_AC_SELECT_DROPPED] += n0 - *n_regs; }
 	set_sam_pri(*n_regs, regs);
 	return regs;
 }
@@ -1498,6 +1520,92 @@ int o_frag_hits(int n_u, const uint64_t *u_in, const uint64_t *a_xy, int64_t n_a
 	}
 	free(u); free(a);
 	return 0;
+}
+
+/* ---------------------------------------------------------------- stage-level entry: chains in, final records out (ref: map.c:379-405 with align_regs)
+ * The align half of o_map_frag on the caller's chains.  The extension-stage tests compare this, fragment by fragment, with oracle/alignref_shim.c's
+ * alignref_frag() over the reference's own functions; arguments, results and the layout of a record (O_ALN_NF words) are the shim's. */
+#include "frag_check.h"
+#define O_ALN_NF 32
+static void aln_put(int32_t *o, const oreg_t *r)
+{
+	o[0] = r->id; o[1] = r->parent; o[2] = r->score; o[3] = r->score0; o[4] = r->cnt; o[5] = r->rid; o[6] = r->qs; o[7] = r->qe; o[8] = r->rs; o[9] = r->re;
+	o[10] = r->subsc; o[11] = r->n_sub; o[12] = (int32_t)r->hash; o[13] = r->mlen; o[14] = r->blen; o[15] = r->mapq; o[16] = r->rev; o[17] = r->split; o[18] = r->inv;
+	o[19] = r->split_inv; o[20] = r->proper_frag; o[21] = r->pe_thru; o[22] = r->sam_pri; o[23] = r->seg_split; o[24] = r->seg_id; o[25] = r->p != 0;
+	o[26] = r->p? r->p->dp_score : 0; o[27] = r->p? r->p->dp_max : 0; o[28] = r->p? r->p->dp_max2 : 0; o[29] = r->p? (int32_t)r->p->n_ambi : 0;
+	o[30] = r->p? (int32_t)r->p->trans_strand : 0; o[31] = r->p? (int32_t)r->p->n_cigar : 0;
+}
+
+static __thread int64_t *al_cnt_to = 0;
+void o_align_count(int64_t *counters) { al_cnt_to = counters; }   /* O_AC_N words this thread's later o_frag_align() calls add to; NULL: none */
+void *o_align_idx(int w, int k, int n, const char **seqs, const char **names) { return oidx_build(k, w, n, names, seqs); }
+void o_align_idx_free(void *mi) { if (mi) oidx_destroy((oidx_t*)mi); }
+
+int o_frag_align(const void *mi_, const int32_t *io, const float *fo, int n_u, const uint64_t *u_in, const uint64_t *a_xy, int64_t n_a, uint32_t hash,
+                 int n_segs, const int *qlens, const char **seqs, int rep_len, int max_hits, int max_cig, int32_t *n_hits, int32_t *out, int32_t *n_cigw, uint32_t *cig)
+{
+	const oidx_t *mi = (const oidx_t*)mi_; oopt_t opt;
+	int i, s, rc, qlen_sum = 0, n_regs0 = n_u, n_regs[2] = {0, 0}, max_gap_ref; int64_t j; uint32_t *lens;
+	uint64_t *u; o128_t *a; oreg_t *regs0, *regs[2] = {0, 0};
+	lens = (uint32_t*)malloc((mi->n_seq? mi->n_seq : 1) * 4);
+	for (i = 0; i < (int)mi->n_seq; ++i) lens[i] = mi->seq[i].len;
+	rc = frag_check(n_u, u_in, a_xy, n_a, n_segs, qlens, mi->n_seq, lens);
+	free(lens);
+	if (rc) return rc;
+	for (s = 0; s < n_segs; ++s) { if (!seqs[s] || (int)strlen(seqs[s]) != qlens[s]) return -20; qlen_sum += qlens[s]; }
+	oopt_sr(&opt);
+	if (mi->k != io[0]) return -20;
+	opt.bw = io[1]; opt.max_gap = io[2]; opt.max_gap_ref = io[3]; opt.max_frag_len = io[4]; opt.min_cnt = io[5]; opt.min_chain_score = io[6]; opt.best_n = io[7];
+	opt.a = io[8]; opt.b = io[9]; opt.q = io[10]; opt.e = io[11]; opt.q2 = io[12]; opt.e2 = io[13]; opt.sc_ambi = io[14]; opt.zdrop = io[15]; opt.zdrop_inv = io[16];
+	opt.end_bonus = io[17]; opt.min_dp_max = io[18]; opt.pe_ori = io[19]; opt.pe_bonus = io[20];
+	opt.mask_level = fo[0]; opt.pri_ratio = fo[1]; opt.max_clip_ratio = fo[2];
+	if (opt.max_gap_ref > 0) max_gap_ref = opt.max_gap_ref;
+	else if (opt.max_frag_len > 0) { max_gap_ref = opt.max_frag_len - qlen_sum; if (max_gap_ref < opt.max_gap) max_gap_ref = opt.max_gap; }
+	else max_gap_ref = opt.max_gap;
+	u = (uint64_t*)malloc((n_u > 0? n_u : 1) * 8); a = (o128_t*)malloc((n_a > 0? n_a : 1) * 16);
+	for (i = 0; i < n_u; ++i) u[i] = u_in[i];
+	for (j = 0; j < n_a; ++j) a[j].x = a_xy[2 * j], a[j].y = a_xy[2 * j + 1];
+	n_hits[0] = n_hits[1] = 0; n_cigw[0] = n_cigw[1] = 0;
+	al_cnt = al_cnt_to;
+	regs0 = gen_regs(hash, qlen_sum, n_u, u, a);
+	set_parent(opt.mask_level, n_regs0, regs0, opt.a * 2 + opt.b);
+	if (n_segs <= 1) select_sub(opt.pri_ratio, mi->k*2, opt.best_n, &n_regs0, regs0);
+	else select_sub_multi(opt.pri_ratio, 0.2f, 0.7f, max_gap_ref, mi->k*2, opt.best_n, n_segs, qlens, &n_regs0, regs0);
+	if (n_segs == 1) {
+		regs0 = align_regs(&opt, mi, qlens[0], seqs[0], &n_regs0, regs0, a, 0);
+		set_mapq(n_regs0, regs0, opt.min_chain_score, opt.a, rep_len);
+		n_regs[0] = n_regs0, regs[0] = regs0;
+	} else {
+		oseg_t *seg = seg_gen(hash, n_segs, qlens, n_regs0, regs0, n_regs, regs, a);
+		free(regs0);
+		for (s = 0; s < n_segs; ++s) {
+			set_parent(opt.mask_level, n_regs[s], regs[s], opt.a * 2 + opt.b);
+			regs[s] = align_regs(&opt, mi, qlens[s], seqs[s], &n_regs[s], regs[s], seg[s].a, 0);
+			set_mapq(n_regs[s], regs[s], opt.min_chain_score, opt.a, rep_len);
+		}
+		for (s = 0; s < n_segs; ++s) free(seg[s].u), free(seg[s].a);
+		free(seg);
+		if (opt.pe_ori >= 0) pair_regs(max_gap_ref, opt.pe_bonus, opt.a * 2 + opt.b, opt.a, qlens, n_regs, regs);
+	}
+	al_cnt = 0;
+	rc = 0;
+	for (s = 0; s < n_segs; ++s) {
+		int k = 0;
+		if (n_regs[s] > max_hits) rc = -21;
+		for (i = 0; i < n_regs[s] && !rc; ++i) {
+			const oreg_t *r = &regs[s][i];
+			aln_put(out + ((size_t)s * max_hits + i) * O_ALN_NF, r);
+			if (r->p) {
+				if (k + (int)r->p->n_cigar > max_cig) { rc = -22; break; }
+				memcpy(cig + (size_t)s * max_cig + k, r->p->cigar, (size_t)r->p->n_cigar * 4); k += r->p->n_cigar;
+			}
+		}
+		n_hits[s] = n_regs[s]; n_cigw[s] = k;
+		for (i = 0; i < n_regs[s]; ++i) free(regs[s][i].p);
+		free(regs[s]);
+	}
+	free(u); free(a);
+	return rc;
 }
 
 void o_map_frag(const oidx_t *mi, const oopt_t *opt, int n_segs, const int *qlens, const char **seqs,

@@ -110,6 +110,17 @@ o128_t *o_collect_seeds(const oidx_t *mi, int max_occ, const o128_t *mv, size_t 
 int     o_frag_hits(int n_u, const uint64_t *u, const uint64_t *a_xy, int64_t n_a, uint32_t hash, int n_segs, const int *qlens, int rep_len,
                     float mask_level, float pri_ratio, int best_n, int min_diff, int max_gap_ref, int sub_diff, int min_chain_sc, int match_sc,
                     int32_t *pre, int32_t *nA, int32_t *A, int32_t *nB, int32_t *B, int32_t *C, uint64_t *anch, int64_t *n_anch);
+/* a fragment's chains to its final records (map.c:379-405 with align_regs): see al_oracle.c and oracle/alignref_shim.c, whose arguments these are;
+ * o_align_count(): O_AC_N words the calling thread's later o_frag_align() calls add to (NULL: none) -- which branches of align1 ran */
+enum { O_AC_ALIGN1, O_AC_STRETCH_FIRST, O_AC_STRETCH_MID, O_AC_STRETCH_LAST, O_AC_WIN_GROWN, O_AC_WIN_PLAIN, O_AC_WIN_LEFT_AT0, O_AC_WIN_LEFT_CUT, O_AC_WIN_RIGHT_AT_END,
+       O_AC_WIN_RIGHT_CUT, O_AC_LEFT, O_AC_RIGHT, O_AC_FLANK_ZDROP, O_AC_REACH_END, O_AC_CLIPPED, O_AC_FLANK_EMPTY, O_AC_CORE_ZDROP, O_AC_CORE_SECOND_PASS_KEPT, O_AC_SPLIT,
+       O_AC_DROP_NO_SPLIT, O_AC_FLT_MLEN, O_AC_FLT_DP, O_AC_FLT_DP_JUST_BELOW, O_AC_FLT_CLIP, O_AC_FLT_CLIP_JUST_ABOVE, O_AC_KEPT_AT_MIN_DP, O_AC_KEPT_CLIP_AT_BOUND, O_AC_FALL_EQ_ZDROP,
+       O_AC_FALL_ZDROP_PLUS1, O_AC_CIGAR_MERGED, O_AC_CIGAR_NOT_MERGED, O_AC_TIE_EQ, O_AC_TIE_ABOVE, O_AC_SELECT_DROPPED, O_AC_N };
+void   *o_align_idx(int w, int k, int n, const char **seqs, const char **names);
+void    o_align_idx_free(void *mi);
+int     o_frag_align(const void *mi, const int32_t *io, const float *fo, int n_u, const uint64_t *u, const uint64_t *a_xy, int64_t n_a, uint32_t hash,
+                     int n_segs, const int *qlens, const char **seqs, int rep_len, int max_hits, int max_cig, int32_t *n_hits, int32_t *out, int32_t *n_cigw, uint32_t *cig);
+void    o_align_count(int64_t *counters);
 void    o_radix_sort_128x(o128_t *beg, o128_t *end);
 void    o_radix_sort_64(uint64_t *beg, uint64_t *end);
 
