@@ -95,6 +95,28 @@ LIFT_GPU_DEFLATE = 2          # AL_LIFT_GPU_DEFLATE
 LIFT_SORTED = 4               # AL_LIFT_SORTED: the lifted BAM in coordinate order
 
 
+class MergeStat(C.Structure):
+    """AlMergeStat of al_merge_bams."""
+    _fields_ = [("n_in", C.c_uint64), ("records", C.c_uint64), ("rounds", C.c_uint64), ("refills", C.c_uint64), ("bytes_in", C.c_uint64), ("held", C.c_uint64),
+                ("records_in", C.c_uint64 * 8),
+                ("read_s", C.c_double), ("up_s", C.c_double), ("inflate_s", C.c_double), ("walk_s", C.c_double), ("key_s", C.c_double), ("merge_s", C.c_double), ("gather_s", C.c_double),
+                ("down_s", C.c_double), ("deflate_s", C.c_double), ("wall_s", C.c_double), ("on_device", C.c_int)]
+
+
+MERGE_HOST = 1                # AL_MERGE_HOST of include/airlift.h
+MERGE_GPU_DEFLATE = 2         # AL_MERGE_GPU_DEFLATE
+
+
+def merge_bams(bams_in, bam_out, flags=0, device=-1, n_threads=3, level=5, piece_bytes=0):
+    """al_merge_bams: the coordinate-sorted BAMs `bams_in` merged into `bam_out`.  Returns the MergeStat."""
+    st = MergeStat()
+    arr = (C.c_char_p * len(bams_in))(*[os.fsencode(b) for b in bams_in])
+    rc = load().al_merge_bams(arr, len(bams_in), os.fsencode(bam_out), flags, device, n_threads, level, piece_bytes, C.byref(st))
+    if rc != 0:
+        raise AirliftError("al_merge_bams failed: %d" % rc)
+    return st
+
+
 def lift_bam(bam_in, chain, bam_out, bed_out, flags=0, device=-1, n_threads=3, level=5, piece_bytes=0):
     """al_lift_bam: the constant-region reads of `bam_in` moved across `chain` into `bam_out`, the reads that do not lift as rows of `bed_out`.  Returns the LiftStat."""
     st = LiftStat()
@@ -212,6 +234,12 @@ def load():
         L.al_dbg_lift_sorted.argtypes = [ci, vp, C.c_size_t, cs, u32p, u32p, C.c_size_t, u64p, vp, C.c_size_t, szp, vp, C.c_size_t, szp, u32p, u64p, C.c_uint, szp]; L.al_dbg_lift_sorted.restype = ci
     L.al_dbg_bam_de_bits.argtypes = [C.c_uint64]; L.al_dbg_bam_de_bits.restype = C.c_uint32
     L.al_dbg_ksw.argtypes = [vp, ci, vp, C.c_size_t, vp, vp, vp, ci]; L.al_dbg_ksw.restype = ci
+    if hasattr(L, "al_merge_bams"):   # (merge: coordinate-sorted BAMs merged into one, and its test taps)
+        cs, ci, vp, u32p, u64p, szp = C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.al_merge_bams.argtypes = [C.POINTER(C.c_char_p), ci, cs, C.c_uint, ci, ci, ci, C.c_size_t, C.POINTER(MergeStat)]; L.al_merge_bams.restype = ci
+        L.al_dbg_merge_host.argtypes = [C.POINTER(C.c_char_p), szp, ci, C.c_size_t, u32p, u64p, C.c_size_t, szp, vp, C.c_size_t, szp, u64p]; L.al_dbg_merge_host.restype = ci
+        L.al_dbg_merge.argtypes = [ci, C.POINTER(C.c_char_p), szp, ci, C.c_size_t, u32p, u64p, C.c_size_t, szp, vp, C.c_size_t, szp, u64p, szp]; L.al_dbg_merge.restype = ci
+        L.al_dbg_merge_tile.argtypes = []; L.al_dbg_merge_tile.restype = C.c_uint32
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci
     if hasattr(L, "al_dbg_chain"):

@@ -247,6 +247,14 @@ static inline int al_lift_bind(AlLiftChain &C, const AlLiftHeader &H, std::strin
 	if (C.ref_slot.empty()) C.ref_slot.reserve(1);
 	return 0;
 }
+// an @HD line with its SO: value set: unsorted, or (sorted) coordinate, added when the line names no order
+static inline std::string al_lift_hd_line(const std::string &l, bool sorted)
+{
+	std::string m; size_t p = 0;
+	while (p <= l.size()) { size_t q = l.find('\t', p); if (q == std::string::npos) q = l.size(); std::string f = l.substr(p, q - p); if (f.compare(0, 3, "SO:") == 0) f = sorted ? "SO:coordinate" : "SO:unsorted"; if (p) m += '\t'; m += f; p = q + 1; }
+	if (sorted && m.find("\tSO:") == std::string::npos) m += "\tSO:coordinate";   // (an @HD line that names no order)
+	return m;
+}
 // The header of the lifted BAM: @SQ lines replaced by one per q-slot where the first old @SQ stood (without any: after a leading @HD, else first), an SO:
 // value of @HD becomes unsorted, other lines are kept; the binary reference list is the q-slots.  sorted (lift --sorted): the SO: value becomes coordinate, and
 // a text without an @HD line gets "@HD\tVN:1.6\tSO:coordinate" as its first line (the line al_bam_header writes for --sorted-bam), an @HD line without SO: gets one.
@@ -269,10 +277,7 @@ static inline void al_lift_header_write(const AlLiftHeader &H, const AlLiftChain
 		std::string l = lines[i];
 		if (is(l, "@SQ")) { if (!put) { o += sq; put = true; } continue; }
 		if (is(l, "@HD")) {
-			std::string m; size_t p = 0;
-			while (p <= l.size()) { size_t q = l.find('\t', p); if (q == std::string::npos) q = l.size(); std::string f = l.substr(p, q - p); if (f.compare(0, 3, "SO:") == 0) f = sorted ? "SO:coordinate" : "SO:unsorted"; if (p) m += '\t'; m += f; p = q + 1; }
-			if (sorted && m.find("\tSO:") == std::string::npos) m += "\tSO:coordinate";   // (an @HD line that names no order)
-			l = m;
+			l = al_lift_hd_line(l, sorted);
 		}
 		o += l; o += '\n';
 		if (!put && !any_sq && i == 0) { o += sq; put = true; }

@@ -111,6 +111,42 @@ template <class Emit> static inline int al_lift_stream(AlLiftBackend &B, AlLiftS
 	}
 }
 
+// The BAM header of a BGZF file: leading members inflated on the host until it is complete.  *file_off / *out_off: file and stream offset of the member
+// that holds the first record's first byte, *start that byte's offset in the member.  0; -1 with a message printed.  tag: the command the messages name
+// (`merge` reads its inputs' headers with it too).
+static inline int lift_read_header(int fd, const char *fn, AlLiftHeader &H, uint64_t *file_off, uint64_t *out_off, uint64_t *start, const char *tag = "lift")
+{
+	std::vector<uint8_t> in, out; std::vector<uint64_t> m_file, m_out; uint64_t fpos = 0, ipos = 0; bool eof = false;
+	for (;;) {
+		uint32_t msize = 0, hd = 0; int r = -1;
+		if (in.size() - ipos >= 18) r = al_inf_parse_header(in.data() + ipos, in.size() - ipos, &msize, &hd);
+		if (r > 0 || (eof && fpos == 0 && in.size() < 28)) { fprintf(stderr, "[ERROR] airlift: %s: '%s' is not a BGZF file (lift reads a BAM by its BGZF members; there is no one-stream reader here)\n", tag, fn); return -1; }
+		if (r < 0 || msize > in.size() - ipos) {
+			if (eof) { fprintf(stderr, "ERROR: '%s': the file ends inside the BAM header\n", fn); return -2; }
+			const size_t at = in.size(); in.resize(at + (1 << 16));
+			const ssize_t g = pread(fd, in.data() + at, 1 << 16, (off_t)fpos);
+			if (g < 0) { fprintf(stderr, "[ERROR] airlift: %s: reading '%s' failed\n", tag, fn); return -1; }
+			in.resize(at + (size_t)g); fpos += (uint64_t)g; if (g == 0) eof = true;
+			continue;
+		}
+		const uint32_t isize = al_inf_le32(in.data() + ipos + msize - 4);
+		if (isize > AL_INF_MAX_ISIZE) { fprintf(stderr, "[ERROR] airlift: %s: '%s': no BGZF member at file offset %llu\n", tag, fn, (unsigned long long)ipos); return -1; }
+		const size_t at = out.size(); out.resize(at + isize);
+		const int stt = al_inflate_member_host(in.data() + ipos, msize, out.data() + at);
+		if (stt) { fprintf(stderr, "[ERROR] airlift: %s: '%s': BGZF member at file offset %llu: status %d (%s)\n", tag, fn, (unsigned long long)ipos, stt, al_inf_strerror(stt)); return -1; }
+		m_file.push_back(ipos); m_out.push_back(at); ipos += msize;
+		size_t used = 0; std::string err;
+		const int hr = al_lift_header_parse(out.data(), out.size(), H, &used, err);
+		if (hr < 0) { fprintf(stderr, "ERROR: '%s': %s\n", fn, err.c_str()); return -2; }
+		if (hr > 0) continue;
+		size_t m = m_out.size();
+		while (m > 0 && m_out[m - 1] > used) --m;                         // the last member that starts at or before the first record
+		if (used == out.size()) { *file_off = ipos; *out_off = out.size(); *start = 0; }
+		else { *file_off = m_file[m - 1]; *out_off = m_out[m - 1]; *start = used - m_out[m - 1]; }
+		return 0;
+	}
+}
+
 // ---- the host backend: the twin (al_dev_lift.h) behind the same calls -----------------------------------------------------------------------------------------
 struct AlLiftHostBackend : AlLiftBackend {
 	AlLiftTab T; int n_threads; std::vector<uint8_t> txt[2], packed[2], arena[2]; std::vector<uint32_t> rec_off[2], verdict[2], keep_len[2], arena_len[2];

@@ -33,73 +33,10 @@
 #include "al_dev_inflate.h"
 #include "al_bam.h"
 #include "al_lift.h"
+#include "al_dev_walk.h"
 #include "al_run_store.h"
 #include "al_prim.h"
 #include "../../include/airlift.h"
-
-#define AL_LIFT_W 8192u                       // bytes of a window (a power of two, a multiple of 64 x 16)
-#define AL_LIFT_V (AL_LIFT_W / 16 / 64)       // 16-byte loads per lane and window
-
-// window w of the text into a lane's registers; lim: the bytes of the text's buffer that may be read.  A window that lies whole below lim -- every window
-// of a text whose buffer has the room begin() asks for -- is loaded without a branch per load, so that the loads stay in flight while the lanes go on.
-typedef uint32_t al_u32x4 __attribute__((ext_vector_type(4)));
-struct AlWalkRegs { al_u32x4 v[AL_LIFT_V]; };
-__device__ __forceinline__ void walk_load(AlWalkRegs &R, const uint8_t *__restrict__ t, uint32_t w, uint32_t lim, uint32_t l)
-{
-	const al_u32x4 zero = {0, 0, 0, 0};
-	if ((uint64_t)(w + 1) * AL_LIFT_W <= lim) {
-		_Pragma("unroll")
-		for (uint32_t j = 0; j < AL_LIFT_V; ++j) R.v[j] = *(const al_u32x4 *)(t + (size_t)w * AL_LIFT_W + (l + 64 * j) * 16); }
-	else {
-		_Pragma("unroll")
-		for (uint32_t j = 0; j < AL_LIFT_V; ++j) { const uint64_t off = (uint64_t)w * AL_LIFT_W + (l + 64 * j) * 16; R.v[j] = off + 16 <= lim ? *(const al_u32x4 *)(t + off) : zero; }
-	}
-}
-// The hop is uniform: every lane reads the same two LDS words (a broadcast), the size field is taken out of them with one funnel shift and made scalar, so
-// the loop's compares and branches are scalar; lane i & 63 keeps the offset of record i and the 64 offsets leave with one store.
-__global__ void __launch_bounds__(64)
-k_bam_walk(const uint8_t *__restrict__ t, uint32_t n, uint32_t lim, uint32_t start, uint32_t *__restrict__ rec_off, uint32_t *__restrict__ res)
-{
-	__shared__ al_u32x4 ring4[2 * AL_LIFT_W / 16];
-	const uint32_t *ring32 = (const uint32_t *)ring4;
-	const uint32_t l = threadIdx.x;
-	uint32_t p = start, n_rec = 0, mine = 0, state = p + 4 > n ? 1u : 0u;   // state 1: the walk has ended; 2: at a block_size out of range
-	uint32_t k = p / AL_LIFT_W;
-	AlWalkRegs R = {};
-	if (state == 0) {
-		walk_load(R, t, k, lim, l);
-		_Pragma("unroll")
-		for (uint32_t j = 0; j < AL_LIFT_V; ++j) ring4[(k & 1) * (AL_LIFT_W / 16) + l + 64 * j] = R.v[j];
-	}
-	__syncthreads();
-	while (state == 0) {
-		const bool pre = (uint64_t)(k + 1) * AL_LIFT_W < n;
-		if (pre) walk_load(R, t, k + 1, lim, l);
-		const uint32_t wend = pre ? (k + 1) * AL_LIFT_W : n;
-		while (p + 4 <= wend) {
-			const uint32_t a = (p & (2 * AL_LIFT_W - 1)) >> 2;
-			const uint32_t lo = ring32[a], hi = ring32[(a + 1) & (2 * AL_LIFT_W / 4 - 1)];
-			const uint32_t bs = __builtin_amdgcn_readfirstlane(__funnelshift_r(lo, hi, (p & 3) * 8));
-			if (bs < 32 || bs > AL_LIFT_MAX_BS) { state = 2; break; }
-			if (p + 4 + bs > n) { state = 1; break; }
-			if (l == (n_rec & 63)) mine = p;
-			++n_rec;
-			if ((n_rec & 63) == 0) rec_off[n_rec - 64 + l] = mine;
-			p += 4 + bs;
-		}
-		if (state == 0 && p + 4 > n) state = 1;
-		if (state) break;
-		const uint32_t k2 = p / AL_LIFT_W;
-		__syncthreads();
-		if (k2 <= k + 1) ++k;                                              // (p + 4 lies beyond window k and inside the text: window k + 1 exists and is on its way)
-		else { k = k2; walk_load(R, t, k, lim, l); }                       // a record that ends beyond the next window: skipped, the window of p loaded afresh
-		_Pragma("unroll")
-		for (uint32_t j = 0; j < AL_LIFT_V; ++j) ring4[(k & 1) * (AL_LIFT_W / 16) + l + 64 * j] = R.v[j];
-		__syncthreads();
-	}
-	if (l < (n_rec & 63)) rec_off[(n_rec & ~63u) + l] = mine;
-	if (l == 0) { res[0] = n_rec; res[1] = p; res[2] = state == 2 ? 1u : 0u; }
-}
 
 __global__ void __launch_bounds__(256)
 k_lift(uint8_t *__restrict__ t, const uint32_t *__restrict__ rec_off, uint32_t n_rec, AlLiftTab T, uint32_t *__restrict__ verdict, uint32_t *__restrict__ keep_len, uint32_t *__restrict__ arena_len,
@@ -419,41 +356,6 @@ struct AlLiftDevBackend : AlLiftBackend {
 	}
 	void stat(AlLiftRun &st) override { st.up_s += up_s; st.inflate_s += S[0].bz.kernel_s + S[1].bz.kernel_s; st.walk_s += walk_s; st.lift_s += lift_s; st.down_s += down_s; st.sort_s += sort_s; st.sgather_s += sgather_s; }
 };
-
-// The BAM header of a BGZF file: leading members inflated on the host until it is complete.  *file_off / *out_off: file and stream offset of the member
-// that holds the first record's first byte, *start that byte's offset in the member.  0; -1 with a message printed.
-int lift_read_header(int fd, const char *fn, AlLiftHeader &H, uint64_t *file_off, uint64_t *out_off, uint64_t *start)
-{
-	std::vector<uint8_t> in, out; std::vector<uint64_t> m_file, m_out; uint64_t fpos = 0, ipos = 0; bool eof = false;
-	for (;;) {
-		uint32_t msize = 0, hd = 0; int r = -1;
-		if (in.size() - ipos >= 18) r = al_inf_parse_header(in.data() + ipos, in.size() - ipos, &msize, &hd);
-		if (r > 0 || (eof && fpos == 0 && in.size() < 28)) { fprintf(stderr, "[ERROR] airlift: lift: '%s' is not a BGZF file (lift reads a BAM by its BGZF members; there is no one-stream reader here)\n", fn); return -1; }
-		if (r < 0 || msize > in.size() - ipos) {
-			if (eof) { fprintf(stderr, "ERROR: '%s': the file ends inside the BAM header\n", fn); return -2; }
-			const size_t at = in.size(); in.resize(at + (1 << 16));
-			const ssize_t g = pread(fd, in.data() + at, 1 << 16, (off_t)fpos);
-			if (g < 0) { fprintf(stderr, "[ERROR] airlift: lift: reading '%s' failed\n", fn); return -1; }
-			in.resize(at + (size_t)g); fpos += (uint64_t)g; if (g == 0) eof = true;
-			continue;
-		}
-		const uint32_t isize = al_inf_le32(in.data() + ipos + msize - 4);
-		if (isize > AL_INF_MAX_ISIZE) { fprintf(stderr, "[ERROR] airlift: lift: '%s': no BGZF member at file offset %llu\n", fn, (unsigned long long)ipos); return -1; }
-		const size_t at = out.size(); out.resize(at + isize);
-		const int stt = al_inflate_member_host(in.data() + ipos, msize, out.data() + at);
-		if (stt) { fprintf(stderr, "[ERROR] airlift: lift: '%s': BGZF member at file offset %llu: status %d (%s)\n", fn, (unsigned long long)ipos, stt, al_inf_strerror(stt)); return -1; }
-		m_file.push_back(ipos); m_out.push_back(at); ipos += msize;
-		size_t used = 0; std::string err;
-		const int hr = al_lift_header_parse(out.data(), out.size(), H, &used, err);
-		if (hr < 0) { fprintf(stderr, "ERROR: '%s': %s\n", fn, err.c_str()); return -2; }
-		if (hr > 0) continue;
-		size_t m = m_out.size();
-		while (m > 0 && m_out[m - 1] > used) --m;                         // the last member that starts at or before the first record
-		if (used == out.size()) { *file_off = ipos; *out_off = out.size(); *start = 0; }
-		else { *file_off = m_file[m - 1]; *out_off = m_out[m - 1]; *start = used - m_out[m - 1]; }
-		return 0;
-	}
-}
 
 } // namespace
 

@@ -24,6 +24,8 @@
 //                                                                   run/1_build_exact_chain_file.py: the exact chain file those scripts assume, verified or built on the GPU
 //          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
 //                                                                   run_pipeline.sh:92-95 (FastRemap): the constant-region reads moved across the chain file on the GPU
+//          airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN1.bam IN2.bam [IN3.bam ...]
+//                 run_pipeline.sh:116 and :119 (samtools merge): 2 to 8 coordinate-sorted BAMs merged into one on the GPU
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -118,6 +120,9 @@ static int usage()
 	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
 	                "       (the reads in constant regions moved across the chain file on the GPU; the reads that do not lift leave as the rows extract-reads writes;\n"
 	                "       --sorted: OUT.bam in coordinate order, what samtools sort makes of it)\n"
+	                "merge: airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
+	                "       (2 to 8 coordinate-sorted BGZF BAMs merged into one on the GPU, what samtools merge does at the end of run_pipeline.sh; equal positions: the\n"
+	                "       earlier input first)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -179,6 +184,35 @@ int main(int argc, char **argv)
 		}
 		if ((lf & AL_LIFT_HOST) && (lf & AL_LIFT_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] lift: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }
 		const int rc2 = al_lift_bam(p[0], c_fn, o_fn, b_fn, lf, dev, nt, level, piece, nullptr) == 0 ? 0 : 1;
+		fflush(stderr);
+		_exit(rc2);
+	}
+	if (!strcmp(argv[1], "merge")) {               // run_pipeline.sh:116 and :119 (samtools merge -l5 -f OUT.bam A.bam B.bam): coordinate-sorted BAMs merged into one
+		int dev = -1, nt = 3, level = 5; unsigned mf = 0; size_t piece = 0; const char *o_fn = nullptr; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "-o") && j + 1 < argc) o_fn = argv[++j];
+			else if (!strcmp(argv[j], "--host")) mf |= AL_MERGE_HOST;
+			else if (!strcmp(argv[j], "--gpu-deflate")) mf |= AL_MERGE_GPU_DEFLATE;
+			else if (!strcmp(argv[j], "-l") && j + 1 < argc) level = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--piece") && j + 1 < argc) piece = (size_t)strtoull(argv[++j], nullptr, 10);
+			else p.push_back(argv[j]);
+		}
+		if (p.empty() || !o_fn || level < 0 || level > 9) {
+			fprintf(stderr, "Usage: airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
+			                "       (2 to 8 BGZF BAMs, each in coordinate order, merged into OUT.bam on the GPU: the records in order of contig and position, records without a\n"
+			                "       contig last, equal positions with the earlier input first and in input order within one input; OUT.bam's reference list is in1.bam's with the\n"
+			                "       contigs only later inputs name appended, and the later inputs' refIDs are translated; its header text is in1.bam's with SO:coordinate and the\n"
+			                "       later inputs' other lines (a colliding @PG ID gets the suffix .K of input K; a colliding @RG ID is refused); an input that is not in order is\n"
+			                "       refused, nothing is sorted here; --host: the kernels' host twin, no device is opened; --gpu-deflate: OUT.bam's blocks are deflated on the GPU;\n"
+			                "       -t: host threads of the compressor; --piece: inflated bytes per refill of an input's window)\n");
+			return 1;
+		}
+		if (p.size() < 2 || p.size() > 8) { fprintf(stderr, "[ERROR] merge takes 2 to 8 input BAMs, not %zu\n", p.size()); return 1; }
+		for (const char *f : p) if (!strcmp(f, o_fn)) { fprintf(stderr, "[ERROR] merge: the input '%s' is also the output (-o)\n", f); return 1; }
+		if ((mf & AL_MERGE_HOST) && (mf & AL_MERGE_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] merge: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }
+		const int rc2 = al_merge_bams(p.data(), (int)p.size(), o_fn, mf, dev, nt, level, piece, nullptr) == 0 ? 0 : 1;
 		fflush(stderr);
 		_exit(rc2);
 	}

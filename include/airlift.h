@@ -541,6 +541,36 @@ int  al_dbg_lift_sorted_host(const void *bam, size_t n, const char *chain_fn, ui
 int  al_dbg_lift_sorted(int device, const void *bam, size_t n, const char *chain_fn, uint32_t *rec_off, uint32_t *verdict, size_t rec_cap, uint64_t *out4, void *packed, size_t packed_cap, size_t *packed_n,
                         void *arena, size_t arena_cap, size_t *arena_n, uint32_t *perm, uint64_t *sort3, unsigned tap_flags, size_t *held);
 
+/* ---- merge: 2 to 8 coordinate-sorted BAMs merged into one (run_pipeline.sh:116 and :119, samtools merge) ----
+ * Every record of the BGZF files `bam_in[0 .. n_in)`, each in coordinate order, written to `bam_out` in non-decreasing order of the key refID << 32 | pos
+ * (records without a refID last); among equal keys the records of an earlier input come first, within one input the input's order holds.  The output's
+ * reference list is input 1's with the contigs only later inputs name appended; refID and next_refID of a later input's records are translated, every other
+ * byte of a record is as read.  The header text is input 1's with SO:coordinate, then the later inputs' lines that are not yet present (a colliding @PG ID gets
+ * the suffix .K, K the input's number; a colliding @RG ID is refused).  An input that is not in coordinate order, a contig with two lengths, and a later input
+ * whose contigs stand in another order than the merged list are refused.  The function is stated in full in airlift_amd/csrc/al_dev_merge.h.  flags:
+ * AL_MERGE_HOST -- the kernels' host twin, no device is opened (it also takes over, with a notice, where the device or its memory is refused);
+ * AL_MERGE_GPU_DEFLATE -- the packed records are deflated where they lie.  level: 0-9 of the host compressor; piece_bytes: inflated bytes per refill of an
+ * input's window (0: 8 MB).  `bam_out` is unlinked on failure.  0; -1 with a message on stderr; -2 refused input (unsorted, malformed, headers that do not
+ * merge), its message on stderr.  With AL_TIMING=1 one line on stderr ends in "device bytes held at return: N". */
+#define AL_MERGE_HOST 1u
+#define AL_MERGE_GPU_DEFLATE 2u
+typedef struct {
+	uint64_t n_in, records, rounds, refills, bytes_in, held;   /* inputs, records written, rounds of the merge, window refills, inflated bytes, device bytes of the call's account at return */
+	uint64_t records_in[8];                   /* records per input */
+	double   read_s, up_s, inflate_s, walk_s, key_s, merge_s, gather_s, down_s, deflate_s, wall_s;   /* file read, copy up, inflate, walk, keys, bounds + merge, gather, copy down, deflate, wall */
+	int      on_device;                       /* 1: the kernels ran; 0: the host twin */
+} AlMergeStat;
+int  al_merge_bams(const char *const *bam_in, int n_in, const char *bam_out, unsigned flags, int device, int n_threads, int level, size_t piece_bytes, AlMergeStat *stat);
+/* Test taps: k uncompressed BAM streams (header and records) through the round loop of the kernels (al_dbg_merge) or of their host twin (al_dbg_merge_host).
+ * piece: bytes per refill of an input's window; 0: every stream whole, which makes ONE round with every input at eof.  tags / keys[0, *n_out) and
+ * packed[0, *packed_n): tag (input << 28 | record index in the input's window of that round), key and bytes of every merged record, round behind round;
+ * *rounds: the rounds.  0; -1 a device failure; -2 unsorted or malformed input (its message printed); -3 the arrays are too small (the counts are set);
+ * -4 a header is refused.  *held: device bytes of the tap's account at return.  al_dbg_merge_tile: AL_MERGE_TILE, the outputs of one k_merge_tile block. */
+int  al_dbg_merge_host(const void *const *bam, const size_t *n, int k, size_t piece, uint32_t *tags, uint64_t *keys, size_t rec_cap, size_t *n_out, void *packed, size_t packed_cap, size_t *packed_n, uint64_t *rounds);
+int  al_dbg_merge(int device, const void *const *bam, const size_t *n, int k, size_t piece, uint32_t *tags, uint64_t *keys, size_t rec_cap, size_t *n_out, void *packed, size_t packed_cap, size_t *packed_n, uint64_t *rounds,
+                  size_t *held);
+uint32_t al_dbg_merge_tile(void);
+
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
 	uint64_t n_frag, n_reads, n_bases;
