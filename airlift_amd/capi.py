@@ -105,6 +105,27 @@ class MergeStat(C.Structure):
 
 MERGE_HOST = 1                # AL_MERGE_HOST of include/airlift.h
 MERGE_GPU_DEFLATE = 2         # AL_MERGE_GPU_DEFLATE
+MERGE_WRITE_INDEX = 4         # AL_MERGE_WRITE_INDEX: bam_out + ".bai" as index_bam writes it
+LIFT_WRITE_INDEX = 8          # AL_LIFT_WRITE_INDEX: the same for al_lift_bam, with LIFT_SORTED only
+
+
+class BaiStat(C.Structure):
+    """AlBaiStat of al_index_bam."""
+    _fields_ = [("records", C.c_uint64), ("unplaced", C.c_uint64), ("pieces", C.c_uint64), ("bytes_in", C.c_uint64), ("chunks", C.c_uint64), ("bai_bytes", C.c_uint64), ("held", C.c_uint64),
+                ("read_s", C.c_double), ("up_s", C.c_double), ("inflate_s", C.c_double), ("walk_s", C.c_double), ("key_s", C.c_double), ("assemble_s", C.c_double), ("wall_s", C.c_double),
+                ("on_device", C.c_int)]
+
+
+BAI_HOST = 1                  # AL_BAI_HOST of include/airlift.h
+
+
+def index_bam(bam, bai=None, flags=0, device=-1, n_threads=3, piece_bytes=0):
+    """al_index_bam: the BAI of the coordinate-sorted BAM `bam` written to `bai` (None: bam + ".bai").  Returns the BaiStat."""
+    st = BaiStat()
+    rc = load().al_index_bam(os.fsencode(bam), None if bai is None else os.fsencode(bai), flags, device, n_threads, piece_bytes, C.byref(st))
+    if rc != 0:
+        raise AirliftError("al_index_bam failed: %d" % rc)
+    return st
 
 
 def merge_bams(bams_in, bam_out, flags=0, device=-1, n_threads=3, level=5, piece_bytes=0):
@@ -240,6 +261,11 @@ def load():
         L.al_dbg_merge_host.argtypes = [C.POINTER(C.c_char_p), szp, ci, C.c_size_t, u32p, u64p, C.c_size_t, szp, vp, C.c_size_t, szp, u64p]; L.al_dbg_merge_host.restype = ci
         L.al_dbg_merge.argtypes = [ci, C.POINTER(C.c_char_p), szp, ci, C.c_size_t, u32p, u64p, C.c_size_t, szp, vp, C.c_size_t, szp, u64p, szp]; L.al_dbg_merge.restype = ci
         L.al_dbg_merge_tile.argtypes = []; L.al_dbg_merge_tile.restype = C.c_uint32
+    if hasattr(L, "al_index_bam"):   # (bam-index: the BAI of a coordinate-sorted BAM, and its test taps)
+        cs, ci, vp, u32p, u64p, szp = C.c_char_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_size_t)
+        L.al_index_bam.argtypes = [cs, cs, C.c_uint, ci, ci, C.c_size_t, C.POINTER(BaiStat)]; L.al_index_bam.restype = ci
+        L.al_dbg_bai_host.argtypes = [vp, C.c_size_t, u64p, u64p, u32p, C.c_size_t, C.c_uint64, C.c_size_t, vp, C.c_size_t, szp]; L.al_dbg_bai_host.restype = ci
+        L.al_dbg_bai.argtypes = [ci, vp, C.c_size_t, u64p, u64p, u32p, C.c_size_t, C.c_uint64, C.c_size_t, vp, C.c_size_t, szp, szp]; L.al_dbg_bai.restype = ci
     if hasattr(L, "al_dbg_ext_dp"):   # (a test tap: an older library named by AIRLIFT_LIB for A/B timing has none, and the test that calls it then fails by name)
         L.al_dbg_ext_dp.argtypes = [vp, ci, vp, vp, vp, ci, vp]; L.al_dbg_ext_dp.restype = ci
     if hasattr(L, "al_dbg_chain"):

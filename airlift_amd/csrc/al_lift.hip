@@ -35,6 +35,7 @@
 #include "al_lift.h"
 #include "al_dev_walk.h"
 #include "al_run_store.h"
+#include "al_bai.h"
 #include "al_prim.h"
 #include "../../include/airlift.h"
 
@@ -364,7 +365,9 @@ extern "C" uint32_t al_dbg_lift_window(void) { return AL_LIFT_W; }
 extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char *bam_out, const char *bed_out, unsigned flags, int device, int n_threads, int level, size_t piece_bytes, AlLiftStat *stat)
 {
 	const auto t_wall = std::chrono::steady_clock::now();
+	const size_t piece_bytes_arg = piece_bytes;
 	if (stat) memset(stat, 0, sizeof(*stat));
+	if ((flags & AL_LIFT_WRITE_INDEX) && !(flags & AL_LIFT_SORTED)) { fprintf(stderr, "[ERROR] airlift: lift: an index needs a BAM in coordinate order: --write-index goes with --sorted\n"); return -1; }
 	AlLiftChain C; std::string err;
 	if (al_lift_build(chain_fn, C, err)) { fprintf(stderr, "[ERROR] airlift: %s\n", err.c_str()); return -1; }
 	const int fd = open(bam_in, O_RDONLY);
@@ -457,6 +460,10 @@ extern "C" int al_lift_bam(const char *bam_in, const char *chain_fn, const char 
 	if (rc == 0 && sorted && al_env().timing)
 		fprintf(stderr, "[airlift] lift --sorted: %llu pieces in order, %llu pieces sorted, %llu chained onto the run before, %llu spills; sort %.3f s, permuted gather %.3f s, host merge %.3f s\n",
 		        (unsigned long long)run.in_order, (unsigned long long)run.sorted_pieces, (unsigned long long)runs_chained, (unsigned long long)spills, run.sort_s, run.sgather_s, merge_s);
+	if (rc == 0 && sorted && (flags & AL_LIFT_WRITE_INDEX)) {          // the output is closed: the bam-index function over it, with the backend that lifted
+		rc = al_bai_index_file(bam_out, nullptr, strcmp(backend, "host twin") == 0, device, n_threads, piece_bytes_arg, nullptr, nullptr, nullptr);
+		if (rc) fprintf(stderr, "[airlift] lift: '%s' is written, its index is not\n", bam_out);
+	}
 	return rc;
 }
 

@@ -22,10 +22,13 @@
 //                                                                   the three scripts alone, file for file
 //          airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] OLD.fa NEW.fa CHAIN
 //                                                                   run/1_build_exact_chain_file.py: the exact chain file those scripts assume, verified or built on the GPU
-//          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
+//          airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--write-index] [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN.bam
 //                                                                   run_pipeline.sh:92-95 (FastRemap): the constant-region reads moved across the chain file on the GPU
-//          airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN1.bam IN2.bam [IN3.bam ...]
+//          airlift-align merge -o OUT.bam [--write-index] [--host] [--gpu-deflate] [-l LEVEL] [-t N] [--device D] [--piece BYTES] IN1.bam IN2.bam [IN3.bam ...]
 //                 run_pipeline.sh:116 and :119 (samtools merge): 2 to 8 coordinate-sorted BAMs merged into one on the GPU
+//          airlift-align bam-index [--host] [-t N] [--device D] [--piece BYTES] IN.bam [OUT.bai]
+//                 run_pipeline.sh:9, :95 and :119 (samtools index): the BAI of a coordinate-sorted BAM built on the GPU; merge and lift --sorted take --write-index
+//                 (`index` stays the accepted no-op of `bwa index REF`)
 //   PAF    airlift-align -x sr --paf [-c] [--cs] [--paf-no-hit] [--secondary=yes] REF.fa R1 [R2]   PAF instead of SAM; without -c / --cs no base-level alignment (the fork's -x sr without -a)
 //   a8     airlift-align -ax sr --count-candidates REF.fa READS     the as-shipped fork's observable: seed-cluster count on stderr
 // SAM goes to stdout; exit status 0 on success, non-zero on failure (so the caller's pipe fails).
@@ -117,12 +120,14 @@ static int usage()
 	                "       --merged-in; --host: the kernels' host twin, no device is opened; malformed input is refused as FILE:LINE: reason)\n"
 	                "chain-exact: airlift-align chain-exact verify|build [--min-region 100] [--host] [--device D] [-o FILE] old.fa new.fa chain  (1_build_exact_chain_file.py: the two\n"
 	                "       references compared over every block of the chain file on the GPU; verify prints the mismatch lines or PASS VERIFICATION, build the exact chain file)\n"
-	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+	                "lift:  airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--write-index] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
 	                "       (the reads in constant regions moved across the chain file on the GPU; the reads that do not lift leave as the rows extract-reads writes;\n"
 	                "       --sorted: OUT.bam in coordinate order, what samtools sort makes of it)\n"
-	                "merge: airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
+	                "merge: airlift-align merge -o OUT.bam [--write-index] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
 	                "       (2 to 8 coordinate-sorted BGZF BAMs merged into one on the GPU, what samtools merge does at the end of run_pipeline.sh; equal positions: the\n"
-	                "       earlier input first)\n"
+	                "       earlier input first; --write-index: OUT.bam.bai as bam-index writes it)\n"
+	                "bam-index: airlift-align bam-index [--host] [-t N] [--device D] [--piece BYTES] in.bam [out.bai]\n"
+	                "       (the BAI of a coordinate-sorted BGZF BAM built on the GPU, out.bai by default in.bam.bai; lift --sorted and merge take --write-index)\n"
 	                "       airlift-align extract-sequence [--gpu-select[=host]] [--gpu-inflate] [--select-piece BYTES] [--device D] [-t N] reads_1.fq reads_2.fq rows.bed outdir\n"
 	                "       airlift-align remap ... --gpu-select[=host] (the selected names are tested against both FASTQ files on the GPU; =host: by the kernels' host twin)\n");
 	return 1;
@@ -164,6 +169,7 @@ int main(int argc, char **argv)
 			else if (!strcmp(argv[j], "--host")) lf |= AL_LIFT_HOST;
 			else if (!strcmp(argv[j], "--gpu-deflate")) lf |= AL_LIFT_GPU_DEFLATE;
 			else if (!strcmp(argv[j], "--sorted")) lf |= AL_LIFT_SORTED;
+			else if (!strcmp(argv[j], "--write-index")) lf |= AL_LIFT_WRITE_INDEX;
 			else if (!strcmp(argv[j], "--sort-mem") && j + 1 < argc) setenv("AL_SORT_MEM", std::to_string(parse_num(argv[++j], "--sort-mem")).c_str(), 1);   // --sorted: bytes held before the held runs are merged into a file
 			else if (!strcmp(argv[j], "-l") && j + 1 < argc) level = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
@@ -172,7 +178,7 @@ int main(int argc, char **argv)
 			else p.push_back(argv[j]);
 		}
 		if (p.size() != 1 || !c_fn || !o_fn || !b_fn || level < 0 || level > 9) {
-			fprintf(stderr, "Usage: airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
+			fprintf(stderr, "Usage: airlift-align lift --chain CHAIN -o OUT.bam --unmapped-bed FILE [--sorted [--sort-mem BYTES]] [--write-index] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in.bam\n"
 			                "       (every record of in.bam, a BGZF file, through the chain file on the GPU: a mapped read that lies wholly and uniquely inside one block of a '+' chain\n"
 			                "       gets its new contig, position and bin and stays in OUT.bam, in input order and unsorted; one that does not becomes a row of FILE -- chrom start end\n"
 			                "       name[.1|.2] MAPQ CIGAR, what extract-reads writes -- and is re-aligned; unmapped reads are kept; --host: the kernels' host twin, no device is opened;\n"
@@ -183,6 +189,7 @@ int main(int argc, char **argv)
 			return 1;
 		}
 		if ((lf & AL_LIFT_HOST) && (lf & AL_LIFT_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] lift: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }
+		if ((lf & AL_LIFT_WRITE_INDEX) && !(lf & AL_LIFT_SORTED)) { fprintf(stderr, "[ERROR] lift: an index needs a BAM in coordinate order: --write-index goes with --sorted\n"); return 1; }
 		const int rc2 = al_lift_bam(p[0], c_fn, o_fn, b_fn, lf, dev, nt, level, piece, nullptr) == 0 ? 0 : 1;
 		fflush(stderr);
 		_exit(rc2);
@@ -193,6 +200,7 @@ int main(int argc, char **argv)
 			if (!strcmp(argv[j], "-o") && j + 1 < argc) o_fn = argv[++j];
 			else if (!strcmp(argv[j], "--host")) mf |= AL_MERGE_HOST;
 			else if (!strcmp(argv[j], "--gpu-deflate")) mf |= AL_MERGE_GPU_DEFLATE;
+			else if (!strcmp(argv[j], "--write-index")) mf |= AL_MERGE_WRITE_INDEX;
 			else if (!strcmp(argv[j], "-l") && j + 1 < argc) level = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
 			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
@@ -200,7 +208,7 @@ int main(int argc, char **argv)
 			else p.push_back(argv[j]);
 		}
 		if (p.empty() || !o_fn || level < 0 || level > 9) {
-			fprintf(stderr, "Usage: airlift-align merge -o OUT.bam [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
+			fprintf(stderr, "Usage: airlift-align merge -o OUT.bam [--write-index] [--host] [--gpu-deflate] [-l LEVEL=5] [-t N] [--device D] [--piece BYTES] in1.bam in2.bam [in3.bam ...]\n"
 			                "       (2 to 8 BGZF BAMs, each in coordinate order, merged into OUT.bam on the GPU: the records in order of contig and position, records without a\n"
 			                "       contig last, equal positions with the earlier input first and in input order within one input; OUT.bam's reference list is in1.bam's with the\n"
 			                "       contigs only later inputs name appended, and the later inputs' refIDs are translated; its header text is in1.bam's with SO:coordinate and the\n"
@@ -213,6 +221,28 @@ int main(int argc, char **argv)
 		for (const char *f : p) if (!strcmp(f, o_fn)) { fprintf(stderr, "[ERROR] merge: the input '%s' is also the output (-o)\n", f); return 1; }
 		if ((mf & AL_MERGE_HOST) && (mf & AL_MERGE_GPU_DEFLATE)) { fprintf(stderr, "[ERROR] merge: --host opens no device: it cannot be combined with --gpu-deflate\n"); return 1; }
 		const int rc2 = al_merge_bams(p.data(), (int)p.size(), o_fn, mf, dev, nt, level, piece, nullptr) == 0 ? 0 : 1;
+		fflush(stderr);
+		_exit(rc2);
+	}
+	if (!strcmp(argv[1], "bam-index")) {           // run_pipeline.sh:9, :95 and :119 (samtools index IN.bam): the BAI of a coordinate-sorted BAM
+		int dev = -1, nt = 3; unsigned xf = 0; size_t piece = 0; std::vector<const char *> p;
+		for (int j = 2; j < argc; ++j) {
+			if (!strcmp(argv[j], "--host")) xf |= AL_BAI_HOST;
+			else if (!strcmp(argv[j], "-t") && j + 1 < argc) nt = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--device") && j + 1 < argc) dev = atoi(argv[++j]);
+			else if (!strcmp(argv[j], "--piece") && j + 1 < argc) piece = (size_t)strtoull(argv[++j], nullptr, 10);
+			else p.push_back(argv[j]);
+		}
+		if (p.size() < 1 || p.size() > 2 || p[0][0] == '-') {
+			fprintf(stderr, "Usage: airlift-align bam-index [--host] [-t N] [--device D] [--piece BYTES] in.bam [out.bai]\n"
+			                "       (the index of in.bam, a BGZF BAM in coordinate order, built on the GPU and written to out.bai, by default in.bam.bai: the members are inflated and\n"
+			                "       the records walked in pieces; a record's bin is reg2bin of its own interval, a run of records of one bin is one chunk, bins are not folded into\n"
+			                "       their parents; the linear index, pseudo-bin 37450 and n_no_coor are written; contigs end at 2^29, CSI is not built; a BAM that is not in order\n"
+			                "       is refused, nothing is sorted here; --host: the kernels' host twin, no device is opened; -t: host threads of the twin's inflater; --piece:\n"
+			                "       inflated bytes per piece)\n");
+			return 1;
+		}
+		const int rc2 = al_index_bam(p[0], p.size() > 1 ? p[1] : nullptr, xf, dev, nt, piece, nullptr) == 0 ? 0 : 1;
 		fflush(stderr);
 		_exit(rc2);
 	}

@@ -42,6 +42,7 @@
 #include "al_dev_inflate.h"
 #include "al_bam.h"
 #include "al_merge.h"
+#include "al_bai.h"
 #include "al_dev_walk.h"
 #include "al_env.h"
 #include "../../include/airlift.h"
@@ -506,6 +507,10 @@ extern "C" int al_merge_bams(const char *const *bam_in, int n_in, const char *ba
 		fprintf(stderr, "[airlift] merge: %d inputs into '%s' (%s): %s records, %llu rounds, %llu refills, %llu bytes in; file read %.3f s, copy up %.3f s, inflate %.3f s, walk %.3f s, keys %.3f s, bounds and merge %.3f s, gather %.3f s, copy down %.3f s, deflate %.3f s, wall %.3f s; device bytes held at return: %zu\n",
 		        n_in, bam_out, backend, per.c_str(), (unsigned long long)run.rounds, (unsigned long long)run.refills, (unsigned long long)run.bytes_in,
 		        run.read_s, run.up_s, run.inflate_s, run.walk_s, run.key_s, run.merge_s, run.gather_s, run.down_s, deflate_s, wall, acct.load());
+	}
+	if (rc == 0 && (flags & AL_MERGE_WRITE_INDEX)) {                    // the output is closed: the bam-index function over it, with the backend that merged
+		rc = al_bai_index_file(bam_out, nullptr, strcmp(backend, "host twin") == 0, device, n_threads, piece_bytes, nullptr, nullptr, nullptr);
+		if (rc) fprintf(stderr, "[airlift] merge: '%s' is written, its index is not\n", bam_out);
 	}
 	return rc;
 }

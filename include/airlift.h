@@ -571,6 +571,33 @@ int  al_dbg_merge(int device, const void *const *bam, const size_t *n, int k, si
                   size_t *held);
 uint32_t al_dbg_merge_tile(void);
 
+/* ---- bam-index: the BAI of a coordinate-sorted BAM (run_pipeline.sh:9, :95 and :119, samtools index) ----
+ * The BGZF file `bam`, in coordinate order as `merge` requires it, is inflated and walked in pieces on `device` (-1: the default device) and its index is
+ * written to `bai` (NULL: `bam` + ".bai") through a temporary name beside it.  The index is defined by the rules of airlift_amd/csrc/al_dev_bai.h -- bins by
+ * reg2bin of [max(pos, 0), + reflen), one chunk per run of records of one bin, bins not folded into their parents, the linear index, pseudo-bin 37450 and
+ * n_no_coor -- and answers the query procedure of the SAM specification; byte parity with samtools index is not claimed.  flags: AL_BAI_HOST -- the kernels'
+ * host twin, no device is opened (it also takes over, with a notice, where the device or its memory is refused).  n_threads: host threads of the twin's
+ * inflater; piece_bytes: inflated bytes per piece (0: 8 MB).  0; -1 with a message on stderr; -2 refused input (not in coordinate order, malformed, a record
+ * that ends beyond 2^29 or beyond its contig), its message on stderr.  No output file is left behind on failure.  With AL_TIMING=1 one line on stderr ends in
+ * "device bytes held at return: N".  AL_MERGE_WRITE_INDEX / AL_LIFT_WRITE_INDEX (the latter with AL_LIFT_SORTED only): the same function over `bam_out` once
+ * it is closed, with the call's backend, written to `bam_out` + ".bai". */
+#define AL_BAI_HOST 1u
+#define AL_MERGE_WRITE_INDEX 4u
+#define AL_LIFT_WRITE_INDEX 8u
+typedef struct {
+	uint64_t records, unplaced, pieces, bytes_in, chunks, bai_bytes, held;   /* records, those without a refID, pieces walked, inflated bytes, chunks written (pseudo-bins apart), bytes of the index, device bytes of the call's account at return */
+	double   read_s, up_s, inflate_s, walk_s, key_s, assemble_s, wall_s;    /* file read, copy up, inflate, walk, keys + runs + linear index, host assembly and write, wall */
+	int      on_device;                       /* 1: the kernels ran; 0: the host twin */
+} AlBaiStat;
+int  al_index_bam(const char *bam, const char *bai, unsigned flags, int device, int n_threads, size_t piece_bytes, AlBaiStat *stat);
+/* Test taps: one uncompressed BAM stream (header and records) with the table of the BGZF members it would lie in -- file offset, stream offset and isize of
+ * each, file_end: the file offset behind the last of them -- through the piece loop of the kernels (al_dbg_bai) or of their host twin (al_dbg_bai_host) with
+ * pieces of `piece` bytes (0: the stream whole).  bai[0, *bai_n): the index (room for bai_cap bytes).  0; -1 a device failure; -2 refused input (its message
+ * printed); -3 bai_cap is too small (*bai_n is set); -4 the header is refused.  *held: device bytes of the tap's account at return. */
+int  al_dbg_bai_host(const void *bam, size_t n, const uint64_t *m_file, const uint64_t *m_stream, const uint32_t *m_isize, size_t n_mem, uint64_t file_end, size_t piece, void *bai, size_t bai_cap, size_t *bai_n);
+int  al_dbg_bai(int device, const void *bam, size_t n, const uint64_t *m_file, const uint64_t *m_stream, const uint32_t *m_isize, size_t n_mem, uint64_t file_end, size_t piece, void *bai, size_t bai_cap, size_t *bai_n,
+                size_t *held);
+
 /* per-batch work counters + per-kernel HIP-event times of the last al_batch_run */
 typedef struct {
 	uint64_t n_frag, n_reads, n_bases;
